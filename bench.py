@@ -17,6 +17,12 @@ frames/sec = n_gpus * frames_per_window / (steps_per_window * sec_per_step), ste
 Default K = one whole window (the timed region begins at a window start and so contains the per-window work once per
 20 steps, the product's own ratio); W = 3 warm-up steps are the tail of the window before it.
 Prints one JSON line (rank 0).
+
+A plain run only sets up, warms up, times the K steps and prints the line.  `--full` adds every side measurement:
+the instrumented roofline pass (`roofline`, `kernel_family`, `winograd`, `--shapes`), the matrix-rate probe, `two_chains`,
+the VAE timing, `other_configs` and the CPU baselines.  `--dump-outputs DIR` writes what the last timed step returned to
+its caller (`videos`: the window's output latents) as DIR/videos.npy, float32; the inputs are seeded, so two builds
+can be compared output for output.
 """
 from __future__ import annotations
 
@@ -67,18 +73,25 @@ def parse():
     ap.add_argument("--size", type=int, default=None, help="override: frame height = width in pixels")
     ap.add_argument("--controlnets", type=int, default=None, help="override the config's number of ControlNets")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement beside the headline (roofline pass, matrix-rate probe, two_chains, VAE timing, "
+                         "other_configs, CPU baselines; each still switched off by its --no-* option).  Off: a plain run sets up, warms "
+                         "up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to its caller as DIR/<name>.npy (float32, "
+                         "at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baselines")
     ap.add_argument("--cpu-baseline-config2", action="store_true", help=argparse.SUPPRESS)  # (old spelling: now the default)
     ap.add_argument("--no-cpu-baseline-config2", action="store_true",
-                    help="skip the full config-2 denoise step of the fp32 oracle on the host cores (44.6 TFLOP, ControlNet + UNet3D: ~100 s "
+                    help="(--full) skip the full config-2 denoise step of the fp32 oracle on the host cores (44.6 TFLOP, ControlNet + UNet3D: ~100 s "
                          "of CPU work and ~40 GB of host memory; measured once per host and cached in the temp directory; skipped by "
                          "itself when less than 48 GB of host memory are available)")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) skip the instrumented roofline pass")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short passes of BASELINE configs 1, 3, 4, 5 and bf16 config 2 that the default single-GPU config-2 run "
+                    help="(--full) skip the short passes of BASELINE configs 1, 3, 4, 5 and bf16 config 2 that a --full single-GPU config-2 run "
                          "appends as `other_configs` (outside `value`; ~2 min)")
-    ap.add_argument("--shapes", action="store_true", help="also print the per-shape GEMM/conv table (stderr)")
-    ap.add_argument("--no-vae", action="store_true", help="skip the VAE encode/decode timing (reported beside the metric)")
+    ap.add_argument("--shapes", action="store_true", help="(--full) also print the per-shape GEMM/conv table (stderr)")
+    ap.add_argument("--no-vae", action="store_true", help="(--full) skip the VAE encode/decode timing (reported beside the metric)")
     ap.add_argument("--no-overlap", action="store_true", help="run the ControlNet stack on the main stream (no 2nd-stream overlap)")
     ap.add_argument("--no-fuse-adds", action="store_true", help="13 separate ControlNet residual adds instead of the zero convolutions' epilogues (A/B)")
     ap.add_argument("--no-graph", action="store_true",
@@ -96,7 +109,7 @@ def parse():
                          "weight-arena broadcast, barriers, max-over-ranks timing, rank-0 JSON with `dry_run: true` and "
                          "`value: null`.  Never a measurement; used by tests/test_bench_launch.py")
     ap.add_argument("--chains", type=int, default=2,
-                    help="after the headline (single GPU, outside `value`): N independent windows in flight on the one GPU (controlanimate_amd/chains.py), "
+                    help="(--full) after the headline (single GPU, outside `value`): N independent windows in flight on the one GPU (controlanimate_amd/chains.py), "
                          "reported as `two_chains`; 1 skips it")
     ap.add_argument("--window-graph", action="store_true",
                     help="ControlAnimationPipeline.window_graph: a whole window as ONE captured hipGraph, one replay per window, no per-step events (A/B; "
@@ -107,6 +120,11 @@ def parse():
     args = ap.parse_args()
     if args.steps <= 0:
         args.steps = int(CONFIGS[args.config]["steps"])
+    if not args.full:
+        if args.shapes:
+            ap.error("--shapes reads the instrumented roofline pass: add --full")
+        args.no_roofline = args.no_vae = args.no_other_configs = args.no_cpu_baseline = True
+        args.chains = 1
     return args
 
 
@@ -587,6 +605,28 @@ def matrix_rate_vs_operand_data(dtype):
         del a, w
     return res
 
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname: str, arrays: dict, limit_bytes: int = DUMP_LIMIT_BYTES) -> dict:
+    """`--dump-outputs`: every array as DIR/<name>.npy in float32, in its own shape.  An array beyond its share of the limit is
+    written as a fixed sample instead: the values at flat indices drawn without replacement by a generator seeded with 0,
+    in ascending index order -- the same elements in every run.  Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = limit_bytes // (4 * max(1, len(arrays)))  # float32 elements per array
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if a.numel() > share:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, f"{name}.npy"), a.numpy())
+        written[name] = tuple(a.shape)
+    return written
+
+
 def thread_cpu_seconds() -> dict:
     """user + system CPU seconds of every thread of this process (/proc/self/task/*/stat, fields 14 and 15), keyed "tid:name"."""
     out, tick = {}, os.sysconf("SC_CLK_TCK")
@@ -817,6 +857,8 @@ def measure(args, timer, rank, world, device, headline=True):
         else:
             step_ms.append(prev.elapsed_time(e))
             prev = e
+    if headline and rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"videos": state["latents"]})  # (the roofline pass below runs more steps)
     step_ms.sort()
     median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
     replays_timed = state.get("replays", 0) - replays_before

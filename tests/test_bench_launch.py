@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -73,3 +75,47 @@ def test_committed_bench_line_keeps_the_driver_contract():
         assert key in c, key
     assert c["kind"] in ("port", "reference") and c["cores"] >= 1
     assert c["config2_step"]["sec_per_step"] > 100 * d["ms_per_step"] * 1e-3  # the CPU port beside it, never the target
+
+
+def test_dump_outputs_writes_float32_and_a_fixed_sample_beyond_the_limit(tmp_path):
+    import numpy as np
+    import torch
+    import bench
+    small = torch.randn(1, 4, 2, 3, 3, dtype=torch.float16)
+    big = torch.arange(1000, dtype=torch.float64)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), {"small": small, "big": big}, limit_bytes=2 * 4 * 100)
+    assert shapes == {"small": (1, 4, 2, 3, 3), "big": (100,)}
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.float().numpy())
+    b = np.load(tmp_path / "a" / "big.npy")
+    assert b.dtype == np.float32 and len(np.unique(b)) == 100 and np.all(np.diff(b) > 0)  # distinct elements, in index order
+    bench.dump_outputs(str(tmp_path / "b"), {"small": small, "big": big}, limit_bytes=2 * 4 * 100)
+    assert np.array_equal(np.load(tmp_path / "b" / "big.npy"), b)  # the same sample in every run
+
+
+def test_plain_run_refuses_what_only_full_measures():
+    r = _run(["--steps", "1", "--shapes"])
+    assert r.returncode != 0 and "--full" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_times_k_steps_and_dumps_what_the_last_step_returned(tmp_path):
+    """A plain `bench.py` run: K timed steps, the headline keys, none of the side measurements of --full, and the last timed
+    step's output written by --dump-outputs (config 2: the window's [1, 4, 16, 64, 64] latents)."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["metric"] == "frames_per_sec" and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "fp16"
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    cfg = d["config"]
+    assert abs(cfg["frames_per_window"] / (cfg["steps_per_window"] * d["ms_per_step"] * 1e-3) - d["value"]) / d["value"] < 1e-3
+    for key in ("roofline", "kernel_family", "other_configs", "cpu_baseline"):
+        assert key not in d, key
+    assert d["vae"] is None and d["two_chains"] is None
+    v = np.load(tmp_path / "videos.npy")
+    assert v.dtype == np.float32 and v.shape == (1, 4, 16, 64, 64) and np.isfinite(v).all() and np.abs(v).max() > 0

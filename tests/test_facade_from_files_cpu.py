@@ -108,7 +108,7 @@ def test_constructor_builds_everything_from_local_files(model_tree):
     pipe = ControlAnimatePipeline(_config(tree))          # <- scripts/vid2vid.py:152
     p = pipe.pipeline
     # UNet: 2-D weights loaded, motion module merged, LoRA fused with scale * alpha / rank
-    sd = p.unet.state_dict()
+    sd = {k: v.cpu() for k, v in p.unet.state_dict().items()}  # (with a GPU present the facade's models live on it)
     k = "down_blocks.0.resnets.0.conv1.weight"
     assert torch.equal(sd[k], tree["unet_sd"][k])
     mk = next(iter(tree["mm"]))
@@ -126,7 +126,7 @@ def test_constructor_builds_everything_from_local_files(model_tree):
     assert p.vae is not None and p.text_encoder is not None and p.tokenizer is not None
     # textual inversion: 8 new tokens, their rows in the token table, and the prompts expanded (reference :118-121)
     assert len(p.tokenizer) == tree["nvocab"] + 8
-    table = p.text_encoder.text_model.embeddings.token_embedding.weight
+    table = p.text_encoder.text_model.embeddings.token_embedding.weight.cpu()
     assert table.shape[0] == tree["nvocab"] + 8
     for i, tok in enumerate(["easynegative"] + [f"easynegative_{j}" for j in range(1, 8)]):
         assert torch.equal(table[p.tokenizer.convert_tokens_to_ids(tok)], tree["ti"][i])
@@ -164,8 +164,9 @@ def test_control_image_processor_matches_the_reference_settings():
     assert norm.shape == (1, 3, 64, 64) and norm.min() >= -1 and norm.min() < 0
 
 
-@pytest.mark.skipif(not os.path.isfile("/root/reference/models/TI/easynegative.safetensors"), reason="reference tree absent")
 def test_the_reference_textual_inversion_file_is_readable():
+    # the reference's models/TI/easynegative.safetensors, stored as a fixture (one F32 tensor `emb_params` [8, 768])
     from controlanimate_amd.local_models import read_textual_inversion
-    tokens, emb = read_textual_inversion("/root/reference/models/TI/easynegative.safetensors", token="easynegative")
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "easynegative.safetensors")
+    tokens, emb = read_textual_inversion(path, token="easynegative")
     assert tokens == ["easynegative"] + [f"easynegative_{i}" for i in range(1, 8)] and tuple(emb.shape) == (8, 768)

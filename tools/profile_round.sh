@@ -1,6 +1,6 @@
 #!/bin/bash
 # Evidence passes of a round, on the GPU box:  bash tools/profile_round.sh round3
-# 1 x kernel trace + stats of the DEFAULT bench command, 4 x PMC passes of a short single-stream eager run (separate
+# 1 x kernel trace + stats of the --full bench command, 4 x PMC passes of a short single-stream eager run (separate
 # passes: gpurun refuses --pmc together with the other trace domains; FETCH_SIZE and WRITE_SIZE do not fit one pass).
 # Summaries are written into profiles/<tag>_* by the tools/pmc_* scripts.  The program itself comes after `--`.
 set -u
@@ -10,7 +10,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/${TAG}_prof
 mkdir -p "$OUT" profiles
 PMCARGS="--steps 2 --warmup 1 --no-cpu-baseline --no-vae --no-roofline --no-overlap --no-graph --no-other-configs --chains 1"
-rocprofv3 --kernel-trace --stats -f csv -d "$OUT/trace" -o run -- python3 bench.py --no-cpu-baseline --no-vae --no-other-configs --chains 1 --shapes > "$OUT/trace_bench.json" 2> "$OUT/trace.err"
+rocprofv3 --kernel-trace --stats -f csv -d "$OUT/trace" -o run -- python3 bench.py --full --no-cpu-baseline --no-vae --no-other-configs --chains 1 --shapes > "$OUT/trace_bench.json" 2> "$OUT/trace.err"
 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/trace1s" -o run -- python3 bench.py --no-cpu-baseline --no-vae --no-roofline --no-overlap --no-graph --no-other-configs --chains 1 > "$OUT/trace1s_bench.json" 2> "$OUT/trace1s.err"
 rocprofv3 --pmc FETCH_SIZE -f csv -d "$OUT/fetch" -o run -- python3 bench.py $PMCARGS > /dev/null 2> "$OUT/fetch.err"
 rocprofv3 --pmc WRITE_SIZE -f csv -d "$OUT/write" -o run -- python3 bench.py $PMCARGS > /dev/null 2> "$OUT/write.err"
