@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("CA_HIP_LIB") or os.path.join(_HERE, "csrc", "libcontr
 
 CA_BF16, CA_F16 = 0, 1
 CA_ACT_NONE, CA_ACT_SILU = 0, 1
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 class CAHipUnavailable(RuntimeError):
@@ -132,6 +132,17 @@ class AttnArgs(C.Structure):
     ]
 
 
+class ConvNarrowArgs(C.Structure):  # ABI v14: ca_conv3x3_narrow_args (the RRDBNet upscaler)
+    _fields_ = [
+        ("x", C.c_void_p), ("w", C.c_void_p), ("y", C.c_void_p), ("bias", C.c_void_p), ("r1", C.c_void_p), ("r2", C.c_void_p),
+        ("ldx", C.c_int64), ("ldy", C.c_int64), ("ld_r1", C.c_int64), ("ld_r2", C.c_int64),
+        ("images", C.c_int32), ("hin", C.c_int32), ("win", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32),
+        ("channel_offset", C.c_int32), ("upsample", C.c_int32), ("leaky_relu", C.c_int32),
+        ("s0", C.c_float), ("s1", C.c_float), ("s2", C.c_float),
+        ("out_u8", C.c_int32), ("dtype", C.c_int32),
+    ]
+
+
 # symbol -> (restype, argtypes); this table is also what tests/test_capi_symbols.py checks
 # against the declarations in include/controlanimate_hip.h.
 SYMBOLS = {
@@ -183,6 +194,12 @@ SYMBOLS = {
                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.POINTER(C.c_float), C.c_float, C.c_void_p]),
     "ca_lincomb": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int32, C.c_int64, C.c_void_p]),
+    # ABI v14
+    "ca_conv3x3_narrow": (C.c_int, [C.POINTER(ConvNarrowArgs), C.c_void_p]),
+    "ca_conv3x3_narrow_plan_name": (C.c_int, [C.POINTER(ConvNarrowArgs), C.c_char_p, C.c_int32]),
+    "ca_rgb8_to_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ca_resize_lanczos4_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -12,7 +12,7 @@ import torch
 
 from . import _capi
 from .context import dispatch
-from ._capi import (AttnArgs, ConvArgs, FfArgs, TattnArgs, XattnArgs, GemmArgs, GroupNormArgs, LayerNormArgs, CA_ACT_NONE,
+from ._capi import (AttnArgs, ConvArgs, ConvNarrowArgs, FfArgs, TattnArgs, XattnArgs, GemmArgs, GroupNormArgs, LayerNormArgs, CA_ACT_NONE,
                     CA_ACT_SILU, CA_BF16, CA_F16, check, lib)
 
 ACT_NONE, ACT_SILU = CA_ACT_NONE, CA_ACT_SILU
@@ -652,3 +652,58 @@ def cfg_combined_eps(eps: torch.Tensor, rep: int, guidance: float, latents: torc
     (ca_cfg_scheduler_step with prev := eps; the multistep samplers keep it as history)."""
     e, _ = cfg_scheduler_step(eps, rep, guidance, latents, None, [0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0], 0.0)
     return e
+
+
+# ---- ABI v14: the RRDBNet upscaler (controlanimate_amd/upscaler.py) ----------------------------------------------------------
+
+def conv3x3_narrow(x: torch.Tensor, w: torch.Tensor, y: torch.Tensor, *, cin: int, cout: int, bias: Optional[torch.Tensor] = None,
+                   channel_offset: int = 0, upsample: bool = False, leaky_relu: bool = False, s0: float = 1.0,
+                   r1: Optional[torch.Tensor] = None, s1: float = 0.0, r2: Optional[torch.Tensor] = None, s2: float = 0.0,
+                   out_u8: bool = False) -> torch.Tensor:
+    """ca_conv3x3_narrow into the caller's `y`: x [images, H, W, ldx] (its first `cin` channels are read), w packed
+    [round_up(cout, 16), 3, 3, round_up(cin, 32)], y [images, Hout, Wout, ldy] (channels channel_offset .. + cout written) or, with
+    out_u8, uint8 [images, Hout, Wout, 3].  r1 / r2 [images, Hout, Wout, ld] (their first cout channels are read)."""
+    _req_cuda(x, w, y, bias, r1, r2)
+    for t in (x, w, y, r1, r2):
+        assert t is None or t.is_contiguous()
+    images, hin, win, ldx = x.shape
+    hout, wout = (2 * hin, 2 * win) if upsample else (hin, win)
+    if out_u8:
+        assert y.dtype == torch.uint8 and tuple(y.shape) == (images, hout, wout, 3)
+    else:
+        assert y.dtype == x.dtype and tuple(y.shape[:3]) == (images, hout, wout)
+    for r in (r1, r2):
+        assert r is None or (r.dtype == x.dtype and tuple(r.shape[:3]) == (images, hout, wout))
+    assert w.dtype == x.dtype and tuple(w.shape) == ((cout + 15) // 16 * 16, 3, 3, (cin + 31) // 32 * 32)
+    assert bias is None or (bias.dtype == torch.float32 and bias.numel() == cout)
+    args = ConvNarrowArgs(x=_p(x), w=_p(w), y=_p(y), bias=_p(bias), r1=_p(r1), r2=_p(r2), ldx=ldx, ldy=0 if out_u8 else y.shape[3],
+                          ld_r1=r1.shape[3] if r1 is not None else 0, ld_r2=r2.shape[3] if r2 is not None else 0,
+                          images=images, hin=hin, win=win, cin=cin, cout=cout, channel_offset=channel_offset, upsample=int(upsample),
+                          leaky_relu=int(leaky_relu), s0=s0, s1=s1, s2=s2, out_u8=int(out_u8), dtype=dt_code(x.dtype))
+    _record_plan(lib().ca_conv3x3_narrow_plan_name, args)
+    check(lib().ca_conv3x3_narrow(C.byref(args), _stream()), "ca_conv3x3_narrow")
+    return y
+
+
+def rgb8_to_nhwc(frames: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """uint8 [n, H, W, 3] -> [n, H, W, 8] `dtype`, channels reversed, /255, zero padded (ca_rgb8_to_nhwc)."""
+    _req_cuda(frames)
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous()
+    n, h, w, _ = frames.shape
+    out = torch.empty((n, h, w, 8), device=frames.device, dtype=dtype)
+    check(lib().ca_rgb8_to_nhwc(_p(frames), _p(out), n, h, w, dt_code(dtype), _stream()), "ca_rgb8_to_nhwc")
+    return out
+
+
+def resize_lanczos4_u8(frames: torch.Tensor, dh: int, dw: int, xofs: torch.Tensor, alpha: torch.Tensor, yofs: torch.Tensor,
+                       beta: torch.Tensor) -> torch.Tensor:
+    """uint8 [n, sh, sw, 3] -> [n, dh, dw, 3] with the INTER_LANCZOS4 tables of upscaler.lanczos4_tables (ca_resize_lanczos4_u8)."""
+    _req_cuda(frames, xofs, alpha, yofs, beta)
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous()
+    assert xofs.dtype == yofs.dtype == torch.int32 and alpha.dtype == beta.dtype == torch.int16
+    assert xofs.numel() == dw and alpha.numel() == 8 * dw and yofs.numel() == dh and beta.numel() == 8 * dh
+    n, sh, sw, _ = frames.shape
+    out = torch.empty((n, dh, dw, 3), device=frames.device, dtype=torch.uint8)
+    check(lib().ca_resize_lanczos4_u8(_p(frames), _p(out), n, sh, sw, dh, dw, _p(xofs), _p(alpha), _p(yofs), _p(beta), _stream()),
+          "ca_resize_lanczos4_u8")
+    return out

@@ -7,6 +7,8 @@
     animatediff/pipelines/controlanimation_pipeline.py:160-163  VaeImageProcessor(do_normalize=False) for control images
     diffusers TextualInversionLoaderMixin (third party): load_textual_inversion / maybe_convert_prompt, restated for the
     one embedding file the reference loads (models/TI/easynegative.safetensors, controlanimate_pipeline.py:118-121)
+    modules/upscaler.py:33-47                  the Real-ESRGAN anime-6B weights (weights/RealESRGAN_x4plus_anime_6B.pth), read
+                                               as RealESRGANer does (params_ema before params); nothing is downloaded
 
 Host-side file handling only; the models themselves run on the HIP path.
 """
@@ -263,3 +265,23 @@ def maybe_convert_prompt(prompt, tokenizer):
             i += 1
         prompt = prompt.replace(tok, repl)
     return prompt
+
+
+REALESRGAN_ANIME_6B_PATH = os.path.join("weights", "RealESRGAN_x4plus_anime_6B.pth")  # modules/upscaler.py:33
+
+
+def load_realesrgan_state_dict(path: str = REALESRGAN_ANIME_6B_PATH) -> Dict[str, torch.Tensor]:
+    """The RRDBNet state dict of a Real-ESRGAN `.pth` file: `torch.load(weights_only=True)`, then `params_ema` if present, else
+    `params` (RealESRGANer.__init__'s choice), else the mapping itself.  The reference downloads the file when it is missing
+    (upscaler.py:34-40); here a missing file is an error naming the path."""
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"Real-ESRGAN weights {path} do not exist (there is no network to download them; the reference "
+                                f"reads {REALESRGAN_ANIME_6B_PATH})")
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    if isinstance(sd, dict) and "params_ema" in sd:
+        sd = sd["params_ema"]
+    elif isinstance(sd, dict) and "params" in sd:
+        sd = sd["params"]
+    if not isinstance(sd, dict):
+        raise ValueError(f"{path}: not a state dict")
+    return sd

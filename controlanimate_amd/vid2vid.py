@@ -1,6 +1,7 @@
 """Host window orchestrator: the sliding-window loop of scripts/vid2vid.py:165-262
-around `ControlAnimatePipeline.animate`, without ffmpeg / OmegaConf / the upscaler (frames come from and
-go to any iterable / callable; the reference pipes raw RGB through ffmpeg, :93-136, :259-260).
+around `ControlAnimatePipeline.animate`, without ffmpeg / OmegaConf (frames come from and go to any iterable / callable;
+the reference pipes raw RGB through ffmpeg, :93-136, :259-260).  The Real-ESRGAN upscaler is opt-in: pass
+`upscaler=` (upscaler.Upscaler, or upscaler.upscaler_from_config(config)) to `run_windows` / `run_video_sharded`.
 
 Per window (file:line of the reference behaviour mirrored):
   :168-175  batch = the previous window's last `overlap_length` INPUT frames + (frame_count - overlaps) new ones
@@ -17,6 +18,8 @@ Per window (file:line of the reference behaviour mirrored):
   :226-228  cross-fade: frames[i] = blend(frames[i], previous_overlap_output[i], (n - i - 0.5) / n)
   :230-232  carry the blended tail and the matching input frames to the next window
   :235      emit len(batch) - overlaps frames, or the whole batch once the requested frame count is reached
+  :236-242  with an upscaler, every EMITTED frame is upscaled (after colour match and blend); the carried overlap, the colour
+            reference and the blend stay at the generated size
 
 Multi-GPU: with overlap_strength >= 1 and no IP-Adapter a window's denoising does not depend on
 its predecessor's pixels, so windows can be denoised on different ranks (window_shard.windows_for_rank)
@@ -172,7 +175,9 @@ def ffmpeg_reader_cmd(path: str, width: int, height: int, fps: float, start_time
 
 
 def ffmpeg_writer_cmd(path: str, width: int, height: int, fps: float, crf: int = 17, ffmpeg_path: str = "ffmpeg") -> List[str]:
-    """The encoder command of scripts/vid2vid.py:120-136: raw rgb24 frames on stdin -> h264 (argv list, no shell)."""
+    """The encoder command of scripts/vid2vid.py:120-136: raw rgb24 frames on stdin -> h264 (argv list, no shell).
+    width x height is the size of the frames WRITTEN: with an upscaler, int(upscale * w) x int(upscale * h) of the generated
+    w x h (:118-119; upscaler.output_size)."""
     return [str(ffmpeg_path), "-loglevel", "error", "-y", "-f", "rawvideo", "-pix_fmt", "rgb24", "-s", f"{width}x{height}", "-r", str(fps),
             "-i", "-", "-c:v", "libx264", "-pix_fmt", "yuv420p", "-crf", str(crf), str(path)]
 
@@ -234,11 +239,13 @@ AnimateFn = Callable[[List, Optional[List], WindowConfig], List]
 
 
 def run_windows(input_frames: Optional[Iterable], animate: AnimateFn, cfg: WindowConfig, total_frames: Optional[int] = None,
-                match_colors: Optional[Callable[[Sequence, object], List]] = match_colors) -> Iterator[List]:
+                match_colors: Optional[Callable[[Sequence, object], List]] = match_colors, upscaler=None) -> Iterator[List]:
     """Yields the output frames of each window, in order (what the reference writes to the encoder).
     input_frames: iterable of frames (vid2vid) or None (text-to-video: `total_frames` must be given and the
     batches are lists of None of the window length).  `animate(batch, last_output_frames, cfg)` is
-    ControlAnimatePipeline.animate's contract (modules/controlanimate_pipeline.py:124-170)."""
+    ControlAnimatePipeline.animate's contract (modules/controlanimate_pipeline.py:124-170).
+    upscaler: None, or an upscaler.Upscaler -- the window's emitted frames are yielded as `upscaler.upscale_frames(frames)`
+    (= upscaler(frame) per frame, scripts/vid2vid.py:236-242); everything carried to the next window stays un-upscaled."""
     src = iter(input_frames) if input_frames is not None else None
     if src is None and total_frames is None:
         raise ValueError("text-to-video needs total_frames")
@@ -306,7 +313,7 @@ def run_windows(input_frames: Optional[Iterable], animate: AnimateFn, cfg: Windo
         last = exhausted or (total_frames is not None and emitted + 1 + len(batch) >= total_frames)  # (:235)
         out_n = len(batch) if last else len(batch) - len(overlap_frames)
         emitted += out_n
-        yield frames[:out_n]
+        yield frames[:out_n] if upscaler is None else upscaler.upscale_frames(frames[:out_n])
         if last:
             break
     cfg.frame_count = frame_count_cfg
@@ -378,7 +385,7 @@ def _run_windows_on_chains(pipe, plan, frames, cfg_of, ip_kw, rank, world, chain
 def run_video_sharded(config, frames: Sequence, components: Optional[dict] = None,
                       match_colors_fn: Optional[Callable[[Sequence, object], List]] = match_colors, device=None,
                       image_prompt_embeds=None, uncond_image_prompt_embeds=None, ip_reference_image=None,
-                      single_rank_group: bool = False, chains_per_gpu: int = 1):
+                      single_rank_group: bool = False, chains_per_gpu: int = 1, upscaler=None):
     """The window loop of scripts/vid2vid.py:168-268 over the GPUs of one node: one process per GPU (torchrun or any launcher
     that sets RANK / LOCAL_RANK / WORLD_SIZE), every rank calls this with the same `config` and the same input `frames`.
 
@@ -416,7 +423,10 @@ def run_video_sharded(config, frames: Sequence, components: Optional[dict] = Non
 
     chains_per_gpu > 1 (round 6): every rank keeps that many of ITS windows in flight on its GPU -- `ControlAnimatePipeline.twin()` facades
     over the same models, one host thread and HIP stream each (chains.py): the same frames, bit for bit, a few per cent more of them per
-    second.  Not with the native LCM sampler (`use_lcm`), whose step noise comes from torch's global generator."""
+    second.  Not with the native LCM sampler (`use_lcm`), whose step noise comes from torch's global generator.
+
+    upscaler: None, or an upscaler.Upscaler used on rank 0: the blended frames are upscaled after the blend, `frame_count` frames per
+    upscale_frames call (scripts/vid2vid.py:236-242); the blend itself runs at the generated size."""
     import torch
     from . import window_shard as WS
     from .controlanimate_pipeline import ControlAnimatePipeline, _get
@@ -504,4 +514,8 @@ def run_video_sharded(config, frames: Sequence, components: Optional[dict] = Non
         return None
     # (PIL frames, as the sequential loop handles them: Image.blend's arithmetic, byte for byte)
     as_frame = (lambda a: Image.fromarray(a)) if Image is not None else (lambda a: a)
-    return blend_windows([[as_frame(w[i].numpy()) for i in range(w.shape[0])] for w in windows], overlap, match_colors_fn)
+    out = blend_windows([[as_frame(w[i].numpy()) for i in range(w.shape[0])] for w in windows], overlap, match_colors_fn)
+    if upscaler is None:
+        return out
+    step = max(frame_count, 1)
+    return [f for s in range(0, len(out), step) for f in upscaler.upscale_frames(out[s:s + step])]

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define CA_ABI_VERSION 13
+#define CA_ABI_VERSION 14
 
 /* element types */
 #define CA_BF16 0
@@ -528,6 +528,60 @@ int ca_cfg_scheduler_step(const float* eps, int32_t ld_eps, int32_t rep, float g
  * host-computed coefficients (controlanimate_amd/schedulers.py).  The CFG combine that precedes it is
  * ca_cfg_scheduler_step with coef = {0,1,0,0, 0,1,0} (prev := combined eps). */
 int ca_lincomb(float* out, const float* const* x, const float* coef, int32_t n_terms, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * ABI v14: the Real-ESRGAN upscaler (RRDBNet anime-6B, num_feat 64, num_grow_ch 32, scale 4) that the reference runs on
+ * every emitted frame (modules/upscaler.py:25-47, scripts/vid2vid.py:236-242, through RealESRGANer.enhance).
+ *
+ * ca_conv3x3_narrow: NHWC 3x3 convolution, padding 1, stride 1, for the narrow output widths of RRDBNet (cout 16 / 32 / 64,
+ *   and conv_last's 3 with out_u8).  Implicit GEMM on the 16x16x32 MFMA; every block computes ALL cout columns of its pixels,
+ *   so the input strip is read once per block; the weight is streamed over K (tap, 32-channel chunk) from L2.
+ *   - input `x` [images, hin, win, ldx]: the first `cin` channels are read (cin % 8 == 0, ldx >= cin, ldx % 8 == 0), so a
+ *     layer reads the leading channels of a dense block's concat buffer [x | x1 | x2 | x3 | x4] without a torch.cat;
+ *   - upsample = 1: nearest x2 (F.interpolate(scale_factor=2, mode='nearest')) folded into the gather: hout = 2 hin;
+ *   - output written at y + pixel * ldy + channel_offset + c (channel_offset % 4 == 0, channel_offset + cout <= ldy, ldy % 4 == 0):
+ *     x1 .. x4 land in their slices of the concat buffer; other channels of y are never touched;
+ *   - epilogue: v = conv + bias[c]; v = leaky_relu ? (v > 0 ? v : 0.2 v) : v; y = s0 v + s1 r1[pixel, c] + s2 r2[pixel, c]
+ *     (r1 / r2 may be NULL; ld_r1 / ld_r2 % 4 == 0).  r1 / r2 may alias y at the same pixel and channel (read before written by
+ *     the same lane);
+ *   - out_u8 = 1 (cout == 3, the last conv): y is uint8 [images, hout, wout, 3]: clamp(v, 0, 1) * 255 rounded half to even,
+ *     channels reversed (RealESRGANer's output_img[[2, 1, 0]]); ldy / channel_offset / r1 / r2 unused.
+ *   The weight `w` is [round_up(cout, 16)][3][3][round_up(cin, 32)] in `dtype`, zero padded (the padding is read).
+ *   Addresses are flat 64-bit (no buffer resource descriptors): a 2048 x 3072 x 64 activation per frame is addressable; the
+ *   pixel count images * hout * wout must stay below 2^31.
+ * ------------------------------------------------------------------------------------ */
+typedef struct ca_conv3x3_narrow_args {
+  const void* x;
+  const void* w;
+  void* y;
+  const float* bias;    /* [cout] fp32 or NULL */
+  const void* r1;
+  const void* r2;
+  int64_t ldx, ldy, ld_r1, ld_r2;
+  int32_t images, hin, win, cin, cout;
+  int32_t channel_offset;
+  int32_t upsample;     /* 0 or 1 */
+  int32_t leaky_relu;   /* 0 or 1: LeakyReLU(negative_slope = 0.2) */
+  float s0, s1, s2;
+  int32_t out_u8;       /* 0 or 1 */
+  int32_t dtype;
+} ca_conv3x3_narrow_args;
+int ca_conv3x3_narrow(const ca_conv3x3_narrow_args* args, void* stream);
+/* as ca_conv3x3_plan_name, for ca_conv3x3_narrow ("convn_n64m64", "convn_n32m128", "convn_n16m128"); no launch */
+int ca_conv3x3_narrow_plan_name(const ca_conv3x3_narrow_args* args, char* buf, int32_t len);
+
+/* uint8 RGB frames [images, h, w, 3] -> RRDBNet input NHWC [images, h, w, 8] in `dtype`: channel c = src[2 - c] / 255 (fp32
+ * division, then rounded to `dtype`) for c < 3, zero for c = 3..7.  RealESRGANer.enhance treats the RGB array the reference hands
+ * it (np.asarray(pil_image)) as BGR and converts BGR -> RGB: the net sees the channels reversed. */
+int ca_rgb8_to_nhwc(const uint8_t* src, void* dst, int32_t images, int32_t h, int32_t w, int32_t dtype, void* stream);
+
+/* uint8 [images, sh, sw, 3] -> [images, dh, dw, 3] with OpenCV's INTER_LANCZOS4 integer path (cv2.resize on 8-bit data, called
+ * by RealESRGANer.enhance when outscale != 4): for every destination column dx, xofs[dx] = floor(fx) - 3 and alpha[dx][0..7]
+ * the 11-bit fixed-point Lanczos-4 weights of source columns xofs[dx] + k (clamped to the image: edge replication); rows the
+ * same with yofs / beta.  dst = saturate((sum_k beta[k] * (sum_j alpha[j] * src[row k][col j]) + 2^21) >> 22), all in int32.
+ * The tables are computed on the host (controlanimate_amd/upscaler.py: lanczos4_tables). */
+int ca_resize_lanczos4_u8(const uint8_t* src, uint8_t* dst, int32_t images, int32_t sh, int32_t sw, int32_t dh, int32_t dw,
+                          const int32_t* xofs, const int16_t* alpha, const int32_t* yofs, const int16_t* beta, void* stream);
 
 #ifdef __cplusplus
 }
