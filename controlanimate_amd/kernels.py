@@ -707,3 +707,93 @@ def resize_lanczos4_u8(frames: torch.Tensor, dh: int, dw: int, xofs: torch.Tenso
     check(lib().ca_resize_lanczos4_u8(_p(frames), _p(out), n, sh, sw, dh, dw, _p(xofs), _p(alpha), _p(yofs), _p(beta), _stream()),
           "ca_resize_lanczos4_u8")
     return out
+
+
+# ---- ABI v15: the colour match (controlanimate_amd/color_match.py) --------------------------------------------------------------
+
+def color_match_workspace_bytes(images: int, pixels: int) -> int:
+    """ca_color_match_workspace_bytes; the sort of `segments` runs needs images = (segments + 2) // 3."""
+    need = lib().ca_color_match_workspace_bytes(images, pixels)
+    if need <= 0:
+        raise _capi.CAHipError(f"ca_color_match_workspace_bytes: images={images} pixels={pixels} out of range")
+    return need
+
+
+def _req_u8_frames(frames: torch.Tensor):
+    _req_cuda(frames)
+    assert frames.dtype == torch.uint8 and frames.dim() == 3 and frames.shape[2] == 3 and frames.is_contiguous(), "uint8 [images, pixels, 3]"
+    return frames.shape[0], frames.shape[1]
+
+
+def _req_f64(*ts):
+    _req_cuda(*ts)
+    for t in ts:
+        assert t.dtype == torch.float64 and t.is_contiguous()
+
+
+def hist_u8x3(frames: torch.Tensor, hist: torch.Tensor) -> torch.Tensor:
+    """uint8 [images, pixels, 3] -> counts [images, 3, 256] into the caller's int32 `hist` (ca_hist_u8x3)."""
+    images, pixels = _req_u8_frames(frames)
+    _req_cuda(hist)
+    assert hist.dtype == torch.int32 and tuple(hist.shape) == (images, 3, 256) and hist.is_contiguous()
+    check(lib().ca_hist_u8x3(_p(frames), _p(hist), images, pixels, _stream()), "ca_hist_u8x3")
+    return hist
+
+
+def color_moments_f64(frames: torch.Tensor, lut: torch.Tensor, mean: torch.Tensor, moments: torch.Tensor, ws: torch.Tensor) -> torch.Tensor:
+    """The six centred second moments per image of lut[image][c][byte] (ca_color_moments_f64) into `moments` [images, 6]."""
+    images, pixels = _req_u8_frames(frames)
+    _req_f64(lut, mean, moments)
+    _req_cuda(ws)
+    assert tuple(lut.shape) == (images, 3, 256) and tuple(mean.shape) == (images, 3) and tuple(moments.shape) == (images, 6)
+    check(lib().ca_color_moments_f64(_p(frames), _p(lut), _p(mean), _p(moments), images, pixels, _p(ws), ws.numel() * ws.element_size(), _stream()),
+          "ca_color_moments_f64")
+    return moments
+
+
+def color_transform_f64(frames: torch.Tensor, lut: torch.Tensor, mean: torch.Tensor, t: torch.Tensor, my: torch.Tensor,
+                        y: torch.Tensor) -> torch.Tensor:
+    """y[image, j, p] = (lut[image, :, byte] - mean[image]) @ t[image] + my into float64 planes [images, 3, pixels] (ca_color_transform_f64)."""
+    images, pixels = _req_u8_frames(frames)
+    _req_f64(lut, mean, t, my, y)
+    assert tuple(lut.shape) == (images, 3, 256) and tuple(mean.shape) == (images, 3) and tuple(t.shape) == (images, 3, 3)
+    assert my.numel() == 3 and tuple(y.shape) == (images, 3, pixels)
+    check(lib().ca_color_transform_f64(_p(frames), _p(lut), _p(mean), _p(t), _p(my), _p(y), images, pixels, _stream()), "ca_color_transform_f64")
+    return y
+
+
+def sort_f64_segments(keys: torch.Tensor, out: torch.Tensor, ws: torch.Tensor) -> torch.Tensor:
+    """Sorts every run keys[..., :] (float64, last dimension) ascending into `out` (may be `keys`) (ca_sort_f64_segments)."""
+    _req_f64(keys, out)
+    _req_cuda(ws)
+    assert keys.shape == out.shape and keys.dim() >= 1
+    n = keys.shape[-1]
+    segments = keys.numel() // n
+    check(lib().ca_sort_f64_segments(_p(keys), _p(out), segments, n, _p(ws), ws.numel() * ws.element_size(), _stream()), "ca_sort_f64_segments")
+    return out
+
+
+def color_rank_map_f64(y: torch.Tensor, srt: torch.Tensor, o: torch.Tensor, knots_q: torch.Tensor, knots_val: torch.Tensor,
+                       knots_n: torch.Tensor, ws: torch.Tensor) -> torch.Tensor:
+    """o = interp(rank of y in its sorted plane / pixels; knots) (ca_color_rank_map_f64); `o` may be `y`.  Leaves the min / max
+    partials of o in `ws` for color_finish_u8."""
+    _req_f64(y, srt, o, knots_q, knots_val)
+    _req_cuda(knots_n, ws)
+    images, _, pixels = y.shape
+    assert y.shape[1] == 3 and srt.shape == y.shape and o.shape == y.shape
+    assert tuple(knots_q.shape) == (3, 256) and tuple(knots_val.shape) == (3, 256) and knots_n.dtype == torch.int32 and knots_n.numel() == 3
+    check(lib().ca_color_rank_map_f64(_p(y), _p(srt), _p(o), _p(knots_q), _p(knots_val), _p(knots_n), images, pixels, _p(ws),
+                                      ws.numel() * ws.element_size(), _stream()), "ca_color_rank_map_f64")
+    return o
+
+
+def color_finish_u8(o: torch.Tensor, out: torch.Tensor, normalize: bool, ws: torch.Tensor) -> torch.Tensor:
+    """float64 planes [images, 3, pixels] -> uint8 [images, pixels, 3]: min-max stretch (normalize), x255, round half to even, clamp
+    (ca_color_finish_u8; `ws` as color_rank_map_f64 left it)."""
+    _req_f64(o)
+    _req_cuda(out, ws)
+    images, _, pixels = o.shape
+    assert out.dtype == torch.uint8 and tuple(out.shape) == (images, pixels, 3) and out.is_contiguous()
+    check(lib().ca_color_finish_u8(_p(o), _p(out), images, pixels, int(bool(normalize)), _p(ws), ws.numel() * ws.element_size(), _stream()),
+          "ca_color_finish_u8")
+    return out

@@ -9,7 +9,9 @@ Per window (file:line of the reference behaviour mirrored):
   :197-213  optional initial IP-Adapter round (run once, then re-run on its own last frames)
   :215-221  colour match every frame to `last_output_frame` (the reference calls the third-party color_matcher package
             with method 'hm-mkl-hm', modules/utils.py:116-130; `match_colors` below restates that compound:
-            histogram matching -> Monge-Kantorovich linear transfer -> histogram matching)
+            histogram matching -> Monge-Kantorovich linear transfer -> histogram matching; on the host, float64 numpy.
+            The same compound on the GPU for uint8 frames is color_match.ColorMatcher(device), passed as the hook:
+            run_windows(..., match_colors=ColorMatcher(device)) / run_video_sharded(..., match_colors_fn=ColorMatcher(device)))
   :93-136   raw-RGB frames through ffmpeg pipes (FFMPEGProcessor, modules/utils.py:87-113) -- `FFMPEGProcessor`,
             `ffmpeg_reader_cmd`, `ffmpeg_writer_cmd` below; `prefetch` decodes the next windows' frames on a host thread
             while the GPU denoises the current one (the reference reads synchronously)
@@ -244,6 +246,8 @@ def run_windows(input_frames: Optional[Iterable], animate: AnimateFn, cfg: Windo
     input_frames: iterable of frames (vid2vid) or None (text-to-video: `total_frames` must be given and the
     batches are lists of None of the window length).  `animate(batch, last_output_frames, cfg)` is
     ControlAnimatePipeline.animate's contract (modules/controlanimate_pipeline.py:124-170).
+    match_colors: the hook `(frames, ref_frame) -> frames`; the default is the host function above, `color_match.ColorMatcher(device)`
+    is the same compound on the GPU (uint8 frames), None switches the stage off.
     upscaler: None, or an upscaler.Upscaler -- the window's emitted frames are yielded as `upscaler.upscale_frames(frames)`
     (= upscaler(frame) per frame, scripts/vid2vid.py:236-242); everything carried to the next window stays un-upscaled."""
     src = iter(input_frames) if input_frames is not None else None
@@ -388,6 +392,8 @@ def run_video_sharded(config, frames: Sequence, components: Optional[dict] = Non
                       single_rank_group: bool = False, chains_per_gpu: int = 1, upscaler=None):
     """The window loop of scripts/vid2vid.py:168-268 over the GPUs of one node: one process per GPU (torchrun or any launcher
     that sets RANK / LOCAL_RANK / WORLD_SIZE), every rank calls this with the same `config` and the same input `frames`.
+    `match_colors_fn` is rank 0's colour-match hook (step 4): the host `match_colors` by default, `color_match.ColorMatcher(device)`
+    for the same compound on rank 0's GPU.
 
       1. `init_distributed` (RCCL over xGMI; gloo when CA_DIST_BACKEND=gloo);
       2. rank 0 builds ControlAnimatePipeline(config) from the checkpoints; every other rank builds the same object from

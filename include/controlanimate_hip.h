@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define CA_ABI_VERSION 14
+#define CA_ABI_VERSION 15
 
 /* element types */
 #define CA_BF16 0
@@ -582,6 +582,67 @@ int ca_rgb8_to_nhwc(const uint8_t* src, void* dst, int32_t images, int32_t h, in
  * The tables are computed on the host (controlanimate_amd/upscaler.py: lanczos4_tables). */
 int ca_resize_lanczos4_u8(const uint8_t* src, uint8_t* dst, int32_t images, int32_t sh, int32_t sw, int32_t dh, int32_t dw,
                           const int32_t* xofs, const int16_t* alpha, const int32_t* yofs, const int16_t* beta, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * ABI v15: the colour match of the window loop.  Every window after the first is matched to the previous window's output
+ * with color_matcher's compound method 'hm-mkl-hm' (scripts/vid2vid.py:216-218 through modules/utils.py:116-130; the host
+ * restatement is controlanimate_amd/vid2vid.py: match_colors / _hist_match / _mkl / _minmax).  For uint8 frames the compound is
+ * a chain of device stages with 256-entry float64 tables and one 3x3 matrix between them; the tables and the matrix are
+ * computed on the host from the histograms and the moments (controlanimate_amd/color_match.py).  Frames are uint8
+ * [images, pixels, 3] (pixels = H * W, interleaved RGB); float64 images are channel planes [images][3][pixels].
+ * All float64 arithmetic is unfused (a * b + c rounds twice, as numpy's); no reduction uses floating-point atomics, so two
+ * runs on the same input give the same bits.  1 <= images <= 21845, 1 <= pixels <= 2^30; float64 buffers 8-byte aligned.
+ * ------------------------------------------------------------------------------------ */
+
+/* Bytes of the scratch buffer the entry points below share for `images` frames of `pixels` pixels: the second key buffer of
+ * the sort (3 * images * pixels float64), its per-pass block counters, the partial sums of the moments and the min / max
+ * partials that the rank map leaves for the finish.  0 for sizes out of range.  No stage reads scratch that it or an earlier stage of
+ * the same call chain did not write. */
+int64_t ca_color_match_workspace_bytes(int32_t images, int64_t pixels);
+
+/* hist[image][channel][value] = number of pixels of that image whose channel has that value (uint32 [images][3][256]; zeroed
+ * by the call).  Replaces the np.unique(..., return_counts=True) sorts of _hist_match on integer-valued images and the
+ * a.min() / a.max() of _minmax in type_norm (vid2vid.py:79-80, :109): per-wave LDS sub-histograms, one integer atomic add per
+ * non-empty bin and block. */
+int ca_hist_u8x3(const uint8_t* src, uint32_t* hist, int32_t images, int64_t pixels, void* stream);
+
+/* moments[image] = { s00, s01, s02, s11, s12, s22 }, s_ij = sum over the pixels of (lut[image][i][a_i] - mean[image][i]) *
+ * (lut[image][j][a_j] - mean[image][j]): np.cov's numerator in _mkl (vid2vid.py:93) for the image whose channel c is
+ * lut[image][c][.] applied to the bytes.  lut float64 [images][3][256], mean float64 [images][3], moments float64 [images][6].
+ * 64 block partials per image into the workspace, summed in a fixed order by a second launch. */
+int ca_color_moments_f64(const uint8_t* src, const double* lut, const double* mean, double* moments, int32_t images,
+                         int64_t pixels, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* y[image][j][p] = ((d0 t[image][0][j] + d1 t[image][1][j]) + d2 t[image][2][j]) + my[j], d_i = lut[image][i][a_i] - mean[image][i]:
+ * the first histogram match (as the table lut) and `(x - mx) @ t + my` of _mkl (vid2vid.py:83, :103) in one pass.
+ * t float64 [images][3][3] row major, my float64 [3] (one reference for all images), y float64 planes [images][3][pixels]. */
+int ca_color_transform_f64(const uint8_t* src, const double* lut, const double* mean, const double* t, const double* my,
+                           double* y, int32_t images, int64_t pixels, void* stream);
+
+/* sorted[s][0..n) = keys[s][0..n) in ascending order for each of `segments` runs of n float64 keys; finite values come out in
+ * np.sort's order (-0.0 before +0.0).  Replaces the np.unique sort of the second _hist_match (vid2vid.py:79), whose input has about as
+ * many distinct values as pixels.  LSD radix sort on the order-preserving 64-bit integer image of the double, eight 8-bit
+ * passes, each a block histogram, a scan and a stable scatter ranked with 64-lane ballots.  `sorted` may be `keys` (in place);
+ * `keys` is otherwise left untouched.  Needs the workspace of ca_color_match_workspace_bytes((segments + 2) / 3, n).
+ * 1 <= segments <= 65535. */
+int ca_sort_f64_segments(const double* keys, double* sorted, int32_t segments, int64_t n, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+
+/* o[image][c][p] = interp(rank / pixels; knots_q[c], knots_val[c]) with rank = the number of values of sorted[image][c] that are <=
+ * y[image][c][p] (ties share the upper rank, as np.unique + cumsum give) and numpy's np.interp: the first value below the first
+ * knot, the last at or above the last knot, a knot's value on an exact hit, else val[j] + slope_j * (q - q[j]) -- the second
+ * _hist_match (vid2vid.py:81-83).  knots_q / knots_val float64 [3][256], knots_n int32 [3] (1 .. 256 knots per channel, q
+ * strictly increasing).  `o` may alias `y`, not `sorted`.  Leaves 64 min / max partials of o per plane in the workspace for
+ * ca_color_finish_u8. */
+int ca_color_rank_map_f64(const double* y, const double* sorted, double* o, const double* knots_q, const double* knots_val,
+                          const int32_t* knots_n, int32_t images, int64_t pixels, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+
+/* dst[image][p][c] = (uint8) clamp(rint(v * 255), 0, 255), v = normalize ? (o - lo) / (hi - lo) : o, with lo / hi the minimum and
+ * maximum of o over the whole image (all channels) as ca_color_rank_map_f64 left them in the same workspace; v = o when hi == lo
+ * (_minmax, np.round and np.clip of match_colors, vid2vid.py:139-141).  With normalize = 0 the workspace is not read and may be NULL. */
+int ca_color_finish_u8(const double* o, uint8_t* dst, int32_t images, int64_t pixels, int32_t normalize, const void* workspace,
+                       int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
