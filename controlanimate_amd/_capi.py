@@ -12,8 +12,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CA_HIP_LIB") or os.path.join(_HERE, "csrc", "libcontrolanimate_hip.so")  # (CA_HIP_LIB: another build of the same ABI, for same-box A/B timing)
 
 CA_BF16, CA_F16 = 0, 1
+CA_F32 = 2  # output of ca_canny_emit only
 CA_ACT_NONE, CA_ACT_SILU = 0, 1
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 class CAHipUnavailable(RuntimeError):
@@ -209,6 +210,14 @@ SYMBOLS = {
     "ca_color_rank_map_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
                                          C.c_void_p, C.c_int64, C.c_void_p]),
     "ca_color_finish_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    # ABI v16: the canny annotator (controlanimate_amd/annotators.py: CannyAnnotator)
+    "ca_canny_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "ca_canny_tile_w": (C.c_int32, []),
+    "ca_canny_tile_h": (C.c_int32, []),
+    "ca_canny_classify": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ca_canny_link": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ca_canny_link_stage": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "ca_canny_emit": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
 }
 
 _lib = None

@@ -42,6 +42,16 @@ def _image_to_chw01(img) -> torch.Tensor:
     return t / 255.0 if arr.dtype == np.uint8 else t
 
 
+def _frame_hw(img) -> Tuple[int, int]:
+    """(H, W) of a PIL image or an HxW[xC] array."""
+    return tuple(np.asarray(img).shape[:2]) if not hasattr(img, "size") or isinstance(img, np.ndarray) else (img.size[1], img.size[0])
+
+
+def _on_device(t: torch.Tensor, device: torch.device) -> bool:
+    """t lies on `device`; a device without an index ("cuda") means any card of that type."""
+    return t.device.type == device.type and device.index in (None, t.device.index)
+
+
 class MultiControlNetResidualsPipeline:
     def __init__(self, hf_controlnet_names: Sequence[str], cond_scale: Sequence[float], use_lcm: bool,
                  controlnets: Optional[Sequence[ControlNetModel]] = None, device="cuda",
@@ -76,6 +86,16 @@ class MultiControlNetResidualsPipeline:
                 return fn(image)
         return image  # already annotated
 
+    def _batch_annotator(self, controlnet_model: str, src):
+        """annotate_batch of the annotator that `prepare_controlnet_input_image` would call per frame, when it has one and `src` is a
+        non-empty list of frames that are not tensors; else None (the per-frame path)."""
+        if not isinstance(src, (list, tuple)) or not src or any(isinstance(im, torch.Tensor) for im in src):
+            return None
+        for key, fn in self.annotators.items():
+            if key in controlnet_model:
+                return getattr(fn, "annotate_batch", None)
+        return None
+
     def prep_control_images(self, images, control_image_processor=None, epoch=0, output_dir="tmp/output",
                             save_outputs=False, do_classifier_free_guidance=True, guess_mode=False):
         """images: list of f control images (PIL / arrays / tensors), or {controlnet name: list} when each
@@ -84,12 +104,29 @@ class MultiControlNetResidualsPipeline:
         prep = []
         for name in self.controlnet_names:
             src = images[name] if isinstance(images, dict) else images
+            doubled = bool(do_classifier_free_guidance and not guess_mode and not self.use_lcm)
+            old = self.prep_images[len(prep)] if self.prep_images is not None and len(self.prep_images) == len(self.controlnet_names) else None
+            batch = self._batch_annotator(name, src)
+            if batch is not None:
+                # a whole-window annotator (annotators.CannyAnnotator): one call for the list; it writes the doubled float32 tensor
+                # itself, straight into the tensor the ControlNets already know when that one fits
+                src = list(src)
+                rep = 2 if doubled else 1
+                # (_annotator_wrote: `old` came from this route unmoved, so the annotator works on the pipeline's device)
+                fits = (old is not None and getattr(old, "_annotator_wrote", False) and old.dtype == torch.float32 and old.is_contiguous()
+                        and tuple(old.shape) == (rep * len(src), 3, *_frame_hw(src[0])))
+                ctrl = batch(src, out=old if fits else None, rep=rep, dtype=torch.float32)
+                here = _on_device(ctrl, self.device)
+                if not here:  # an annotator on another device than the pipeline's: as the per-frame path's .to(self.device)
+                    ctrl = ctrl.to(self.device)
+                ctrl._annotator_wrote = here
+                ctrl._cfg_doubled = doubled
+                prep.append(ctrl)
+                continue
             frames = [_image_to_chw01(self.prepare_controlnet_input_image(name, im)) for im in src]
             ctrl = torch.stack(frames).to(self.device)
-            doubled = bool(do_classifier_free_guidance and not guess_mode and not self.use_lcm)
             if doubled:
                 ctrl = torch.cat([ctrl] * 2)
-            old = self.prep_images[len(prep)] if self.prep_images is not None and len(self.prep_images) == len(self.controlnet_names) else None
             if old is not None and old.shape == ctrl.shape and old.dtype == ctrl.dtype and old.device == ctrl.device:
                 # the next window's frames go INTO the tensor the ControlNets already know: their hint embeddings are then
                 # refreshed in place (ControlNetModel.hint_embedding) and a captured hipGraph of the step stays valid

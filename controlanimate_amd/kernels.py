@@ -797,3 +797,59 @@ def color_finish_u8(o: torch.Tensor, out: torch.Tensor, normalize: bool, ws: tor
     check(lib().ca_color_finish_u8(_p(o), _p(out), images, pixels, int(bool(normalize)), _p(ws), ws.numel() * ws.element_size(), _stream()),
           "ca_color_finish_u8")
     return out
+
+
+# ---- ABI v16: the canny annotator (controlanimate_amd/annotators.py: CannyAnnotator) ---------------------------------------------
+
+CANNY_TILE_H, CANNY_TILE_W = 16, 64  # kTH / kTW of csrc/ca_canny.hip (ca_canny_tile_h / ca_canny_tile_w; tests/test_canny_cpu.py compares)
+_CANNY_DT = {torch.float16: CA_F16, torch.float32: _capi.CA_F32}
+CANNY_LINK_STAGES = ("label", "merge", "flatten")  # CA_CANNY_LINK_LABEL / _MERGE / _FLATTEN
+
+
+def canny_workspace_bytes(images: int, h: int, w: int) -> int:
+    """ca_canny_workspace_bytes: the scratch of classify / link / emit for `images` frames of h x w pixels."""
+    need = lib().ca_canny_workspace_bytes(images, h, w)
+    if need <= 0:
+        raise _capi.CAHipError(f"ca_canny_workspace_bytes: images={images} h={h} w={w} out of range (images * h * w < 2^31)")
+    return need
+
+
+def _ws_bytes(ws: torch.Tensor) -> int:
+    return ws.numel() * ws.element_size()
+
+
+def canny_classify(frames: torch.Tensor, low: int, high: int, ws: torch.Tensor) -> None:
+    """uint8 [images, H, W, C] (C = 1 or 3) -> class byte per pixel in `ws` (ca_canny_classify)."""
+    _req_cuda(frames, ws)
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.is_contiguous(), "uint8 [images, H, W, C]"
+    n, h, w, c = frames.shape
+    check(lib().ca_canny_classify(_p(frames), n, h, w, c, int(low), int(high), _p(ws), _ws_bytes(ws), _stream()), "ca_canny_classify")
+
+
+def canny_link(images: int, h: int, w: int, ws: torch.Tensor) -> None:
+    """Hysteresis over the class bytes in `ws`: component labels and the strong flag per root (ca_canny_link, three launches)."""
+    _req_cuda(ws)
+    check(lib().ca_canny_link(images, h, w, _p(ws), _ws_bytes(ws), _stream()), "ca_canny_link")
+
+
+def canny_link_stage(images: int, h: int, w: int, ws: torch.Tensor, stage: str) -> None:
+    """One launch of canny_link, `stage` in CANNY_LINK_STAGES: the three in that order are canny_link (ca_canny_link_stage; for
+    timing each launch on its own)."""
+    _req_cuda(ws)
+    check(lib().ca_canny_link_stage(images, h, w, _p(ws), _ws_bytes(ws), CANNY_LINK_STAGES.index(stage), _stream()), "ca_canny_link_stage")
+
+
+def canny_emit(images: int, h: int, w: int, ws: torch.Tensor, edges: Optional[torch.Tensor] = None, control: Optional[torch.Tensor] = None,
+               rep: int = 1) -> None:
+    """Writes the edge map (uint8 [images, H, W], 0 / 255) and / or the control tensor ([rep * images, 3, H, W], 0.0 / 1.0) from
+    `ws` as canny_link left it (ca_canny_emit)."""
+    _req_cuda(ws, edges, control)
+    if edges is not None:
+        assert edges.dtype == torch.uint8 and tuple(edges.shape) == (images, h, w) and edges.is_contiguous()
+    dt = _capi.CA_F32
+    if control is not None:
+        if control.dtype not in _CANNY_DT:
+            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
+        assert tuple(control.shape) == (rep * images, 3, h, w) and control.is_contiguous()
+        dt = _CANNY_DT[control.dtype]
+    check(lib().ca_canny_emit(images, h, w, _p(ws), _ws_bytes(ws), _p(edges), _p(control), int(rep), dt, _stream()), "ca_canny_emit")

@@ -26,11 +26,12 @@
 extern "C" {
 #endif
 
-#define CA_ABI_VERSION 15
+#define CA_ABI_VERSION 16
 
 /* element types */
 #define CA_BF16 0
 #define CA_F16 1
+#define CA_F32 2 /* output of ca_canny_emit only (ABI v16) */
 
 /* error codes */
 #define CA_OK 0
@@ -643,6 +644,53 @@ int ca_color_rank_map_f64(const double* y, const double* sorted, double* o, cons
  * (_minmax, np.round and np.clip of match_colors, vid2vid.py:139-141).  With normalize = 0 the workspace is not read and may be NULL. */
 int ca_color_finish_u8(const double* o, uint8_t* dst, int32_t images, int64_t pixels, int32_t normalize, const void* workspace,
                        int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * ABI v16: the canny annotator of the ControlNet path for a whole window of frames.  The reference annotates every frame on the
+ * host with cv2.Canny(img, 100, 200) (modules/controlresiduals_pipeline.py:48-55: 8-bit RGB, aperture 3, L1 gradient norm); the
+ * host restatement, which is the specification of these entry points down to its tie rules, is
+ * controlanimate_amd/annotators.py: canny_edges.  All arithmetic is int32, so the device result equals the host's byte for byte.
+ * Frames are uint8 [images, h, w, channels], channels = 1 or 3; images * h * w < 2^31 (labels are int32 pixel indices).
+ * The three stages share one caller-owned workspace and run in the order classify, link, emit on one stream; a fixed set of
+ * launches (1 + 3 + 1) with no device-to-host read, so the chain can be captured in a hipGraph.  Nothing in the workspace is
+ * assumed: every byte a stage reads was written by an earlier stage of the same chain.  Frames never link to each other.
+ * ------------------------------------------------------------------------------------ */
+
+/* Bytes of the workspace for `images` frames of h x w pixels: an int32 label, a class byte and a root flag byte per pixel,
+ * rounded up to 256.  0 for sizes out of range.  The workspace must be 16-byte aligned. */
+int64_t ca_canny_workspace_bytes(int32_t images, int32_t h, int32_t w);
+
+/* The tile of the kernels (64 x 16 pixels): the sizes at which tests/test_canny_gpu.py places its tile-border cases. */
+int32_t ca_canny_tile_w(void);
+int32_t ca_canny_tile_h(void);
+
+/* Class byte per pixel into the workspace: 0 none, 1 weak candidate (mag > low), 2 strong (mag > high), for pixels that survive
+ * the non-maximum suppression.  One launch: a 64 x 16 tile with a 2-pixel halo goes into LDS through aligned 4-byte loads; Sobel
+ * 3x3 with replicated image borders; per pixel the channel with the largest |dx| + |dy| (the first wins ties); the sector test
+ * ay < tg22x / ay > tg67x / (dx ^ dy) < 0 with tg22 = 13573 / 2^15 and the host's > / >= pattern, magnitudes outside the image
+ * counting as 0.  low / high are the floors of cv2's thresholds; low <= high. */
+int ca_canny_classify(const uint8_t* src, int32_t images, int32_t h, int32_t w, int32_t channels, int32_t low, int32_t high,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Hysteresis as connected-component labelling of the candidates (8-neighbourhood), three launches: union-find per tile in LDS
+ * with label = the global pixel index of the tile-local root; unions of the neighbour pairs that straddle a tile border (the
+ * diagonal pairs at tile corners included) by atomicMin on the labels; label = root for every candidate, and one flag byte per
+ * root that says whether its component holds a strong pixel.  Needs the class bytes of ca_canny_classify in the workspace. */
+int ca_canny_link(int32_t images, int32_t h, int32_t w, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* One of the three launches of ca_canny_link, for timing each on its own (tools/bench_canny.py): the stages in the order
+ * label, merge, flatten on one stream are ca_canny_link. */
+#define CA_CANNY_LINK_LABEL 0
+#define CA_CANNY_LINK_MERGE 1
+#define CA_CANNY_LINK_FLATTEN 2
+int ca_canny_link_stage(int32_t images, int32_t h, int32_t w, void* workspace, int64_t workspace_bytes, int32_t stage, void* stream);
+
+/* edge = candidate whose root is flagged.  Writes either or both of: `edges`, uint8 [images, h, w] with 0 / 255; `control`,
+ * [rep * images, 3, h, w] of control_dtype (CA_F16 or CA_F32) with 0.0 / 1.0, the three channels equal and, with
+ * rep = 2, the frames written twice (torch.cat([ctrl] * 2) of classifier-free guidance, controlresiduals_pipeline.py:268-269).
+ * Needs the workspace as ca_canny_link left it.  rep is 1 or 2. */
+int ca_canny_emit(int32_t images, int32_t h, int32_t w, const void* workspace, int64_t workspace_bytes, uint8_t* edges,
+                  void* control, int32_t rep, int32_t control_dtype, void* stream);
 
 #ifdef __cplusplus
 }
