@@ -166,22 +166,22 @@ __global__ __launch_bounds__(256) void k_gemm(GemmKParams p) {
 
 // ---- LDS-DMA variant ------------------------------------------------------------------------
 
-// NBUF = 2: tile t+1 is issued before the MFMA phase of tile t, `__syncthreads()` (which hipcc
-//           precedes with vmcnt(0)) once per tile.
-// NBUF >= 3: tiles are issued NBUF - 1 ahead into a ring; a wave waits with a COUNTED
+// NBUF = 1: one LDS stage, two `__syncthreads()` per tile (hipcc precedes them with vmcnt(0)); 4 blocks (128 x 160 tiles: 3)
+//           per CU cover each other's transfer latency.
+// NBUF = 3: tiles are issued NBUF - 1 ahead into a ring; a wave waits with a COUNTED
 //           `s_waitcnt vmcnt(per-tile DMA count x younger tiles)` (tile t landed, the younger ones may still be in
 //           flight), then a raw s_barrier: DMA transfers stay in flight across barriers
-//           (cdna_hip_programming.md "Pipelining across barriers").  All LDS is one array.
-template <int DT, int BM, int BN, int WAVES_M, int WAVES_N, int MODE, int NBUF, int KT = 64>
-__global__ __launch_bounds__(WAVES_M * WAVES_N * 64,
-                             ((BM / WAVES_M) * (BN / WAVES_N) > 64 * 80 ? 2 : (NBUF * KT == 64 ? (BN > 128 ? 3 : 4) : (NBUF * (BM + BN) * KT * 2 > 80 * 1024 ? 1 : 2))) * 4 / (WAVES_M * WAVES_N))
+//           (cdna_hip_programming.md "Pipelining across barriers").  All LDS is one array; 2 blocks per CU.
+// Instantiated (launch_gemm): 128x160 / 1, 128x128 / 1, 128x64 / 1 and 128x64 / 3; the double buffer, deeper rings, 256-row
+// tiles and a 32-wide K stage were measured and lost.
+template <int DT, int BM, int BN, int WAVES_M, int WAVES_N, int MODE, int NBUF>
+__global__ __launch_bounds__(256, NBUF == 1 ? (BN > 128 ? 3 : 4) : 2)
 void k_gemm_dma(GemmKParams p) {
-  // KT = K elements per LDS stage: 64 (one 128-byte row per tile row) or 32 with NBUF = 2 -- the same 32 KB
-  // as one 64-wide stage, so 4 blocks still share a CU, but each block also prefetches its own next stage
-  static_assert(KT == 64 || KT == 32, "k tile");
+  static_assert(WAVES_M * WAVES_N == 4 && (NBUF == 1 || NBUF == 3), "instantiations: see above");
+  constexpr int KT = BK;             // K elements per LDS stage: one 128-byte row per tile row
   constexpr int CPR = KT / 8;        // 16-byte chunks per LDS row
   constexpr int RPI = 64 / CPR;      // tile rows one wave-wide DMA instruction covers
-  constexpr int NW = WAVES_M * WAVES_N, NT = NW * 64;  // 4 waves (128-row tiles) or 8 waves (256x128 tiles)
+  constexpr int NW = WAVES_M * WAVES_N, NT = NW * 64;
   constexpr int TM = BM / WAVES_M / 16;
   constexpr int TN = BN / WAVES_N / 16;
   constexpr int AG = BM / RPI / NW;  // DMA instructions per wave per stage (A)
@@ -189,8 +189,7 @@ void k_gemm_dma(GemmKParams p) {
   // the LDS-staged epilogue needs BM x (BN + 8) elements: more than ONE 128x128x64 stage
   constexpr int SMEM_ELEMS = NBUF * (BM + BN) * KT > BM * (BN + 8) ? NBUF * (BM + BN) * KT : BM * (BN + 8);
   // XOR swizzle of the chunk index: conflict-free ds_read_b128 for the hardware's 16-lane groups
-  // (128-byte rows: (row>>1)&7; 64-byte rows: the map [0,3,2,1][(row>>2)&3] = (-(row>>2))&3)
-  auto swz = [](int row) { return KT == 64 ? ((row >> 1) & 7) : ((-(row >> 2)) & 3); };
+  auto swz = [](int row) { return (row >> 1) & 7; };
   auto lds_at = [&](int row, int chunk) { return row * KT + ((chunk ^ swz(row)) << 3); };
   __shared__ __attribute__((aligned(16))) u16 smem[SMEM_ELEMS];
 
@@ -306,21 +305,17 @@ void k_gemm_dma(GemmKParams p) {
   auto compute = [&](int buf) {
     const u16* sa = smem + buf * (BM + BN) * KT;
     const u16* sb = sa + BM * KT;
-    if (CA_GEMM_ABLATE == 1) return;
+    // (tid and lane stay captured, in this position: the removed timing ablations named them here, and without the two closure
+    //  fields hipcc orders the inlined body differently -- other registers and schedule in every k_gemm_dma.  Dropping this line
+    //  is a code-generation change to be measured, not a clean-up.)
+    (void)tid, (void)lane;
 #pragma unroll
     for (int s = 0; s < KT / 32; ++s) {
       u32x4 fa[TM], fb[TN];
-      if (CA_GEMM_ABLATE == 4) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i) fa[i] = (u32x4){(unsigned)tid, 1u, 2u, 3u};
-#pragma unroll
-        for (int j = 0; j < TN; ++j) fb[j] = (u32x4){(unsigned)lane, 5u, 6u, 7u};
-      } else {
 #pragma unroll
       for (int i = 0; i < TM; ++i) fa[i] = ld16(sa + lds_at(wm * TM * 16 + i * 16 + l15, s * 4 + g));
 #pragma unroll
       for (int j = 0; j < TN; ++j) fb[j] = ld16(sb + lds_at(wn * TN * 16 + j * 16 + l15, s * 4 + g));
-      }
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -331,24 +326,15 @@ void k_gemm_dma(GemmKParams p) {
     // single LDS buffer (32 KB for 128x128): two barriers per tile, but 3 blocks per CU -- the
     // other resident blocks' MFMA phases cover this block's transfer latency
     for (int t = 0; t < nt; ++t) {
-      if (CA_GEMM_ABLATE < 2 || t == 0) stage(t_first + t, 0);
-      if (CA_GEMM_ABLATE != 5 || t == 0) __syncthreads();
+      stage(t_first + t, 0);
+      __syncthreads();  // hipcc drains the LDS-DMA queue (vmcnt(0)) ahead of the barrier
       compute(0);
-      if (CA_GEMM_ABLATE != 3 && CA_GEMM_ABLATE != 5) __syncthreads();
-    }
-  } else if (NBUF == 2) {
-    stage(t_first, 0);
-    __syncthreads();  // hipcc drains the LDS-DMA queue (vmcnt(0)) ahead of the barrier
-    for (int t = 0; t < nt; ++t) {
-      const int buf = t & 1;
-      if (t + 1 < nt) stage(t_first + t + 1, buf ^ 1);
-      compute(buf);
       __syncthreads();
     }
   } else {
     // NBUF >= 3 (round 4): a ring with NBUF - 1 tiles in flight, for the launches whose K loop is a chain of DMA round trips with
     // almost nothing to compute per tile (M = 2048: the 8x8-latent level -- 8 MFMAs per wave and K tile against ~1.2 us per
-    // round trip).  With two stages ONE tile is in flight while the previous one is computed; here tile t is awaited with a
+    // round trip).  With two stages ONE tile would be in flight while the previous one is computed; here tile t is awaited with a
     // COUNTED vmcnt (the pieces of the min(NBUF - 2, tiles left) younger tiles stay outstanding), one raw barrier per tile
     // publishes it, and tile t + NBUF - 1 goes into the slot whose reads the same barrier has just retired.
     constexpr int PER = AG + BG;  // DMA instructions per wave and stage
@@ -470,9 +456,9 @@ inline bool wres_eligible(const GemmKParams& p) {
   static const int wres_env = CA_KNOB("CA_GEMM_WRES", -1);  // (experiment builds: 0 = never, 1 = whenever the shape qualifies)
   const int kc = p.c1 + p.c2;
   return wres_env != 0 && kc == 320 && p.taps == 1 && (p.c2 == 0 || p.c1 % 32 == 0) && p.n % 160 == 0 && p.n / 160 <= 32 && !p.out_f32 &&
-         p.splits <= 1 && !p.ln_parts && p.a_bytes != 0 && p.w_bytes != 0 && (p.c2 == 0 || p.a2_bytes != 0) && p.a_bytes < 0x7FFFFF00u &&
-         (!p.c2 || p.a2_bytes < 0x7FFFFF00u) && (!p.rowbias || p.rows_per_group % 32 == 0) &&
-         (((int64_t)p.m - 1) * p.ldc + (p.geglu ? p.n / 2 : p.n)) * 2 < 0x7FFFFF00ll && (!p.res || (((int64_t)p.m - 1) * p.ld_res + p.n) * 2 < 0x7FFFFF00ll) &&
+         p.splits <= 1 && !p.ln_parts && p.a_bytes != 0 && p.w_bytes != 0 && (p.c2 == 0 || p.a2_bytes != 0) &&
+         (!p.rowbias || p.rows_per_group % 32 == 0) &&
+         act_out_fit31(p) &&  // (w_bytes needs no bound here: K = 320 and N <= 32 x 160 make the weights 3.3 MB at most)
          (wres_env == 1 || p.m >= 16384);
 }
 
@@ -508,25 +494,12 @@ inline int splitk_plan_dense(int m, int n, int nt, int geglu, int out_f32) {
 // ---- the launch plan: WHICH kernel instantiation a set of arguments runs, as a pure function of the arguments (the
 // product build has no environment knobs: CA_KNOB compiles to its default; experiment builds, -DCA_EXPERIMENTS, read
 // them for same-box A/B runs).  ca_gemm_plan_name / ca_conv3x3_plan_name report it without a launch;
-// tests/test_dispatch_plan.py pins every shape of the benchmark workload to its label.
-enum PlanKind {
-  PK_WRES = 0,    // weight-resident streaming kernel, 160-column panels (ca_gemm_wres.h)
-  PK_PP2,         // 128 x 320 ping-pong tiles (ca_gemm_pp2.h)
-  PK_PP2_SPLITK,  // the same with K ranges writing fp32 slabs + k_splitk_reduce
-  PK_DMA,         // k_gemm_dma<bm, bn>: LDS-DMA staging, nbuf LDS stages
-  PK_DMA_SPLITK,  // k_gemm_dma<128,128> K ranges + k_splitk_reduce
-  PK_REG,         // k_gemm<bm, bn>: register-staged (channel counts the DMA path cannot take)
-  PK_PS,          // persistent streaming kernel, 128 x 320 tiles (ca_gemm_ps.h)
-  PK_PQ,          // persistent streaming kernel, 256 x 320 tiles / 128 x 80 wave tiles (ca_gemm_pq.h)
-  PK_AR,          // activation-resident kernel, 128-row tiles / 128 x 80 wave tiles, W fragments from L2 (ca_gemm_ar.h)
-  PK_EXP,         // experiment builds only: `exp` selects (see launch_gemm)
-};
+// tests/test_dispatch_plan.py pins every shape of the benchmark workload to its label.  (PlanKind: ca_gemm_core.h)
 struct GemmPlan {
-  int kind;
-  int bm, bn, waves_m, waves_n, nbuf;
+  PlanKind kind;
+  int bm, bn, nbuf;   // block tile; LDS stages of k_gemm_dma
   int splits;       // K ranges (PK_*_SPLITK)
   unsigned tiles;   // output tiles (x splits = blocks) of the ping-pong kernels
-  int exp;
 };
 
 inline bool dma_capable(const GemmKParams& p) {
@@ -537,9 +510,7 @@ inline bool dma_capable(const GemmKParams& p) {
 // Persistent streaming kernel (ca_gemm_ps.h): can this launch run on it?
 inline bool ps_capable(const GemmKParams& p) {
   const int nt = p.taps * p.kc_tiles;
-  const int64_t ncols = p.geglu ? p.n / 2 : p.n;
-  const bool fits32 = (((int64_t)p.m - 1) * p.ldc + ncols) * 2 < 0x7FFFFF00ll && (!p.res || (((int64_t)p.m - 1) * p.ld_res + p.n) * 2 < 0x7FFFFF00ll) &&
-                      p.a_bytes < 0x7FFFFF00u && p.w_bytes < 0x7FFFFF00u && (!p.c2 || p.a2_bytes < 0x7FFFFF00u);
+  const bool fits32 = act_out_fit31(p) && p.w_bytes < FIT31;  // (the weights of a convolution or a wide projection can be large: bounded too)
   const bool aligned = ((uintptr_t)p.c & 15) == 0 && (!p.res || ((uintptr_t)p.res & 15) == 0) && p.ldc % 8 == 0 && (!p.res || p.ld_res % 8 == 0);
   return dma_capable(p) && p.n % 320 == 0 && nt >= 2 && p.splits <= 1 && !p.out_f32 && !p.ln_inline && (p.ln_parts <= 2 || p.ln_parts == 4) && fits32 && aligned &&
          (!p.rowbias || p.rows_per_group % 64 == 0) && !(p.geglu && (p.res || p.row_sums)) && p.post == 1.f && p.act == CA_ACT_NONE;
@@ -555,10 +526,9 @@ inline bool pq_capable(const GemmKParams& p, int mode) {
          (!epi1 || (mode == 0 && !p.res && !p.rowbias && p.ln_parts == 0 && (!p.ln_colsum || p.ln_stats)));
 }
 
-inline GemmPlan plan_gemm(const GemmKParams& p, int mode, bool allow_pq = true) {
+inline GemmPlan plan_gemm(const GemmKParams& p, int mode) {
   GemmPlan g{};
   g.splits = 1;
-  const int kc = p.c1 + p.c2;
   const bool dma = dma_capable(p);
   const int nt = p.taps * p.kc_tiles;
   if (dma && p.splits > 1) {
@@ -577,7 +547,7 @@ inline GemmPlan plan_gemm(const GemmKParams& p, int mode, bool allow_pq = true) 
       }
     }
     g.kind = PK_DMA_SPLITK;
-    g.bm = 128, g.bn = 128, g.waves_m = 2, g.waves_n = 2, g.nbuf = 1, g.splits = p.splits;
+    g.bm = 128, g.bn = 128, g.nbuf = 1, g.splits = p.splits;
     g.tiles = (unsigned)(ceil_div_i(p.m, 128) * (p.n / 128));
     return g;
   }
@@ -586,7 +556,7 @@ inline GemmPlan plan_gemm(const GemmKParams& p, int mode, bool allow_pq = true) 
   // channel count of the SD1.5 UNet exactly and wins where the 128x128 grid under-fills the chip (<= 2 rounds of tiles:
   // the 16x16- and 32x32-latent levels, +10..19%); with many rounds the exposed epilogue of a one-block-per-CU kernel
   // (35..45% of a K = 1280 GEMM) loses against 4 co-resident blocks of k_gemm_dma.
-  static const int pp_env = CA_KNOB("CA_GEMM_PP", -1);  // (experiment builds: 0 = never, 2 = whenever N % 320 == 0, 1 / 3 / 4 = ca_gemm_pp.h / pp3.h)
+  static const int pp_env = CA_KNOB("CA_GEMM_PP", -1);  // (experiment builds: 0 = never, 2 = whenever N % 320 == 0)
   // Persistent streaming kernel (ca_gemm_ps.h): same main loop as the 128 x 320 ping-pong kernel, but no launch / prologue
   // bubble per tile and an epilogue whose stores nothing waits for.  Measured against the kernel each shape had before
   // (tools/ps_check.py --time, same box): 131072x320x1280 149 vs 180 us, 32768x640x640 50 vs 58, 8192x1280x1280 41.6 vs 43.3,
@@ -606,7 +576,7 @@ inline GemmPlan plan_gemm(const GemmKParams& p, int mode, bool allow_pq = true) 
   // 64.37 / 64.34, + folded-LayerNorm projections 63.75 / 63.94.
   // CA_GEMM_PQ (experiment builds): 0 = never, 1 = every launch it can take
   static const int pq_env = CA_KNOB("CA_GEMM_PQ", -1);
-  if (allow_pq && pq_env != 0 && pq_capable(p, mode)) {
+  if (pq_env != 0 && pq_capable(p, mode)) {
     const int64_t tiles = (int64_t)ceil_div_i(p.m, 256) * (p.n / 320);
     // (whole rounds of 256 tiles, or many: 8192x3840x1280 = 384 tiles measured 107 vs 95 us on the 128x128 kernel)
     // (convolutions, clean build: 64x64 latents 640->320 468 vs 508, 640->640 908 vs 986, 32x32 1280->1280 820 vs 929; 320->320 at 64x64 -- N = 320, 45 K tiles -- 256 vs 251: not)
@@ -640,84 +610,36 @@ inline GemmPlan plan_gemm(const GemmKParams& p, int mode, bool allow_pq = true) 
     g.bm = 256, g.bn = 160;
     return g;
   }
-  if (dma && pp_env != 0 && pp_env != 3 && nt >= 2 && p.n % 320 == 0 && p.splits <= 1) {  // 128 x 320 tiles
+  if (dma && pp_env != 0 && nt >= 2 && p.n % 320 == 0 && p.splits <= 1) {  // 128 x 320 tiles
     const int64_t tiles = (int64_t)ceil_div_i(p.m, 128) * (p.n / 320);
-#ifdef CA_EXPERIMENTS
-    const int64_t ncols = p.geglu ? p.n / 2 : p.n;
-    const bool fits32 = (((int64_t)p.m - 1) * p.ldc + ncols) * 2 < 0x7FFFFF00ll && (!p.res || (((int64_t)p.m - 1) * p.ld_res + p.n) * 2 < 0x7FFFFF00ll) &&
-                        p.a_bytes < 0x7FFFFF00u && p.w_bytes < 0x7FFFFF00u && (!p.c2 || p.a2_bytes < 0x7FFFFF00u);
-    const bool pp3_ok = nt >= 5 && !p.out_f32 && !p.ln_parts && fits32 && (!p.rowbias || p.rows_per_group % 64 == 0) && p.ldc % 8 == 0 && (!p.res || p.ld_res % 8 == 0);
-    if (pp3_ok && pp_env == 4) {
-      g.kind = PK_EXP, g.exp = 321, g.tiles = (unsigned)tiles;
-      return g;
-    }
-#endif
     // (thresholds re-checked inside the step, same box, interleaved: dense 768 / 1024 tiles +0.25 ms, conv 512 +0.7, conv 128 +0.2)
-    if (p.row_sums || pp_env == 1 || pp_env == 2 || (pp_env < 0 && tiles >= 128 && nt >= 10 && (tiles <= 256 || (tiles <= 512 && mode == 0)))) {
+    if (p.row_sums || pp_env == 2 || (pp_env < 0 && tiles >= 128 && nt >= 10 && (tiles <= 256 || (tiles <= 512 && mode == 0)))) {
       g.kind = PK_PP2;
       g.bm = 128, g.bn = 320, g.tiles = (unsigned)tiles;
       return g;
     }
   }
-#ifdef CA_EXPERIMENTS
-  if (dma && (pp_env == 1 || pp_env == 3) && nt >= 2 && p.n % 128 == 0 && p.splits <= 1) {
-    const bool bn256 = p.n % 256 == 0;
-    g.kind = PK_EXP, g.exp = bn256 ? 256 : 128;
-    g.tiles = (unsigned)((int64_t)ceil_div_i(p.m, 256) * (p.n / (bn256 ? 256 : 128)));
-    return g;
-  }
-#endif
   // 128x128 tiles unless N is not a multiple of 128 or the grid would leave CUs idle
   // (8x8 / 16x16 latent levels: M = 2048 / 8192 rows -> < 2 blocks per CU with the big tile).
-  static const int bn_env = CA_KNOB("CA_GEMM_BN", 0);
-  bool wide = p.n % 128 == 0 && (int64_t)ceil_div_i(p.m, 128) * ceil_div_i(p.n, 128) >= 512;
-  if (bn_env == 64) wide = false;
-  if (bn_env == 128 && p.n % 128 == 0) wide = true;
+  const bool wide = p.n % 128 == 0 && (int64_t)ceil_div_i(p.m, 128) * ceil_div_i(p.n, 128) >= 512;
   const int64_t blocks = (int64_t)ceil_div_i(p.m, 128) * ceil_div_i(p.n, wide ? 128 : 64);
   // LDS stages: ONE buffer (32 KB, two barriers per tile) lets 4 blocks share a CU, whose MFMA phases
   // cover each other's transfer latency: measured +10..25% over double buffering (2 blocks per CU)
   // and far better than 3-4 stage rings (1 block per CU).  Small grids (< 2 blocks per CU) have no
-  // co-resident blocks to overlap with and keep the double buffer.
-  static const int nbuf_env = CA_KNOB("CA_GEMM_NBUF", 0);
-  // (round 4: three stages instead of two for the small grids -- their K loops are chains of DMA round trips with 8 MFMAs per
-  //  wave and tile in between; two tiles in flight instead of one: -0.3 ms per step, 62.0 vs 62.3 interleaved three times.  The
-  //  128 x 64 tile's ring is 74 KB: two blocks still share a CU.  Four stages (98 KB, one block per CU) lose.)
-  int nbuf = nbuf_env ? nbuf_env : (blocks >= 512 ? 1 : 3);
-  if (nbuf < 1 || nbuf > 4) nbuf = 3;
-  static const int ring_env = CA_KNOB("CA_GEMM_RING", 0);  // (experiment builds: 2 = the round-3 double buffer, 4 = four stages, for the launches that take the ring)
-  if (nbuf == 3 && (ring_env == 2 || ring_env == 4)) nbuf = ring_env;
+  // co-resident blocks to overlap with: three stages (round 4; before that the double buffer) -- their K loops are chains of
+  // DMA round trips with 8 MFMAs per wave and tile in between; two tiles in flight instead of one: -0.3 ms per step, 62.0 vs
+  // 62.3 interleaved three times.  The 128 x 64 tile's ring is 74 KB: two blocks still share a CU.  Four stages (98 KB, one
+  // block per CU) lose.  (wide implies blocks >= 512: the 128 x 128 tile only ever runs single-buffered.)
+  const int nbuf = blocks >= 512 ? 1 : 3;
   // N = 320 / 960 (every projection and conv of the 64x64-latent level): 128x160 tiles divide N
   // exactly and read the A panel 2 / 6 times instead of 5 / 15 times
-  static const int t160_env = CA_KNOB("CA_GEMM_T160", 1);
-  if (dma && !wide && t160_env && p.n % 160 == 0 && (int64_t)ceil_div_i(p.m, 128) * (p.n / 160) >= 512) {
+  if (dma && !wide && p.n % 160 == 0 && (int64_t)ceil_div_i(p.m, 128) * (p.n / 160) >= 512) {
     g.kind = PK_DMA;
-    g.bm = 128, g.bn = 160, g.waves_m = 2, g.waves_n = 2, g.nbuf = 1;
+    g.bm = 128, g.bn = 160, g.nbuf = 1;
     return g;
   }
-#ifdef CA_EXPERIMENTS
-  // CA_GEMM_BIG: 1 = 256x128 tiles whenever the grid allows, 3 = the wide feed-forward GEMMs only (the round-1 default:
-  // +4..8% on 8192x10240x1280 and 32768x5120x640 measured in isolation; inside the step, with the ControlNet stream
-  // beside it, the 128x128 tiles are 0.3 ms faster), 2 = 4 waves x (128 x 64) per wave, 2 blocks per CU
-  static const int big_env = CA_KNOB("CA_GEMM_BIG", 0);
-  const bool big = big_env == 1 || (big_env == 3 && mode == 0 && p.n >= 5120 && kc >= 640);
-  if (dma && big_env == 2 && p.n % 128 == 0 && (int64_t)ceil_div_i(p.m, 256) * (p.n / 128) >= 256) {
-    g.kind = PK_EXP, g.exp = 2562;
-    return g;
-  }
-  if (dma && big && p.n % 128 == 0 && (int64_t)ceil_div_i(p.m, 256) * (p.n / 128) >= 512) {
-    g.kind = PK_EXP, g.exp = 2561;
-    return g;
-  }
-  static const int kt_env = CA_KNOB("CA_GEMM_KT", 64);
-  if (wide && dma && kt_env == 32) {
-    g.kind = PK_EXP, g.exp = 32;
-    return g;
-  }
-#else
-  (void)kc;
-#endif
   g.kind = dma ? PK_DMA : PK_REG;
-  g.bm = 128, g.bn = wide ? 128 : 64, g.waves_m = wide ? 2 : 4, g.waves_n = wide ? 2 : 1, g.nbuf = dma ? nbuf : 2;
+  g.bm = 128, g.bn = wide ? 128 : 64, g.nbuf = dma ? nbuf : 2;
   return g;
 }
 
@@ -726,7 +648,7 @@ inline GemmPlan plan_gemm(const GemmKParams& p, int mode, bool allow_pq = true) 
 inline int row_sums_parts_of(GemmKParams p) {  // partial sums per row the launch can leave (0: none)
   p.row_sums = nullptr;
   if (p.geglu || p.out_f32) return 0;
-  const int k = plan_gemm(p, 0).kind;
+  const PlanKind k = plan_gemm(p, 0).kind;
   if (k == PK_PP2 || k == PK_PS) return p.n / 320;          // one (sum, sum of squares) per 320-column tile
   if (k == PK_PQ && !p.ln_colsum && !p.ln_stats) return 4 * (p.n / 320);  // the 256 x 320 kernel: one per 80-column wave quarter
   return 0;
@@ -741,27 +663,26 @@ inline void plan_label(const GemmPlan& g, char* buf, int len) {
     case PK_PS: snprintf(buf, len, "ps128x320"); break;
     case PK_PQ: snprintf(buf, len, "pq256x320"); break;
     case PK_PP2_SPLITK: snprintf(buf, len, "pp128x320_splitk%d", g.splits); break;
-    case PK_DMA: snprintf(buf, len, "%dx%d%s", g.bm, g.bn, g.nbuf == 2 ? "_db" : g.nbuf == 3 ? "_r3" : g.nbuf == 4 ? "_r4" : ""); break;
+    case PK_DMA: snprintf(buf, len, "%dx%d%s", g.bm, g.bn, g.nbuf == 3 ? "_r3" : ""); break;
     case PK_DMA_SPLITK: snprintf(buf, len, "128x128_splitk%d", g.splits); break;
     case PK_REG: snprintf(buf, len, "reg_%dx%d", g.bm, g.bn); break;
-    default: snprintf(buf, len, "exp%d", g.exp); break;
   }
 }
 
 template <int DT, int MODE>
 int launch_gemm(const GemmKParams& p, hipStream_t st) {
   const GemmPlan g = plan_gemm(p, MODE);
-  const dim3 grid(ceil_div_i(p.m, g.bm ? g.bm : 128) * ceil_div_i(p.n, g.bn ? g.bn : 128));
+  const dim3 grid(ceil_div_i(p.m, g.bm) * ceil_div_i(p.n, g.bn));  // (the one-block-per-tile kernels below)
   switch (g.kind) {
-    case PK_WRES: return ca_launch_gemm_pp(p, DT, MODE, 160, 0u, st);
+    case PK_WRES: return ca_launch_gemm_pp(p, DT, MODE, PK_WRES, 0u, st);
     case PK_AR: return ca_launch_gemm_ar(p, DT, st);
-    case PK_PP2: return ca_launch_gemm_pp(p, DT, MODE, 320, g.tiles, st);
-    case PK_PS: return ca_launch_gemm_pp(p, DT, MODE, 322, g.tiles, st);
-    case PK_PQ: return ca_launch_gemm_pp(p, DT, MODE, 323, g.tiles, st);
+    case PK_PP2:
+    case PK_PS:
+    case PK_PQ: return ca_launch_gemm_pp(p, DT, MODE, g.kind, g.tiles, st);
     case PK_PP2_SPLITK: {
       GemmKParams q = p;
       q.splits = g.splits;
-      const int rc = ca_launch_gemm_pp(q, DT, MODE, 320, g.tiles * (unsigned)g.splits, st);
+      const int rc = ca_launch_gemm_pp(q, DT, MODE, PK_PP2, g.tiles * (unsigned)g.splits, st);
       hipLaunchKernelGGL((k_splitk_reduce<DT>), dim3(ceil_div_i((int64_t)q.m * (q.n / 8), 256)), dim3(256), 0, st, q);
       return rc;
     }
@@ -769,32 +690,20 @@ int launch_gemm(const GemmKParams& p, hipStream_t st) {
       hipLaunchKernelGGL((k_gemm_dma<DT, 128, 128, 2, 2, MODE, 1>), dim3(g.tiles * (unsigned)p.splits), dim3(256), 0, st, p);
       hipLaunchKernelGGL((k_splitk_reduce<DT>), dim3(ceil_div_i((int64_t)p.m * (p.n / 8), 256)), dim3(256), 0, st, p);
       return CA_OK;
-    case PK_DMA:
-      if (g.bn == 160) hipLaunchKernelGGL((k_gemm_dma<DT, 128, 160, 2, 2, MODE, 1>), grid, dim3(256), 0, st, p);
+    case PK_DMA:  // the instantiations plan_gemm can ask for
+      if (g.bn == 160 && g.nbuf == 1) hipLaunchKernelGGL((k_gemm_dma<DT, 128, 160, 2, 2, MODE, 1>), grid, dim3(256), 0, st, p);
       else if (g.bn == 128 && g.nbuf == 1) hipLaunchKernelGGL((k_gemm_dma<DT, 128, 128, 2, 2, MODE, 1>), grid, dim3(256), 0, st, p);
-      else if (g.bn == 128 && g.nbuf == 4) hipLaunchKernelGGL((k_gemm_dma<DT, 128, 128, 2, 2, MODE, 4>), grid, dim3(256), 0, st, p);
-      else if (g.bn == 128 && g.nbuf == 3) hipLaunchKernelGGL((k_gemm_dma<DT, 128, 128, 2, 2, MODE, 3>), grid, dim3(256), 0, st, p);
-      else if (g.bn == 128) hipLaunchKernelGGL((k_gemm_dma<DT, 128, 128, 2, 2, MODE, 2>), grid, dim3(256), 0, st, p);
-      else if (g.bn == 64 && g.nbuf == 4) hipLaunchKernelGGL((k_gemm_dma<DT, 128, 64, 4, 1, MODE, 4>), grid, dim3(256), 0, st, p);
+      else if (g.bn == 64 && g.nbuf == 1) hipLaunchKernelGGL((k_gemm_dma<DT, 128, 64, 4, 1, MODE, 1>), grid, dim3(256), 0, st, p);
       else if (g.bn == 64 && g.nbuf == 3) hipLaunchKernelGGL((k_gemm_dma<DT, 128, 64, 4, 1, MODE, 3>), grid, dim3(256), 0, st, p);
-      else if (g.nbuf == 1) hipLaunchKernelGGL((k_gemm_dma<DT, 128, 64, 4, 1, MODE, 1>), grid, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((k_gemm_dma<DT, 128, 64, 4, 1, MODE, 2>), grid, dim3(256), 0, st, p);
+      else break;
       return CA_OK;
     case PK_REG:
       if (g.bn == 128) hipLaunchKernelGGL((k_gemm<DT, 128, 128, 2, 2, MODE>), grid, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((k_gemm<DT, 128, 64, 4, 1, MODE>), grid, dim3(256), 0, st, p);
+      else if (g.bn == 64) hipLaunchKernelGGL((k_gemm<DT, 128, 64, 4, 1, MODE>), grid, dim3(256), 0, st, p);
+      else break;
       return CA_OK;
-    default: break;
   }
-#ifdef CA_EXPERIMENTS
-  if (g.exp == 321 || g.exp == 256 || g.exp == 128) return ca_launch_gemm_pp(p, DT, MODE, g.exp, g.tiles, st);
-  if (g.exp == 2562) hipLaunchKernelGGL((k_gemm_dma<DT, 256, 128, 2, 2, MODE, 1>), dim3(ceil_div_i(p.m, 256) * (p.n / 128)), dim3(256), 0, st, p);
-  if (g.exp == 2561) hipLaunchKernelGGL((k_gemm_dma<DT, 256, 128, 4, 2, MODE, 1>), dim3(ceil_div_i(p.m, 256) * (p.n / 128)), dim3(512), 0, st, p);
-  if (g.exp == 32) hipLaunchKernelGGL((k_gemm_dma<DT, 128, 128, 2, 2, MODE, 2, 32>), dim3(ceil_div_i(p.m, 128) * ceil_div_i(p.n, 128)), dim3(256), 0, st, p);
-  return CA_OK;
-#else
-  return CA_ERR_LAUNCH;
-#endif
+  CA_FAIL(CA_ERR_LAUNCH, "ca_gemm: no kernel for plan kind %d, tile %dx%d, %d stages", (int)g.kind, g.bm, g.bn, g.nbuf);
 }
 
 // descriptor size in bytes, or 0 when the buffer is too large for 32-bit offsets (-> register variant)
@@ -901,8 +810,8 @@ extern "C" int ca_gemm(const ca_gemm_args* a, void* stream) {
   int rc = gemm_prepare(a, p);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (a->dtype == CA_BF16) launch_gemm<CA_BF16, 0>(p, st);
-  else launch_gemm<CA_F16, 0>(p, st);
+  rc = a->dtype == CA_BF16 ? launch_gemm<CA_BF16, 0>(p, st) : launch_gemm<CA_F16, 0>(p, st);
+  if (rc) return rc;
   CA_CHECK_LAUNCH("ca_gemm");
   return CA_OK;
 }
@@ -1106,7 +1015,7 @@ static int launch_conv_wino(const ca_conv_args* a, const GemmKParams& cp, hipStr
   q.w_group_rows = (int)tiles;
   q.w_group_stride = (unsigned)((int64_t)a->cout * kc * 2);
   const unsigned gemm_tiles = (unsigned)((q.m / 256) * (q.n / 320));
-  int rc = ca_launch_gemm_pp(q, a->dtype, 0, 323, gemm_tiles, st);
+  int rc = ca_launch_gemm_pp(q, a->dtype, 0, PK_PQ, gemm_tiles, st);
   if (rc) return rc;
   if (a->dtype == CA_BF16) hipLaunchKernelGGL((k_wino_out<CA_BF16>), dim3((unsigned)((out_threads + 255) / 256)), dim3(256), 0, st, w);
   else hipLaunchKernelGGL((k_wino_out<CA_F16>), dim3((unsigned)((out_threads + 255) / 256)), dim3(256), 0, st, w);
@@ -1137,8 +1046,8 @@ extern "C" int ca_conv3x3(const ca_conv_args* a, void* stream) {
   CA_REQUIRE(!a->x_is_wino_v, "ca_conv3x3: x_is_wino_v, but the Winograd route does not take these arguments (images=%d %dx%d cin=%d+%d cout=%d dtype=%d w_wino=%p "
              "workspace=%p of %lld bytes, needs %lld)", a->images, a->hin, a->win, a->cin1, a->cin2, a->cout, a->dtype, a->w_wino, a->workspace,
              (long long)a->workspace_bytes, (long long)wino_workspace_bytes(a));
-  if (a->dtype == CA_BF16) launch_gemm<CA_BF16, 1>(p, st);
-  else launch_gemm<CA_F16, 1>(p, st);
+  rc = a->dtype == CA_BF16 ? launch_gemm<CA_BF16, 1>(p, st) : launch_gemm<CA_F16, 1>(p, st);
+  if (rc) return rc;
   CA_CHECK_LAUNCH("ca_conv3x3");
   return CA_OK;
 }

@@ -28,8 +28,7 @@ using namespace ca_gemm_detail;
 template <int DT>
 int launch_ar(const GemmKParams& p, hipStream_t st) {
   const int tiles_m = (p.m + 127) / 128;
-  const unsigned c_bytes = (unsigned)((((int64_t)p.m - 1) * p.ldc + (p.geglu ? p.n / 2 : p.n)) * 2);
-  const unsigned res_bytes = p.res ? (unsigned)((((int64_t)p.m - 1) * p.ld_res + p.n) * 2) : 0u;
+  const unsigned c_bytes = (unsigned)c_extent_bytes(p), res_bytes = (unsigned)res_extent_bytes(p);  // (bounded by wres_eligible)
   const int slots = 2 * ar_cu_count();  // two blocks (80 KB of LDS, four waves each) per CU
   const unsigned grid = (unsigned)(tiles_m < slots ? tiles_m : slots);
   float* ws = p.ln_inline ? p.partial : nullptr;

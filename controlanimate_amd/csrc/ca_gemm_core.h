@@ -48,10 +48,6 @@ struct GemmKParams {
 };
 
 constexpr int BK = 64;
-#ifndef CA_GEMM_ABLATE
-#define CA_GEMM_ABLATE 0  // timing experiments only: 1 = no MFMA / fragment reads (DMA + barriers only), 2 = no DMA after tile 0,
-                          // 3 = 2 + one barrier per tile, 4 = 2 + fragments read once (MFMA + barriers only), 5 = 2 + no barriers
-#endif
 
 // Tile order inside an XCD's contiguous id range: groups of GROUP_M row-tiles are swept column by
 // column, so the ~128 blocks resident on an XCD share 8 A panels and ~16 W panels in its 4 MB L2.
@@ -388,8 +384,37 @@ __device__ __forceinline__ void gemm_epilogue(const GemmKParams& p, f32x4 (&acc)
 
 constexpr unsigned DMA_OOB = 0xFFFFFFF0u;  // beyond any descriptor size we accept -> hardware writes zeros
 
+// ---- host side ------------------------------------------------------------------------------------------------------
+// The launch plan: WHICH kernel a set of arguments runs (plan_gemm in ca_gemm.hip decides, the launchers switch on it).
+enum PlanKind {
+  PK_WRES = 0,    // weight-resident streaming kernel, 160-column panels (ca_gemm_wres.h)
+  PK_PP2,         // 128 x 320 ping-pong tiles (ca_gemm_pp2.h)
+  PK_PP2_SPLITK,  // the same with K ranges writing fp32 slabs + k_splitk_reduce
+  PK_DMA,         // k_gemm_dma<bm, bn>: LDS-DMA staging, nbuf LDS stages
+  PK_DMA_SPLITK,  // k_gemm_dma<128,128> K ranges + k_splitk_reduce
+  PK_REG,         // k_gemm<bm, bn>: register-staged (channel counts the DMA path cannot take)
+  PK_PS,          // persistent streaming kernel, 128 x 320 tiles (ca_gemm_ps.h)
+  PK_PQ,          // persistent streaming kernel, 256 x 320 tiles / 128 x 80 wave tiles (ca_gemm_pq.h)
+  PK_AR,          // activation-resident kernel, 128-row tiles / 128 x 80 wave tiles, W fragments from L2 (ca_gemm_ar.h)
+};
+
+// The streaming kernels address the output and the residual through buffer descriptors with 32-bit byte offsets and use
+// offsets from 2 GB up as "out of range": every operand must end below FIT31.  A capability predicate and the descriptor
+// size its kernel is launched with come from the same functions.
+constexpr int64_t FIT31 = 0x7FFFFF00ll;
+// bytes from the first stored output element to the end of the last one (GEGLU stores N / 2 columns per row)
+inline int64_t c_extent_bytes(const GemmKParams& p) { return (((int64_t)p.m - 1) * p.ldc + (p.geglu ? p.n / 2 : p.n)) * 2; }
+// the same for the residual (always N columns: a GEGLU launch that has one never reaches these kernels); 0 without one
+inline int64_t res_extent_bytes(const GemmKParams& p) { return p.res ? (((int64_t)p.m - 1) * p.ld_res + p.n) * 2 : 0; }
+// output, residual and activation sources addressable with 31-bit byte offsets.  (The weights are not part of it:
+// ps_capable bounds w_bytes as well, wres_eligible does not -- see there.)
+inline bool act_out_fit31(const GemmKParams& p) {
+  return c_extent_bytes(p) < FIT31 && res_extent_bytes(p) < FIT31 && p.a_bytes < FIT31 && (!p.c2 || p.a2_bytes < FIT31);
+}
+
 }  // namespace ca_gemm_detail
 
-// ping-pong 256 x BN kernel family (ca_gemm_pp.hip); bn = 256 | 128
-int ca_launch_gemm_pp(const ca_gemm_detail::GemmKParams& p, int dtype, int mode, int bn, unsigned tiles, hipStream_t st);
+// the tiled kernels of ca_gemm_pp.hip: kind = PK_WRES | PK_PP2 | PK_PS | PK_PQ; `tiles` = blocks of PK_PP2 (tiles x K ranges
+// with split-K), output tiles of the persistent kernels, unused by PK_WRES
+int ca_launch_gemm_pp(const ca_gemm_detail::GemmKParams& p, int dtype, int mode, ca_gemm_detail::PlanKind kind, unsigned tiles, hipStream_t st);
 int ca_launch_gemm_ar(const ca_gemm_detail::GemmKParams& p, int dtype, hipStream_t st);  // ca_gemm_ar.hip

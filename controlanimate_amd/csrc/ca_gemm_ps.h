@@ -11,7 +11,7 @@
 //   * DMA COMPLETION WITHOUT THE VMEM COUNTER.  On gfx950 loads and stores share one counter and retire out of order with
 //     respect to each other, so a wave that streams operands AND stores results can only wait for "all but the N youngest
 //     loads" by also waiting for its stores -- that made every persistent variant of round 2 pay for its epilogue stores
-//     inside the operand stream (ca_gemm_pp3.h).  Here every DMA unit is followed by one 4-byte LDS-DMA that fetches the
+//     inside the operand stream.  Here every DMA unit is followed by one 4-byte LDS-DMA that fetches the
 //     unit's sequence number from a global table into an LDS flag word of the issuing wave: loads return IN ORDER among
 //     themselves (the property a counted vmcnt relies on), so when the flag shows the number, the unit has landed.  The
 //     wave polls the flag with a ds_read in the shadow of its fragment reads (tools/probe_flag.hip: 1.01 polls per unit,
@@ -86,12 +86,7 @@ __device__ __forceinline__ int ca_ps_col(int j, int i, bool geglu) {
   return 32 * (j >> 1) + 8 * (i >> 2) + 4 * (j & 1) + (i & 3);
 }
 
-// FLAGS = false (experiment, CA_PS_FLAGS=0): the same kernel with COUNTED vmcnt waits instead of the LDS flags -- every VMEM
-// instruction of a wave is counted (`issued`), a unit remembers the count at its issue and is awaited with
-// vmcnt(issued - mark), which allows the epilogue's stores to stay outstanding behind it.  That is only correct if loads and
-// stores retire in issue order (what LLVM's waitcnt insertion assumes on gfx9, and what tools/probe_flag.hip mode 1 did not
-// contradict in 36 million checked slots; the round-2 report of out-of-order retirement may have been a miscount).
-template <int DT, int MODE, bool FLAGS = true>
+template <int DT, int MODE>
 __global__ __launch_bounds__(512, 2) void k_gemm_ps(GemmKParams p, int tiles_total, unsigned c_bytes, unsigned res_bytes) {
   constexpr int BM = 128, BN = 320, KT = 64;
   constexpr int TM = 4, TN = 5;
@@ -190,7 +185,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm_ps(GemmKParams p, int tiles_tot
 
   auto dma_set_tile = [&](int seq, int m0, int n0) __attribute__((always_inline)) {
     // everything below is recomputed from the lane id on purpose: hipcc hoists lane-dependent invariants out of the
-    // tile loop and then SPILLS them (ca_gemm_pp3.h).  The empty asm makes the lane id opaque here.
+    // tile loop and then SPILLS them (seen in the round-2 persistent kernel).  The empty asm makes the lane id opaque here.
     int lane_o = lane;
     asm volatile("" : "+v"(lane_o));
     const int r8 = lane_o >> 3, cp = lane_o & 7;
@@ -255,15 +250,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm_ps(GemmKParams p, int tiles_tot
     }
   };
 
-  int mark_u[4] = {0, 0, 0, 0};  // FLAGS == false: `issued` right after the unit in flag slot s
   auto issue_flag = [&](int slot, int seqno) __attribute__((always_inline)) {
-    if (!FLAGS) {
-      if (slot == 0) mark_u[0] = issued;
-      else if (slot == 1) mark_u[1] = issued;
-      else if (slot == 2) mark_u[2] = issued;
-      else mark_u[3] = issued;
-      return;
-    }
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_seq, (__attribute__((address_space(3))) void*)(my_flags + slot * 256), 4, 0u, (unsigned)(seqno & 1023) * 4u, 0, 0);
     issued += 1;
   };
@@ -334,20 +321,12 @@ __global__ __launch_bounds__(512, 2) void k_gemm_ps(GemmKParams p, int tiles_tot
   // earlier in the phase (behind the fragment reads); the slow path re-reads with a short sleep and gives up after ~2^20
   // polls (a hung wave would take the whole device down; wrong results are caught by the tests, a hang is not).
   auto flag_begin = [&](int slot) __attribute__((always_inline)) -> unsigned {
-    if (!FLAGS) return 0u;
     unsigned fv;
     const unsigned addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)(my_flags + slot * 256);
     asm volatile("ds_read_b32 %0, %1" : "=v"(fv) : "v"(addr) : "memory");
     return fv;
   };
   auto flag_finish = [&](int slot, int seqno, unsigned fv) __attribute__((always_inline)) {
-    if (!FLAGS) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      const int n = issued - (slot == 0 ? mark_u[0] : slot == 1 ? mark_u[1] : slot == 2 ? mark_u[2] : mark_u[3]);
-      if (n == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");  // the steady state: one A/B0 unit (4) and one B1 unit (3) younger
-      else ca_ps_vm_wait(n);
-      return;
-    }
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fv)::"memory");
     const unsigned want = (unsigned)(seqno & 1023);
     if ((unsigned)__builtin_amdgcn_readfirstlane(fv) == want) return;
@@ -461,7 +440,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm_ps(GemmKParams p, int tiles_tot
     const float a = (((0.f + q0[0]) + q0[2]) + q1[0]) + q1[2], b = (((0.f + q0[1]) + q0[3]) + q1[1]) + q1[3];  // (quarters in order)
     if (m < p.m) *reinterpret_cast<float2*>(p.row_sums + ((int64_t)m * tiles_n + rs_tn) * 2) = make_float2(a, b);
     // (NOT counted in `issued`: the compiler may branch around the store when no lane is active; an uncounted store only makes
-    //  the counted waits of the FLAGS == false variant one operation stricter, a phantom one would make them too weak)
+    //  the counted residual wait one operation stricter, a phantom one would make it too weak)
   };
 
   // ---- the epilogue of one tile, from the accumulators (see the header)

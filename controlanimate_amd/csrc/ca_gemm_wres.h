@@ -96,7 +96,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_wres(GemmKParams p, int panels,
   unsigned d_v1[2], d_v2[2];
   auto head_slab = [&]() {
     int lane_o = lane;
-    asm volatile("" : "+v"(lane_o));  // (keeps the address arithmetic where it is used: see ca_gemm_pp3.h)
+    asm volatile("" : "+v"(lane_o));  // (keeps the address arithmetic where it is used: see dma_set_tile in ca_gemm_ps.h)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int m = d_c * 256 + wid * 32 + h * 16 + (lane_o >> 2);

@@ -64,7 +64,7 @@ def conv_label(capi, images, h, cin, cout, *, cin2=0, stride=1, upsample=0, work
 
 # (M, N, K, keyword flags) -> label.  Rows = the dense launches of one config-2 denoise step (ControlNet + UNet3D,
 # `bench.py --shapes`), largest time share first.  Labels: wres160 = weight-resident K = 320 kernel, ps128x320 = persistent
-# streaming kernel (round 3), pq256x320 = its 256 x 320 / 128 x 80-wave-tile sibling (round 3), pp128x320 = ping-pong 128 x 320 tiles, BMxBN = k_gemm_dma tiles (_r3: a three-stage LDS ring, round 4; _db: two stages),
+# streaming kernel (round 3), pq256x320 = its 256 x 320 / 128 x 80-wave-tile sibling (round 3), pp128x320 = ping-pong 128 x 320 tiles, BMxBN = k_gemm_dma tiles (_r3: a three-stage LDS ring, round 4),
 # _splitkS = S K ranges + reduce, reg_ = register-staged fallback, ar128x64 = activation-resident K = 320 kernel (round 4: the launches
 # that hand over W in fragment order and, for in-kernel LayerNorm statistics, the 8 M bytes of scratch -- what kernels.gemm does).
 GEMMS = [
@@ -121,6 +121,33 @@ CONVS = [
     ((32, 64, 8, 320, dict()), "reg_128x64"),                         # conv_in (4 latent channels padded to 8)
     ((32, 32, 640, 640, dict(upsample=1)), "128x128"),                # (the 256 x 320 kernel's gather has no upsampling)
 ]
+
+
+# every name plan_label (csrc/ca_gemm.hip) can produce: the kernels a launch can reach.  (_splitkS: S = 2 .. 8 K ranges.)
+PLAN_LABELS = ({"wres160", "ar128x64", "pp128x320", "ps128x320", "pq256x320", "wino_pq256x320", "128x160", "128x128", "128x64", "128x64_r3",
+                "reg_128x128", "reg_128x64"} | {f"{t}_splitk{s}" for t in ("pp128x320", "128x128") for s in range(2, 9)})
+
+
+def test_every_plan_is_a_kernel_that_exists(capi):
+    """A sweep over sizes (up to 2^23 rows: past the 31-bit byte offsets of the streaming kernels) and epilogue flags: every launch
+    gets one of the labels above -- no experiment plan ("exp..."), no double-buffered or four-stage k_gemm_dma ("_db", "_r4")."""
+    seen = set()
+    for m in (32, 2048, 8192, 32768, 131072, 1 << 23):
+        for n in (4, 64, 320, 960, 1280, 5120, 10240):
+            for k in (8, 64, 320, 1280, 5120):
+                for kw in (dict(), dict(res=True), dict(workspace=True), dict(ln="stats"), dict(ln=2), dict(k2=k // 2), dict(rowbias=4096),
+                           dict(geglu=1), dict(geglu=1, ln="stats", workspace=True), dict(ln="inline", frag=True, workspace=True)):
+                    if (n < 8 and (kw.get("geglu") or kw.get("ln"))) or (kw.get("k2", 0) % 8) or (kw.get("ln") == "inline" and (k != 320 or m not in (32768, 131072) or n % 160 or n > 5120)):
+                        continue  # (arguments ca_gemm rejects -- in-kernel statistics are the K = 320 kernels' only -- : nothing to plan)
+                    seen.add(gemm_label(capi, m, n, k, **kw))
+    for images in (1, 32):
+        for h in (3, 8, 32, 64, 128):
+            for cin, cout in ((8, 320), (320, 4), (320, 320), (640, 320), (1280, 1280), (2560, 1280)):
+                for kw in (dict(), dict(workspace=False), dict(stride=2), dict(upsample=1), dict(cin2=cin // 2 if cin > 8 else 0)):
+                    seen.add(conv_label(capi, images, h, cin, cout, **kw))
+    assert seen <= PLAN_LABELS, sorted(seen - PLAN_LABELS)
+    assert not any(s.startswith("exp") or s.endswith(("_db", "_r4")) for s in seen)
+    assert len(seen) >= 12  # (the sweep reaches most kernels: it is not vacuous)
 
 
 @pytest.mark.parametrize("shape,label", GEMMS, ids=[f"gemm{m}x{n}x{k}{'_' + '_'.join(sorted(kw)) if kw else ''}" for (m, n, k, kw), _ in GEMMS])

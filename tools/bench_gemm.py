@@ -14,7 +14,7 @@ def timeit(fn, it=10):
     return s.elapsed_time(e) / it
 
 if __name__ == "__main__":
-    tag = f"NBUF={os.environ.get('CA_GEMM_NBUF','-')} BN={os.environ.get('CA_GEMM_BN','-')}"
+    tag = " ".join(f"{k}={v}" for k, v in os.environ.items() if k.startswith("CA_"))
     for (m, n, k) in [(131072, 320, 320), (131072, 2560, 320), (32768, 5120, 640), (8192, 10240, 1280), (131072, 320, 1280), (8192, 1280, 5120), (8192, 1280, 1280)]:
         a = torch.randn(m, k, device="cuda").half(); w = (torch.randn(n, k, device="cuda") * k ** -0.5).half()
         ms = timeit(lambda: K.gemm(a, w))

@@ -2,7 +2,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from controlanimate_amd import kernels as K
-from tools.pp_check import timeit
+from tools.bench_gemm import timeit
 tag = " ".join(f"{k}={v}" for k, v in os.environ.items() if k.startswith("CA_"))
 shapes = [(8192, 10240, k) for k in (640, 1280, 2560, 5120, 10240)] + [(8192, 8192, 8192), (16384, 4096, 1280), (65536, 1280, 1280)]
 if len(sys.argv) > 1:

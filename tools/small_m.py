@@ -1,6 +1,5 @@
 """The latency-bound GEMMs of the 8x8-latent level (M = 2048) and their neighbours: time per launch and dispatch label.
-Experiments build: CA_GEMM_NBUF=3|4 (ring depth of k_gemm_dma), CA_GEMM_BN=64|128 (tile width).
-    [CA_HIP_LIB=.../libcontrolanimate_hip_exp.so CA_GEMM_NBUF=3] python tools/small_m.py
+    [CA_HIP_LIB=.../libcontrolanimate_hip_exp.so CA_SPLITK_DENSE=0] python tools/small_m.py
 """
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
