@@ -101,9 +101,14 @@ __global__ __launch_bounds__(NW * 64) void k_attn(AttnKParams p) {
 
   f32x4 oacc[QT][DV16];
   float mref[QT], lrun[QT];  // mref: reference maximum, already multiplied by scale*log2(e)
+  // "Nothing seen yet" is a FINITE floor far below any score, not -inf: a key mask can hide every key of a tile (or of the
+  // whole row), and then -inf would meet itself -- exp2(-inf - -inf) in the rescale, fma(-inf, scale, +inf) in the exponent --
+  // and turn the row into NaN.  With the floor a hidden score gives exp2(-inf) = 0, a row that has seen nothing rescales by
+  // exp2(0) = 1, and the first visible score exceeds the floor by more than 2^8 and rescales the (all-zero) state by exp2(-huge) = 0.
+  constexpr float MREF_FLOOR = -1.0e30f;
 #pragma unroll
   for (int t = 0; t < QT; ++t) {
-    mref[t] = -INFINITY;
+    mref[t] = MREF_FLOOR;
     lrun[t] = 0.f;
 #pragma unroll
     for (int dt = 0; dt < DV16; ++dt) oacc[t][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -336,7 +341,10 @@ __global__ __launch_bounds__(NW * 64) void k_attn(AttnKParams p) {
       lsum = __shfl(lv, (((p.head_dim & 15) >> 2) << 4) + l15);
     }
     if (qi >= p.nq) continue;
-    const float inv = p.out_scale / lsum;
+    // a query whose keys are ALL hidden (key mask) has row sum 0: it gets zeros, and an accumulating launch leaves its row alone
+    const bool seen = lsum > 0.f;
+    if (!seen && p.accumulate) continue;
+    const float inv = seen ? p.out_scale / lsum : 0.f;
     u16* orow = op + (int64_t)qi * p.o_row;
 #pragma unroll
     for (int dt = 0; dt < DV16; ++dt) {

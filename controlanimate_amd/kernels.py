@@ -490,9 +490,10 @@ def attention_spatial(qkv: torch.Tensor, images: int, tokens: int, heads: int, c
 def attention_cross(q: torch.Tensor, kv: torch.Tensor, images: int, tokens: int, heads: int, kv_tokens: int,
                     kv_rows_per_batch: int, frames_per_kv: int, *, out: Optional[torch.Tensor] = None,
                     out_scale: float = 1.0, accumulate: bool = False, kv_row_offset: int = 0,
-                    kv_mod: int = 0) -> torch.Tensor:
+                    kv_mod: int = 0, key_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Cross-attention. q: [images*tokens, C]; kv: [kv_batches*kv_rows_per_batch, 2C] (k | v).
-    Image z uses kv batch (z // frames_per_kv) % kv_mod, rows [kv_row_offset, kv_row_offset + kv_tokens)."""
+    Image z uses kv batch (z // frames_per_kv) % kv_mod, rows [kv_row_offset, kv_row_offset + kv_tokens).
+    key_mask: uint8 [images, kv_tokens], 0 = that key is invisible to the image's queries."""
     c = q.shape[1]
     d = c // heads
     if out is None:
@@ -502,7 +503,7 @@ def attention_cross(q: torch.Tensor, kv: torch.Tensor, images: int, tokens: int,
                   q_strides=(tokens * q.stride(0), 0, q.stride(0)), o_strides=(tokens * out.stride(0), 0, out.stride(0)),
                   k_strides=(kv_rows_per_batch * ldk, 0, ldk), inner_count=1, kv_inner_count=1,
                   kv_div=frames_per_kv, batches=images, heads=heads, head_dim=d, nq=tokens, nk=kv_tokens,
-                  scale=d ** -0.5, out_scale=out_scale, accumulate=accumulate, kv_mod=kv_mod)
+                  scale=d ** -0.5, out_scale=out_scale, accumulate=accumulate, kv_mod=kv_mod, key_mask=key_mask)
     return out
 
 

@@ -448,7 +448,7 @@ typedef struct ca_attn_args {
    * transformers' CLIPTextModel `attention_mask` ([B, L] -> additive [B,1,1,L]): what Compel 2.0.2's default
    * DownweightMode.MASK passes for a down-weighted fragment such as `(muscle body)0.2`
    * (modules/controlanimate_pipeline.py:133-135, configs/prompts/SampleConfig.yaml:16).  NULL = no mask.  A query whose
-   * keys are ALL masked gets zeros. */
+   * keys are ALL masked gets zeros (with `accumulate`: its output row is left as it was). */
   const uint8_t* key_mask;
   int64_t key_mask_stride;
 } ca_attn_args;
