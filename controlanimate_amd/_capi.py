@@ -218,6 +218,10 @@ SYMBOLS = {
     "ca_canny_link": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "ca_canny_link_stage": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "ca_canny_emit": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    # added to ABI v16 (no struct or existing function changes, the number stays): the nearest-x2 upsampling convolution as four 2x2 phase convolutions (ConvArgs.w = w_phase [4, Cout, 2, 2, Cin])
+    "ca_conv_up2_phase_supported": (C.c_int, [C.POINTER(ConvArgs)]),
+    "ca_conv_up2_phase": (C.c_int, [C.POINTER(ConvArgs), C.c_void_p]),
+    "ca_conv_up2_phase_plan_name": (C.c_int, [C.POINTER(ConvArgs), C.c_char_p, C.c_int32]),
 }
 
 _lib = None

@@ -40,6 +40,7 @@ class Dispatch:
     xattn_ip_fused = True  # ... the IP-Adapter's image-prompt attention inside the text cross-attention's launch (ABI v13)
     conv_winograd = True  # Winograd F(2x2, 3x3) form of the deep convolutions at the small-latent levels (read at prepare() time)
     gn_winograd = True    # ... with the GroupNorm in front writing the transformed input itself (ca_groupnorm_args.wino_v)
+    conv_up2_phase = True  # Upsample3D's nearest-x2 + 3x3 as four 2x2 phase convolutions in one launch (ca_conv_up2_phase; read at prepare() and at run time)
     ln_row_sums = True    # LayerNorm statistics from the producing GEMM's epilogue
     repeat_kernel = True  # ca_repeat instead of torch.cat for the CFG-shared prefix
     ln_fold = True        # LayerNorm folded into the projection it feeds

@@ -1052,6 +1052,78 @@ extern "C" int ca_conv3x3(const ca_conv_args* a, void* stream) {
   return CA_OK;
 }
 
+// ---- nearest-x2 upsampling 3x3 convolution as four 2x2 phase convolutions in one launch (k_gemm_pq MODE 2, ca_gemm_pq.h).
+// An output pixel of parity (py, px) reads a 2x2 neighbourhood of the SOURCE image; the nine taps that land on the same source
+// pixel are summed at pack time (a->w = w_phase [4][cout][2][2][cin]): 4/9 of the multiply-adds of ca_conv3x3(upsample = 1).
+// up2_capable: what the kernel implements; up2_pays: where the form is taken by default (ca_conv_up2_phase_supported = both).
+static bool up2_capable(const ca_conv_args* a, GemmKParams& p) {
+  if (!a || !a->x || !a->w || !a->y || a->x2 || a->cin2 != 0 || a->images <= 0 || a->hin <= 0 || a->win <= 0) return false;
+  if (a->upsample != 1 || a->stride != 1 || a->pad_asym || a->out_f32 || a->x_is_wino_v || a->rowbias) return false;
+  if ((a->dtype != CA_F16 && a->dtype != CA_BF16) || a->act != CA_ACT_NONE || a->post_scale != 1.f) return false;
+  if (a->cin1 <= 0 || a->cin1 % BK != 0 || a->cout <= 0 || a->cout % 320 != 0) return false;
+  if ((((uintptr_t)a->x | (uintptr_t)a->w | (uintptr_t)a->y | (uintptr_t)a->residual) & 15) != 0) return false;
+  if (a->residual && (a->ld_res < a->cout || a->ld_res % 8 != 0)) return false;
+  const int64_t rows = (int64_t)a->images * a->hin * a->win;  // per phase: the source pixels
+  if (rows + a->win + 2 >= (1 << 23)) return false;           // packed row state of the gather: 24 signed bits of pixel index
+  p = GemmKParams{};
+  p.a = (const u16*)a->x;
+  p.w = (const u16*)a->w;
+  p.c = a->y;
+  p.bias = a->bias;
+  p.res = (const u16*)a->residual;
+  p.ldc = a->cout;
+  p.ld_res = a->ld_res;
+  p.a_bytes = desc_bytes(rows * a->cin1);
+  p.w_bytes = desc_bytes((int64_t)4 * a->cout * 4 * a->cin1);
+  p.n = a->cout;
+  p.c1 = a->cin1;
+  p.taps = 4;
+  p.tap_inner = 1;
+  p.kc_tiles = a->cin1 / BK;
+  p.hin = a->hin, p.win = a->win, p.hout = 2 * a->hin, p.wout = 2 * a->win;
+  p.stride = 1, p.ups = 1, p.pad_lo = 1;
+  p.rows_per_group = 1;
+  p.alpha = a->alpha, p.post = 1.f;
+  p.splits = 1;
+  p.up2_rows = (int)rows;
+  p.up2_tiles = ceil_div_i((int)rows, 256);
+  p.m = 4 * p.up2_tiles * 256;
+  p.up2_mag_w = a->win == 1 ? 0xFFFFFFFFu : (unsigned)((1ull << 32) / (unsigned)a->win);
+  p.up2_mag_h = a->hin == 1 ? 0xFFFFFFFFu : (unsigned)((1ull << 32) / (unsigned)a->hin);
+  p.w_group_stride = (unsigned)((int64_t)a->cout * 4 * a->cin1 * 2);
+  return p.a_bytes && p.w_bytes && act_out_fit31(p) && p.w_bytes < FIT31;
+}
+inline unsigned up2_tiles_total(const GemmKParams& p) { return (unsigned)(4 * p.up2_tiles * (p.n / 320)); }
+// Whole rounds of 256 tiles, or many (the rule of the 256 x 320 kernel's dense launches): 32 x 32x32 640->640 is 1024 tiles,
+// 32 x 16x16 1280->1280 is 512; 32 x 8x8 1280->1280 is 128 tiles -- half the chip -- and stays on the Winograd form.
+inline bool up2_pays(const GemmKParams& p) {
+  const unsigned tiles = up2_tiles_total(p);
+  return tiles >= 256 && (tiles % 256 == 0 || tiles >= 1024);
+}
+
+extern "C" int ca_conv_up2_phase_supported(const ca_conv_args* a) {
+  GemmKParams p{};
+  return up2_capable(a, p) && up2_pays(p) ? 1 : 0;
+}
+
+extern "C" int ca_conv_up2_phase(const ca_conv_args* a, void* stream) {
+  GemmKParams p{};
+  CA_REQUIRE(up2_capable(a, p), "ca_conv_up2_phase: arguments the phase form does not take (one fp16 / bf16 source with cin %% 64 == 0, cout %% 320 == 0, upsample = 1, "
+             "stride 1, symmetric padding, no row bias / activation / post scale / fp32 output, 16-byte aligned operands, < 2^23 source pixels)");
+  int rc = ca_launch_gemm_pp(p, a->dtype, 2, PK_PQ, up2_tiles_total(p), (hipStream_t)stream);
+  if (rc) return rc;
+  CA_CHECK_LAUNCH("ca_conv_up2_phase");
+  return CA_OK;
+}
+
+extern "C" int ca_conv_up2_phase_plan_name(const ca_conv_args* a, char* buf, int32_t len) {
+  CA_REQUIRE(buf && len > 0, "ca_conv_up2_phase_plan_name: buffer");
+  GemmKParams p{};
+  CA_REQUIRE(up2_capable(a, p), "ca_conv_up2_phase_plan_name: arguments the phase form does not take");
+  snprintf(buf, (size_t)len, "up2_pq256x320");
+  return CA_OK;
+}
+
 // ---- which kernel would these arguments run?  (no launch, no device access: the pointers only have to be non-NULL where
 // the launch requires them)
 extern "C" int ca_gemm_plan_name(const ca_gemm_args* a, char* buf, int32_t len) {

@@ -45,6 +45,12 @@ struct GemmKParams {
   // at w + g * w_group_stride BYTES -- the sixteen independent GEMMs of a Winograd convolution as one launch (ca_conv_wino.h).  0 = off.
   int w_group_rows;
   unsigned w_group_stride;
+  // nearest-x2 upsampling 3x3 convolution as four 2x2 phase convolutions (k_gemm_pq MODE 2, ca_conv_up2_phase): rows per phase
+  // (= source pixels, images * hin * win; 0 = off), 256-row tiles per phase, floor(2^32 / win) and floor(2^32 / hin) (capped at
+  // 2^32 - 1) for the row -> pixel maps.  m = 4 * up2_tiles * 256 (phase-major row tiles), taps = 4, w_group_stride = bytes of one
+  // phase's weights.
+  int up2_rows, up2_tiles;
+  unsigned up2_mag_w, up2_mag_h;
 };
 
 constexpr int BK = 64;
@@ -403,9 +409,10 @@ enum PlanKind {
 // size its kernel is launched with come from the same functions.
 constexpr int64_t FIT31 = 0x7FFFFF00ll;
 // bytes from the first stored output element to the end of the last one (GEGLU stores N / 2 columns per row)
-inline int64_t c_extent_bytes(const GemmKParams& p) { return (((int64_t)p.m - 1) * p.ldc + (p.geglu ? p.n / 2 : p.n)) * 2; }
+inline int64_t out_rows(const GemmKParams& p) { return p.up2_rows ? 4 * (int64_t)p.up2_rows : (int64_t)p.m; }  // (phase convolution: m counts padded row tiles)
+inline int64_t c_extent_bytes(const GemmKParams& p) { return ((out_rows(p) - 1) * p.ldc + (p.geglu ? p.n / 2 : p.n)) * 2; }
 // the same for the residual (always N columns: a GEGLU launch that has one never reaches these kernels); 0 without one
-inline int64_t res_extent_bytes(const GemmKParams& p) { return p.res ? (((int64_t)p.m - 1) * p.ld_res + p.n) * 2 : 0; }
+inline int64_t res_extent_bytes(const GemmKParams& p) { return p.res ? ((out_rows(p) - 1) * p.ld_res + p.n) * 2 : 0; }
 // output, residual and activation sources addressable with 31-bit byte offsets.  (The weights are not part of it:
 // ps_capable bounds w_bytes as well, wres_eligible does not -- see there.)
 inline bool act_out_fit31(const GemmKParams& p) {

@@ -95,12 +95,22 @@ int launch_pp(const GemmKParams& p, PlanKind kind, unsigned tiles, hipStream_t s
     default: return CA_ERR_LAUNCH;
   }
 }
+
+// mode 2, the four-phase upsampling convolution (ca_conv_up2_phase): the 256 x 320 kernel only
+template <int DT>
+int launch_up2(const GemmKParams& p, PlanKind kind, unsigned tiles, hipStream_t st) {
+  if (kind != PK_PQ) return CA_ERR_LAUNCH;
+  const unsigned grid = tiles < (unsigned)cu_count() ? tiles : (unsigned)cu_count();
+  hipLaunchKernelGGL((k_gemm_pq<DT, 2>), dim3(grid), dim3(512), 0, st, p, (int)tiles, (unsigned)c_extent_bytes(p), (unsigned)res_extent_bytes(p));
+  return CA_OK;
+}
 }  // namespace
 
 int ca_launch_gemm_pp(const ca_gemm_detail::GemmKParams& p0, int dtype, int mode, ca_gemm_detail::PlanKind kind, unsigned tiles, hipStream_t st) {
   static const int dbg = CA_KNOB("CA_PP_DBG", 0);  // (timing experiments: 1 = no epilogue, 2 = no main loop)
   ca_gemm_detail::GemmKParams p = p0;
   p.dbg = dbg;
+  if (mode == 2) return dtype == CA_BF16 ? launch_up2<CA_BF16>(p, kind, tiles, st) : launch_up2<CA_F16>(p, kind, tiles, st);
   if (dtype == CA_BF16) return mode ? launch_pp<CA_BF16, 1>(p, kind, tiles, st) : launch_pp<CA_BF16, 0>(p, kind, tiles, st);
   return mode ? launch_pp<CA_F16, 1>(p, kind, tiles, st) : launch_pp<CA_F16, 0>(p, kind, tiles, st);
 }

@@ -22,6 +22,12 @@
 // Requirements: N % 320 == 0, >= 2 K tiles, fp16 / bf16 output, no row sums / activation / second dense source, LayerNorm fold
 // and GEGLU only without a residual (EPI = 1), 32-bit byte offsets, row-bias groups of a multiple of 128 rows; convolutions: pad 1, no upsampling, < 2^23
 // input pixels.
+//
+// MODE = 2: a nearest-x2 upsampling 3x3 convolution as four 2x2 "phase" convolutions in one launch (ca_conv_up2_phase).  An output
+// pixel (2y + py, 2x + px) reads the 2x2 source pixels (y + py - 1 + dy, x + px - 1 + dx), dy, dx in {0, 1}, with the weights of
+// phase 2 py + px (four taps: the nine taps that land on the same source pixel summed at pack time).  Row tiles are numbered
+// phase-major: a row tile belongs to ONE phase, its rows are source pixels (the last tile of a phase is partial), the gather is the
+// convolution's with four taps, and the epilogue's row address is the interleaved output pixel.  Same main loop, ring and epilogue.
 
 // Timing-only ablations (never in a shipped library: results are wrong): -DCA_PQ_ABLATE=bits, 1 = no global -> LDS units after
 // a block's first two, 2 = no fragment reads, 4 = no MFMAs, 8 = no barriers inside the K loop, 16 = every tile streams the operands of
@@ -31,6 +37,12 @@
 #else
 #define CA_PQ_ABL(bit) false
 #endif
+
+// r / d for r < 2^31 with mag = min(floor(2^32 / d), 2^32 - 1): the estimate is at most one short (MODE = 2 row -> pixel maps)
+__device__ __forceinline__ unsigned pq_udiv(unsigned r, unsigned d, unsigned mag) {
+  const unsigned q = __umulhi(r, mag);
+  return r - q * d >= d ? q + 1 : q;
+}
 
 // EPI = 0: bias, row bias, alpha, residual (GEMM and convolution).  EPI = 1 (dense only): LayerNorm fold with finished (mean,
 // rstd) per row, bias, alpha and optionally GEGLU; no residual, no row bias.  EPI = 2 (dense only): EPI = 0 + row sums of the
@@ -57,7 +69,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm_pq(GemmKParams p, int tiles_tot
   const int g = lane >> 4, l15 = lane & 15;
 
   const int tiles_n = p.n / BN;
-  const int tiles_m = (p.m + BM - 1) / BM;
+  const int tiles_m = MODE == 2 ? 4 * p.up2_tiles : (p.m + BM - 1) / BM;  // (MODE 2: p.m = 4 * up2_tiles * BM, phase-major row tiles)
   const int G = gridDim.x;
   const int bslot = (G % 8 == 0) ? (int)(blockIdx.x % 8) * (G / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
   const int my_tiles = bslot < tiles_total ? (tiles_total - bslot + G - 1) / G : 0;
@@ -125,7 +137,22 @@ __global__ __launch_bounds__(512, 2) void k_gemm_pq(GemmKParams p, int tiles_tot
     for (int i = 0; i < 4; ++i) {
       const int m = m0 + wid * 32 + i * 8 + r8;  // A pieces stage rows wid*32 + 8i + r8: chunk_i = chunk_0 ^ 4(i & 1)
       const bool ok = m < p.m;
-      if (MODE == 1) {
+      if (MODE == 2) {
+        // row = source pixel r of phase (py, px): tap (0, 0) reads source pixel r + (py - 1) W + (px - 1); same packed state as
+        // MODE 1 with bit 25 / 27 = the row / column of tap dy = 1 / dx = 1 inside the image
+        const int ph = m0 / (p.up2_tiles * BM);
+        const int py = ph >> 1, px = ph & 1;
+        const int r = m - ph * (p.up2_tiles * BM);
+        const bool okr = r < p.up2_rows;
+        const int rr = okr ? r : p.up2_rows - 1;
+        const unsigned q = pq_udiv((unsigned)rr, (unsigned)p.win, p.up2_mag_w);
+        const int xs = rr - (int)q * p.win;
+        const int ys = (int)q - (int)pq_udiv(q, (unsigned)p.hin, p.up2_mag_h) * p.hin;
+        const int hi0 = ys + py - 1, wi0 = xs + px - 1;
+        const int p0 = rr + (py - 1) * p.win + (px - 1);
+        a_v[i] = ((unsigned)p0 & 0xFFFFFFu) | (hi0 >= 0 ? 1u << 24 : 0u) | (hi0 + 1 < p.hin ? 1u << 25 : 0u) | (wi0 >= 0 ? 1u << 26 : 0u) | (wi0 + 1 < p.win ? 1u << 27 : 0u) |
+                 (okr ? 1u << 28 : 0u);
+      } else if (MODE == 1) {
         // pixel index of the row's tap (0, 0) -- may be negative at the top / left border -- in bits 0..23 (signed), and which
         // taps exist: bit 24 / 25 = input row of kh = 0 / 2 inside the image, bit 26 / 27 = input column of kw = 0 / 2, bit 28 =
         // the output row exists.  (The middle row / column always exists: pad 1, checked by the launcher.)  Per tap the source
@@ -146,6 +173,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm_pq(GemmKParams p, int tiles_tot
     // row-grouped weights (dense, EPI = 0 only: the Winograd convolutions' sixteen GEMMs in one launch): this row tile's weight matrix
     unsigned wgrp = 0u;
     if (MODE == 0 && EPI == 0 && p.w_group_rows > 0) wgrp = (unsigned)(m0 / p.w_group_rows) * p.w_group_stride;
+    if (MODE == 2) wgrp = (unsigned)(m0 / (p.up2_tiles * BM)) * p.w_group_stride;  // the phase's weight matrix [cout][2][2][cin]
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int r = wid * 16 + i * 8 + r8;  // B0 local row r: quarter r >> 5, MFMA tile (r >> 4) & 1, fragment row r & 15
@@ -200,12 +228,14 @@ __global__ __launch_bounds__(512, 2) void k_gemm_pq(GemmKParams p, int tiles_tot
     const bool src2 = d_c0 >= p.c1;                          // c1 % 64 == 0: a K tile never straddles the two sources
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)(buf + OFF_B0 + (wid * 2 + 0) * 8 * KT), 16, b0_v[0], wk, 0, 0);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)(buf + OFF_B0 + (wid * 2 + 1) * 8 * KT), 16, b0_v[1], wk, 0, 0);
-    if (MODE == 1) {
+    if (MODE != 0) {
       int lane_o = lane;
       asm volatile("" : "+v"(lane_o));
       const unsigned cs2 = (unsigned)(src2 ? p.c2 : p.c1) * 2u;
-      const int kh = d_tap >= 6 ? 2 : (d_tap >= 3 ? 1 : 0), kw = d_tap - kh * 3;
-      const unsigned need = (1u << 28) | (kh == 0 ? 1u << 24 : kh == 2 ? 1u << 25 : 0u) | (kw == 0 ? 1u << 26 : kw == 2 ? 1u << 27 : 0u);
+      // MODE 1: taps (kh, kw) of 3 x 3, the middle row / column always inside; MODE 2: taps (dy, dx) of 2 x 2, either may be outside
+      const int kh = MODE == 2 ? d_tap >> 1 : (d_tap >= 6 ? 2 : (d_tap >= 3 ? 1 : 0)), kw = MODE == 2 ? d_tap & 1 : d_tap - kh * 3;
+      const unsigned need = MODE == 2 ? (1u << 28) | (kh == 0 ? 1u << 24 : 1u << 25) | (kw == 0 ? 1u << 26 : 1u << 27)
+                                      : (1u << 28) | (kh == 0 ? 1u << 24 : kh == 2 ? 1u << 25 : 0u) | (kw == 0 ? 1u << 26 : kw == 2 ? 1u << 27 : 0u);
       const int delta = kh * p.win + kw;
       // byte offset inside a pixel: first channel of the K tile + the lane's (swizzled) 16-byte chunk; odd pieces flip chunk bit 2
       const unsigned cadd = (unsigned)(src2 ? d_c0 - p.c1 : d_c0) * 2u + (unsigned)(((lane_o & 7) ^ swz(lane_o >> 3)) * 16);
@@ -344,9 +374,16 @@ __global__ __launch_bounds__(512, 2) void k_gemm_pq(GemmKParams p, int tiles_tot
       bi[j] = *reinterpret_cast<const f32x4*>(pset + P_BI + c0 * 4);
       rb[j] = *reinterpret_cast<const f32x4*>(rbp + c0 * 4);
     }
+    const int up_ph = MODE == 2 ? m0 / (p.up2_tiles * BM) : 0;
     auto rowoff_of = [&](int i, int64_t ld) __attribute__((always_inline)) -> unsigned {
-      const int m = m0 + wr * 128 + i * 16 + l15;
-      return m < p.m ? (unsigned)m * (unsigned)ld * 2u + (unsigned)(n0 + wc * 80) * 2u : OOB_V;
+      int m = m0 + wr * 128 + i * 16 + l15;
+      if (MODE == 2) {
+        // source pixel r = (img, y, x) of phase (py, px) -> output pixel (img, 2y + py, 2x + px) = 4 r - 2 x + 2 py W + px
+        const int r = m - up_ph * (p.up2_tiles * BM);
+        const int xs = r - (int)pq_udiv((unsigned)r, (unsigned)p.win, p.up2_mag_w) * p.win;
+        m = r < p.up2_rows ? 4 * r - 2 * xs + (up_ph >> 1) * 2 * p.win + (up_ph & 1) : 0x7FFFFFFF;
+      }
+      return m < (MODE == 2 ? 4 * p.up2_rows : p.m) ? (unsigned)m * (unsigned)ld * 2u + (unsigned)(n0 + wc * 80) * 2u : OOB_V;
     };
     u32x4 r16[2][2];
     u32x2 r8[2];
@@ -521,7 +558,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm_pq(GemmKParams p, int tiles_tot
   // k half 0 (a unit then has three intervals to land instead of two; the gather's issue takes ~1300 cycles against ~500 of a
   // dense unit).  Measured in one process (tools/ps_check.py --time, us): convolutions 32x32 latents 640->640 258 vs 294,
   // 1280->640 468 vs 545, 1280->1280 945 vs 1102; dense 32768x640x2560 135 vs 117, 131072x320x1280 160 vs 146 -- so per MODE.
-  const bool g1_late = MODE == 1 && wr == 1;
+  const bool g1_late = MODE != 0 && wr == 1;
   CA_PQ_SET_TILE(0)
   issue_tile();  // K tile 0 -> buffer 0
   if (g1_late) advance_and_issue();

@@ -341,6 +341,45 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, *, x2: Optional[torch.Tensor] = No
     return y
 
 
+def _up2_args(x, w_phase, bias, residual, alpha, y=None) -> ConvArgs:
+    """ca_conv_args of the phase form; without an output yet (the `_supported` query: pointers are only checked for alignment) y = x."""
+    images, hin, win, cin = x.shape
+    cout = w_phase.shape[1]
+    return ConvArgs(x=_p(x), w=_p(w_phase), y=_p(y) if y is not None else _p(x), bias=_p(bias), residual=_p(residual),
+                    ld_res=cout if residual is not None else 0, images=images, hin=hin, win=win, cin1=cin, cin2=0, cout=cout, stride=1,
+                    upsample=1, rows_per_group=0, alpha=alpha, post_scale=1.0, act=ACT_NONE, out_f32=0, dtype=dt_code(x.dtype), pad_asym=0)
+
+
+def conv_up2_phase_supported(x: torch.Tensor, w_phase: torch.Tensor, *, bias: Optional[torch.Tensor] = None,
+                             residual: Optional[torch.Tensor] = None, alpha: float = 1.0) -> bool:
+    """Does the library take this nearest-x2 upsampling convolution as four phase convolutions by default (ca_conv_up2_phase_supported:
+    the kernel implements the arguments and the form pays at the size)?  No launch, no device access."""
+    if x.dim() != 4 or w_phase.dim() != 5 or not x.is_contiguous() or x.dtype not in (torch.float16, torch.bfloat16):
+        return False
+    return bool(lib().ca_conv_up2_phase_supported(C.byref(_up2_args(x, w_phase, bias, residual, alpha))))
+
+
+def conv_up2_phase(x: torch.Tensor, w_phase: torch.Tensor, *, bias: Optional[torch.Tensor] = None,
+                   residual: Optional[torch.Tensor] = None, alpha: float = 1.0) -> torch.Tensor:
+    """conv3x3(nearest_x2(x)) as four 2x2 phase convolutions in one launch (ca_conv_up2_phase): x [images, H, W, Cin],
+    w_phase [4, Cout, 2, 2, Cin] (layers.phase_weights of the 3x3 weight); returns [images, 2H, 2W, Cout].  Runs every shape the
+    kernel implements (Cin % 64 == 0, Cout % 320 == 0); whether the form PAYS at a size is conv_up2_phase_supported's answer."""
+    _req_cuda(x, w_phase, bias, residual)
+    assert x.dim() == 4 and x.is_contiguous() and w_phase.dim() == 5 and w_phase.is_contiguous() and w_phase.dtype == x.dtype
+    images, hin, win, cin = x.shape
+    cout = w_phase.shape[1]
+    assert tuple(w_phase.shape) == (4, cout, 2, 2, cin)
+    y = torch.empty((images, 2 * hin, 2 * win, cout), device=x.device, dtype=x.dtype)
+    if residual is not None:
+        assert residual.dtype == x.dtype and residual.is_contiguous() and residual.numel() == y.numel()
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.numel() == cout
+    args = _up2_args(x, w_phase, bias, residual, alpha, y)
+    _record_plan(lib().ca_conv_up2_phase_plan_name, args)
+    check(lib().ca_conv_up2_phase(C.byref(args), _stream()), "ca_conv_up2_phase")
+    return y
+
+
 _gn_wino_declined: dict = {}  # shapes group_norm_conv3x3_wino has declined (the library's answer depends on nothing else)
 
 

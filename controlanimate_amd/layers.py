@@ -192,6 +192,16 @@ class HipConv1x1(nn.Module):
         return K.gemm(a, self.w.t, bias=self.b.t, **kw)
 
 
+def phase_weights(w: torch.Tensor) -> torch.Tensor:
+    """w [Cout, Cin, 3, 3] (fp32) -> wp [4, Cout, 2, 2, Cin], phase p = 2 py + px: conv3x3(nearest_x2(x)) at output pixel
+    (2y + py, 2x + px) = sum over dy, dx in {0, 1} of wp[p, :, dy, dx] . x[y + py - 1 + dy, x + px - 1 + dx].  Per axis the three taps of
+    the upsampled image fall on two source pixels: parity 0 reads {s - 1, s} with {w0, w1 + w2}, parity 1 reads {s, s + 1} with
+    {w0 + w1, w2}; a source row / column outside the image is exactly the zero padding of the upsampled image (row -1, row 2H)."""
+    sel = torch.tensor([[[1.0, 0.0, 0.0], [0.0, 1.0, 1.0]], [[1.0, 1.0, 0.0], [0.0, 0.0, 1.0]]], dtype=w.dtype, device=w.device)  # [parity][d][k]
+    wp = torch.einsum("ydk,xel,oikl->yxodei", sel, sel, w)  # [py, px, Cout, dy, dx, Cin]
+    return wp.reshape(4, w.shape[0], 2, 2, w.shape[1]).contiguous()
+
+
 class HipConv3x3(nn.Module):
     """Conv2d 3x3 pad 1 parameters (weight [Cout,Cin,3,3]); NHWC implicit GEMM via ca_conv3x3."""
 
@@ -208,6 +218,9 @@ class HipConv3x3(nn.Module):
         # the de-duplicated ControlNet batch -- nearest-x2 upsampling included, asymmetric padding and stride 2 not); a model that never
         # reaches such a shape can set this False before prepare() and save 16/9 of the weight per convolution (VAE: never packed, < 640)
         self.winograd = True
+        # True (set by the owner before prepare(): Upsample3D): pack() also stores the four 2x2 phase weights of conv(nearest_x2(x)),
+        # and run(upsample=True) takes ca_conv_up2_phase where the library says it pays.  Every other convolution stays as it is.
+        self.up2_phase = False
 
     def _packed_weight(self) -> torch.Tensor:
         w = _f32(self.weight).permute(0, 2, 3, 1)  # [Cout, kh, kw, Cin]
@@ -230,8 +243,16 @@ class HipConv3x3(nn.Module):
         if (dispatch.conv_winograd and self.stride == 1 and self.winograd and self.in_channels >= 640 and self.in_channels % 64 == 0
                 and self.out_channels % 320 == 0):
             self.u = arena.add((16, self.out_channels, self.in_channels), dtype, self._winograd_weight)
+        self.wp = None
+        if dispatch.conv_up2_phase and self.up2_phase and self.stride == 1 and self.in_channels % 64 == 0 and self.out_channels % 320 == 0:
+            self.wp = arena.add((4, self.out_channels, 2, 2, self.in_channels), dtype, lambda: phase_weights(_f32(self.weight)))
 
     def run(self, x: torch.Tensor, **kw) -> torch.Tensor:
+        wp = getattr(self, "wp", None)
+        if wp is not None and dispatch.conv_up2_phase and kw.get("upsample") and set(kw) <= {"upsample", "residual", "alpha"}:
+            ph = {k: v for k, v in kw.items() if k != "upsample"}
+            if K.conv_up2_phase_supported(x, wp.t, bias=self.b.t, **ph):
+                return K.conv_up2_phase(x, wp.t, bias=self.b.t, **ph)
         u = getattr(self, "u", None)
         return K.conv3x3(x, self.w.t, bias=self.b.t, stride=self.stride, w_wino=None if u is None else u.t, **kw)
 

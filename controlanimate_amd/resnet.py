@@ -34,6 +34,7 @@ class Upsample3D(nn.Module):
         super().__init__()
         self.channels, self.out_channels = channels, out_channels or channels
         self.conv = InflatedConv3d(channels, self.out_channels)
+        self.conv.up2_phase = True  # pack the four 2x2 phase weights too (layers.phase_weights): run(upsample=True) takes them where they pay
 
     def pack(self, arena, dtype):
         self.conv.pack(arena, dtype)

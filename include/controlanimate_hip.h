@@ -338,6 +338,18 @@ int64_t ca_conv3x3_workspace_bytes(const ca_conv_args* args);
 int ca_conv3x3(const ca_conv_args* args, void* stream);
 /* ABI v7: as ca_gemm_plan_name, for ca_conv3x3 */
 int ca_conv3x3_plan_name(const ca_conv_args* args, char* buf, int32_t len);
+/* Added to ABI v16 (three new functions; no struct or existing function changes, so the version number stays): the upsampling convolution (upsample = 1, stride 1, padding 1) as four 2x2 "phase" convolutions in ONE launch of the
+ * 256 x 320 kernel.  An output pixel (2y + py, 2x + px) reads only the 2x2 source pixels (y + py - 1 + dy, x + px - 1 + dx), so the nine
+ * taps that land on the same source pixel are summed ahead of time: args->w is w_phase [4][cout][2][2][cin], phase = 2 py + px, with
+ *   rows  py = 0: {w[0], w[1] + w[2]}   py = 1: {w[0] + w[1], w[2]}     (columns alike; summed in fp32, rounded once)
+ * and an out-of-image source row / column is exactly the zero padding of the upsampled image.  4/9 of the multiply-adds of
+ * ca_conv3x3(upsample = 1); same output dtype, bias, residual and alpha; deterministic.  Takes one source (x2 NULL) with cin % 64 == 0,
+ * cout % 320 == 0, no row bias / activation / post_scale / fp32 output, 16-byte aligned operands; w_wino and workspace are ignored.
+ * ca_conv_up2_phase_supported: 1 where the kernel takes the arguments AND the form pays (whole rounds of 256 output tiles over the four
+ * phases, or >= 1024 tiles); ca_conv_up2_phase itself runs every shape the kernel implements and fails on the others. */
+int ca_conv_up2_phase_supported(const ca_conv_args* args);
+int ca_conv_up2_phase(const ca_conv_args* args, void* stream);
+int ca_conv_up2_phase_plan_name(const ca_conv_args* args, char* buf, int32_t len);
 
 /* ------------------------------------------------------------------------------------
  * GroupNorm (+ optional SiLU), NHWC, two launches: statistics then apply.
