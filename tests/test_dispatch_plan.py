@@ -8,6 +8,7 @@ and the network-level parity test at the headline size (tests/test_fullsize_gpu.
 is what then has to be re-run on the GPU.
 """
 import ctypes as C
+import os
 
 import pytest
 
@@ -49,11 +50,19 @@ def gemm_label(capi, m, n, k, *, geglu=0, res=False, ln=None, row_sums=False, wo
     return buf.value.decode()
 
 
-def conv_label(capi, images, h, cin, cout, *, cin2=0, stride=1, upsample=0, workspace=True):
-    a = capi.ConvArgs(x=FAKE, w=FAKE, y=FAKE, images=images, hin=h, win=h, cin1=cin - cin2, cin2=cin2, cout=cout, stride=stride,
-                      upsample=upsample, alpha=1.0, post_scale=1.0, dtype=capi.CA_F16, rows_per_group=1)
+def conv_label(capi, images, h, cin, cout, *, cin2=0, stride=1, upsample=0, workspace=True, w=None, wino=False, pad_asym=0, epilogue=0,
+               dtype=None):
+    """h x h images, or h x w where `w` is given; wino: the Winograd weights are offered; epilogue: bias, residual and a row bias
+    with groups of that many rows."""
+    a = capi.ConvArgs(x=FAKE, w=FAKE, y=FAKE, images=images, hin=h, win=h if w is None else w, cin1=cin - cin2, cin2=cin2, cout=cout,
+                      stride=stride, upsample=upsample, alpha=1.0, post_scale=1.0, dtype=capi.CA_F16 if dtype is None else dtype,
+                      rows_per_group=1, pad_asym=pad_asym)
     if cin2:
         a.x2 = FAKE
+    if wino:
+        a.w_wino = FAKE
+    if epilogue:
+        a.bias, a.residual, a.ld_res, a.rowbias, a.rows_per_group, a.ld_rowbias = FAKE, FAKE, cout, FAKE, epilogue, cout
     if workspace:
         a.workspace, a.workspace_bytes = FAKE, 1 << 40
     buf = C.create_string_buffer(64)
@@ -122,6 +131,60 @@ CONVS = [
     ((32, 32, 640, 640, dict(upsample=1)), "128x128"),                # (the 256 x 320 kernel's gather has no upsampling)
 ]
 
+# (images, H, W, Cin, Cout, keyword flags) -> label: the 3x3 convolutions of one UNet3D step of BASELINE config 4 (512x768: 32 images of
+# 64x96, 32x48, 16x24, 8x12) and config 5 (768x768, 32 frames: 64 images of 96x96 .. 12x12), enumerated from the model's HipConv3x3
+# modules (test_rect_conv_table_is_the_models_convolutions).  wino=True where the module packs the Winograd weights
+# (layers.HipConv3x3.pack) and so offers them.  A pin: the labels are what ca_conv3x3_plan_name answers today.
+RECT_CONVS = [
+    ((32, 64, 96, 8, 320, dict()), "reg_128x64"),                                  # conv_in
+    ((32, 64, 96, 320, 320, dict()), "128x160"),
+    ((32, 64, 96, 320, 320, dict(stride=2)), "128x160"),
+    ((32, 32, 48, 320, 640, dict()), "pq256x320"),
+    ((32, 32, 48, 640, 640, dict(wino=True)), "pq256x320"),
+    ((32, 32, 48, 640, 640, dict(stride=2)), "pp128x320"),
+    ((32, 16, 24, 640, 1280, dict(wino=True)), "wino_pq256x320"),
+    ((32, 16, 24, 1280, 1280, dict(wino=True)), "wino_pq256x320"),
+    ((32, 16, 24, 1280, 1280, dict(stride=2)), "128x128_splitk4"),
+    ((32, 8, 12, 1280, 1280, dict(wino=True)), "wino_pq256x320"),
+    ((32, 8, 12, 2560, 1280, dict(wino=True)), "wino_pq256x320"),
+    ((32, 8, 12, 1280, 1280, dict(upsample=1, wino=True)), "wino_pq256x320"),
+    ((32, 16, 24, 2560, 1280, dict(wino=True)), "wino_pq256x320"),
+    ((32, 16, 24, 1920, 1280, dict(wino=True)), "wino_pq256x320"),
+    ((32, 16, 24, 1280, 1280, dict(upsample=1, wino=True)), "wino_pq256x320"),
+    ((32, 32, 48, 1920, 640, dict(wino=True)), "wino_pq256x320"),
+    ((32, 32, 48, 1280, 640, dict(wino=True)), "wino_pq256x320"),
+    ((32, 32, 48, 960, 640, dict(wino=True)), "pq256x320"),
+    ((32, 32, 48, 640, 640, dict(upsample=1, wino=True)), "128x128"),
+    ((32, 64, 96, 960, 320, dict(wino=True)), "pq256x320"),
+    ((32, 64, 96, 640, 320, dict(wino=True)), "pq256x320"),
+    ((32, 64, 96, 320, 4, dict()), "128x64"),                                      # conv_out
+    ((64, 96, 96, 8, 320, dict()), "reg_128x64"),
+    ((64, 96, 96, 320, 320, dict()), "128x160"),
+    ((64, 96, 96, 320, 320, dict(stride=2)), "128x160"),
+    ((64, 48, 48, 320, 640, dict()), "pq256x320"),
+    ((64, 48, 48, 640, 640, dict(wino=True)), "pq256x320"),
+    ((64, 48, 48, 640, 640, dict(stride=2)), "pq256x320"),
+    ((64, 24, 24, 640, 1280, dict(wino=True)), "pq256x320"),
+    ((64, 24, 24, 1280, 1280, dict(wino=True)), "wino_pq256x320"),
+    ((64, 24, 24, 1280, 1280, dict(stride=2)), "128x128"),
+    ((64, 12, 12, 1280, 1280, dict(wino=True)), "wino_pq256x320"),
+    ((64, 12, 12, 2560, 1280, dict(wino=True)), "wino_pq256x320"),
+    ((64, 12, 12, 1280, 1280, dict(upsample=1, wino=True)), "wino_pq256x320"),
+    ((64, 24, 24, 2560, 1280, dict(wino=True)), "wino_pq256x320"),
+    ((64, 24, 24, 1920, 1280, dict(wino=True)), "wino_pq256x320"),
+    ((64, 24, 24, 1280, 1280, dict(upsample=1, wino=True)), "128x128"),
+    ((64, 48, 48, 1920, 640, dict(wino=True)), "pq256x320"),
+    ((64, 48, 48, 1280, 640, dict(wino=True)), "pq256x320"),
+    ((64, 48, 48, 960, 640, dict(wino=True)), "pq256x320"),
+    ((64, 48, 48, 640, 640, dict(upsample=1, wino=True)), "128x128"),
+    ((64, 96, 96, 960, 320, dict(wino=True)), "pq256x320"),
+    ((64, 96, 96, 640, 320, dict(wino=True)), "pq256x320"),
+    ((64, 96, 96, 320, 4, dict()), "128x64"),
+]
+# the upsampling convolutions above that ca_conv_up2_phase_supported takes first (layers.HipConv3x3.run): they run as "up2_pq256x320"
+RECT_UP2 = {(32, 8, 12, 1280, 1280): 0, (32, 16, 24, 1280, 1280): 1, (32, 32, 48, 640, 640): 1,
+            (64, 12, 12, 1280, 1280): 0, (64, 24, 24, 1280, 1280): 1, (64, 48, 48, 640, 640): 1}
+
 
 # every name plan_label (csrc/ca_gemm.hip) can produce: the kernels a launch can reach.  (_splitkS: S = 2 .. 8 K ranges.)
 PLAN_LABELS = ({"wres160", "ar128x64", "pp128x320", "ps128x320", "pq256x320", "wino_pq256x320", "128x160", "128x128", "128x64", "128x64_r3",
@@ -160,6 +223,78 @@ def test_gemm_dispatch(capi, shape, label):
 def test_conv_dispatch(capi, shape, label):
     i, h, ci, co, kw = shape
     assert conv_label(capi, i, h, ci, co, **kw) == label
+
+
+def _rect_id(shape):
+    i, h, w, ci, co, kw = shape
+    return f"conv{i}x{h}x{w}_{ci}to{co}{'_' + '_'.join(sorted(kw)) if kw else ''}"
+
+
+@pytest.mark.parametrize("shape,label", RECT_CONVS, ids=[_rect_id(s) for s, _ in RECT_CONVS])
+def test_rect_conv_dispatch(capi, shape, label):
+    i, h, w, ci, co, kw = shape
+    assert conv_label(capi, i, h, ci, co, w=w, **kw) == label
+
+
+def test_rect_conv_table_is_the_models_convolutions(capi):
+    """The table's shapes are the HipConv3x3 modules of the full-width UNet3D (built on the meta device: no weights) at the four
+    latent levels of configs 4 and 5 -- none missing, none invented -- and the phase form takes the upsampling convolutions listed."""
+    import sys
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import conv_ref
+    from controlanimate_amd.configs import unet_config
+    from controlanimate_amd.layers import HipConv3x3
+    from controlanimate_amd.unet import UNet3DConditionModel
+    with torch.device("meta"):
+        unet = UNet3DConditionModel.from_config(unet_config("v2"))
+    want = set()
+    for images, (hh, ww) in ((32, (64, 96)), (64, (96, 96))):
+        for name, m in unet.named_modules():
+            if not isinstance(m, HipConv3x3):
+                continue
+            part = name.split(".")
+            level = {"down_blocks": lambda: int(part[1]), "up_blocks": lambda: 3 - int(part[1]), "mid_block": lambda: 3}.get(part[0], lambda: 0)()
+            kw = {}
+            if m.stride == 2:
+                kw["stride"] = 2
+            if part[0] == "up_blocks" and part[2] == "upsamplers":
+                kw["upsample"] = 1
+            if m.stride == 1 and m.in_channels >= 640 and m.in_channels % 64 == 0 and m.out_channels % 320 == 0:   # HipConv3x3.pack
+                kw["wino"] = True
+            want.add((images, hh >> level, ww >> level, m.cin_pad, m.out_channels, tuple(sorted(kw.items()))))
+    have = [(i, h, w, ci, co, tuple(sorted(kw.items()))) for (i, h, w, ci, co, kw), _ in RECT_CONVS]
+    assert len(have) == len(set(have)) and set(have) == want, (sorted(want - set(have)), sorted(set(have) - want))
+    ups = {s[:5] for s, _ in RECT_CONVS if s[5].get("upsample")}
+    assert ups == set(RECT_UP2)
+    for (i, h, w, ci, co), taken in RECT_UP2.items():
+        a = capi.ConvArgs(x=FAKE, w=FAKE, y=FAKE, bias=FAKE, images=i, hin=h, win=w, cin1=ci, cout=co, stride=1, upsample=1, alpha=1.0,
+                          post_scale=1.0, dtype=capi.CA_F16)
+        assert capi.lib().ca_conv_up2_phase_supported(C.byref(a)) == taken, (i, h, w, ci, co)
+    # every kernel these workloads reach has a rectangular parity case on the GPU (tests/test_rect_latents_gpu.py)
+    reached = {label for _, label in RECT_CONVS} | {"up2_pq256x320"}
+    assert reached <= conv_ref.LABELS, sorted(reached - conv_ref.LABELS)
+
+
+def test_rect_parity_cases_are_on_the_kernels_they_name(capi):
+    """The cases of tests/test_rect_latents_gpu.py carry the label the plan gives them today, in both dtypes (the GPU test asserts the
+    label of the launch itself; this says so without a GPU)."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import conv_ref
+    for c in conv_ref.DIRECT_CASES + conv_ref.WINO_CASES:
+        for dt in (capi.CA_F16, capi.CA_BF16):
+            got = conv_label(capi, c.images, c.h, c.c1 + c.c2, c.cout, w=c.w, cin2=c.c2, stride=c.stride, upsample=int(c.upsample),
+                             pad_asym=int(c.pad_asym), wino=c.wino, epilogue=c.rows_per_group(), dtype=dt)
+            assert got == c.label, (c.id, dt, got)
+    taken = []
+    for c in conv_ref.UP2_CASES:
+        a = capi.ConvArgs(x=FAKE, w=FAKE, y=FAKE, images=c.images, hin=c.h, win=c.w, cin1=c.c1, cout=c.cout, stride=1, upsample=1, alpha=1.0,
+                          post_scale=1.0, dtype=capi.CA_F16)
+        buf = C.create_string_buffer(64)
+        assert capi.lib().ca_conv_up2_phase_plan_name(C.byref(a), buf, 64) == 0 and buf.value.decode() == c.label
+        taken.append(capi.lib().ca_conv_up2_phase_supported(C.byref(a)))
+    assert taken == [1, 0]   # (the first is a shape the form pays at; the second runs through the direct entry)
 
 
 def test_partial_layernorm_sums_never_reach_a_kernel_that_reads_mean_rstd(capi):

@@ -244,6 +244,22 @@ GN_CASES = [
     (8, 32, 32, 320, 320, 1, 1, 1e-5),
     (16, 16, 16, 1280, 1280, 1, 0, 1e-5),
     (3, 24, 24, 1280, 0, 1, 1, 1e-5),
+    # the row counts of the 512x768 / 768x768 workloads (96, 144, 384, 576, 1536, 2304, 6144 rows per image) against the instantiation
+    # boundaries; the kernel each case should reach (ca_groupnorm has no plan query)
+    (2, 8, 12, 1280, 0, 1, 1, 1e-5),       # k_gn_small<2>: 480 chunks
+    (2, 8, 12, 1280, 1280, 1, 1, 1e-5),    # k_gn_small<5>: 960 chunks
+    (2, 12, 12, 1280, 1280, 1, 1, 1e-5),   # k_gn_small<12>: 1440 chunks
+    (2, 24, 24, 1280, 0, 1, 1, 1e-5),      # k_gn_small<12>: 2880 of 3072 chunks, the last slot partly filled
+    (2, 16, 24, 1280, 1280, 1, 1, 1e-5),   # 3840 chunks: statistics + apply
+    (2, 16, 24, 640, 0, 1, 1, 1e-5),       # k_gn_unit<5>
+    (2, 16, 64, 320, 0, 1, 1, 1e-5),       # k_gn_unit<5>: 5120 chunks per unit, the last size it takes
+    (2, 18, 57, 320, 0, 1, 1, 1e-5),       # k_gn_unit<20>: 5130 chunks per unit, the first size it takes
+    (2, 32, 48, 640, 0, 1, 1, 1e-5),       # k_gn_unit<20>
+    (3, 48, 48, 320, 0, 1, 1, 1e-5),       # k_gn_unit<20>
+    (2, 16, 24, 1280, 640, 1, 1, 1e-5),    # units of 120 channels do not divide c1: statistics + apply
+    (2, 32, 48, 640, 320, 1, 1, 1e-5),     # likewise
+    (2, 64, 96, 320, 0, 1, 1, 1e-5),       # 30720 chunks per unit: statistics + apply with 24 chunks of rows
+    (16, 8, 12, 320, 0, 16, 1, 1e-5),      # statistics spanning 16 frames
 ]
 
 

@@ -13,16 +13,18 @@ dev = "cuda"
 G = torch.tensor([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]])
 
 
-def make(images, h, c1, c2, cout, dt=torch.float16, seed=3, epilogue=True):
+def make(images, h, c1, c2, cout, dt=torch.float16, seed=3, epilogue=True, w=None):
+    """Operands of one case on h x h images; h x w images where `w` is given."""
+    wd = h if w is None else w
     g = torch.Generator(device="cpu").manual_seed(seed)
     rn = lambda *s, scale=1.0: (torch.randn(*s, generator=g) * scale).to(dev)
-    x = rn(images, h, h, c1).to(dt)
-    x2 = rn(images, h, h, c2).to(dt) if c2 else None
+    x = rn(images, h, wd, c1).to(dt)
+    x2 = rn(images, h, wd, c2).to(dt) if c2 else None
     w = rn(cout, c1 + c2, 3, 3, scale=(9 * (c1 + c2)) ** -0.5)          # fp32 [Cout, Cin, kh, kw]
     d = dict(x=x, x2=x2, w32=w, w=w.permute(0, 2, 3, 1).contiguous().to(dt), u=torch.einsum("xk,oikl,yl->xyoi", G.to(dev), w, G.to(dev)).reshape(16, cout, c1 + c2).contiguous().to(dt),
              bias=None, rowbias=None, residual=None, rows_per_group=0, post=1.0)
     if epilogue:
-        d.update(bias=rn(cout, scale=0.1), rowbias=rn(2, cout, scale=0.3), residual=rn(images, h, h, cout).to(dt), rows_per_group=images // 2 * h * h, post=1.0 / 1.3)
+        d.update(bias=rn(cout, scale=0.1), rowbias=rn(2, cout, scale=0.3), residual=rn(images, h, wd, cout).to(dt), rows_per_group=images // 2 * h * wd, post=1.0 / 1.3)
     return d
 
 
