@@ -16,7 +16,7 @@
 // V and M live in the caller's workspace (ca_conv3x3_workspace_bytes).  The input transform adds and subtracts pairs of activations:
 // packed fp16 arithmetic (two roundings per V element) or, for bf16, fp32 arithmetic rounded per operation.
 // Taken where it pays: stride 1, pad 1 (optionally behind a nearest x2 upsampling), even H and W, Cin >= 1280, Cout % 320 == 0, T % 256 == 0,
-// at most 16384 tiles (wino_workspace_bytes in ca_gemm.hip).
+// at most 16384 tiles (wino_workspace_bytes in ca_gemm_plan.h).
 
 // dst[f][co][ci] = sum_{kh, kw} G[xi][kh] G[nu][kw] w[co][kh][kw][ci],  f = 4 xi + nu,  G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]
 template <int DT>

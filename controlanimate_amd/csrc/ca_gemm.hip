@@ -20,7 +20,7 @@
 // MFMA is issued with swapped operands (mfma(Wfrag, Afrag)) so each lane ends up holding 4
 // consecutive output columns of one output row -> 8-byte epilogue stores.
 
-#include "ca_gemm_core.h"
+#include "ca_gemm_plan.h"  // the launch planner (host only): which kernel, how many K ranges, how much workspace
 
 namespace {
 using namespace ca_gemm_detail;
@@ -435,243 +435,9 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(GemmKParams p) {
   }
 }
 
-// Split-K plan for a launch: 1 = none.  Only grids that leave the chip under-filled (8x8 / 16x16 latent
-// levels) and have a long K loop are split; the tile shape used with a split is 128x128 (N % 128 == 0).
-inline int splitk_plan(int m, int n, int nt, int geglu) {
-  static const int env = CA_KNOB("CA_SPLITK", -1);
-  if (env == 0 || geglu || n % 128 != 0) return 1;
-  const int64_t blocks = (int64_t)ceil_div_i(m, 128) * (n / 128);
-  if (blocks >= 384 || nt < 48) return 1;
-  int s = env > 0 ? env : (int)((960 + blocks - 1) / blocks);  // measured best on 160 tiles: 6 (89 vs 181 us unsplit)
-  if (s > 8) s = 8;
-  while (s > 1 && nt / s < 12) --s;
-  return s;
-}
-
-// Weight-resident streaming kernel (ca_gemm_wres.h) for the K = 320 GEMMs of the 64x64-latent level: does this dense
-// launch take it?  M >= 16384 (measured: a tie at 32768 rows, ahead above).  (Also the condition under which ca_gemm can
-// compute folded-LayerNorm statistics itself: ca_gemm_ln_inline_supported.)  The kernel reads ln_stats as (mean, rstd)
-// per row: a launch that hands over partial sums (ln_parts) is not eligible.
-inline bool wres_eligible(const GemmKParams& p) {
-  static const int wres_env = CA_KNOB("CA_GEMM_WRES", -1);  // (experiment builds: 0 = never, 1 = whenever the shape qualifies)
-  const int kc = p.c1 + p.c2;
-  return wres_env != 0 && kc == 320 && p.taps == 1 && (p.c2 == 0 || p.c1 % 32 == 0) && p.n % 160 == 0 && p.n / 160 <= 32 && !p.out_f32 &&
-         p.splits <= 1 && !p.ln_parts && p.a_bytes != 0 && p.w_bytes != 0 && (p.c2 == 0 || p.a2_bytes != 0) &&
-         (!p.rowbias || p.rows_per_group % 32 == 0) &&
-         act_out_fit31(p) &&  // (w_bytes needs no bound here: K = 320 and N <= 32 x 160 make the weights 3.3 MB at most)
-         (wres_env == 1 || p.m >= 16384);
-}
-
-// Activation-resident kernel (ca_gemm_ar.h, round 4): the same K = 320 launches when the caller also hands over W in fragment
-// order (ca_gemm_args.w_frag).  A subset of what the weight-resident kernel takes: one A source, N a multiple of 64 (64-column
-// panels dealt to four waves), alpha = post = 1, no activation, residual only without LayerNorm / GEGLU, row-bias groups of whole
-// 128-row tiles; in-kernel LayerNorm statistics need the caller's scratch (p.partial: 8 M bytes).
-// CA_GEMM_AR (experiment builds): 0 = never, 1 = every launch it can take (also N = 320), default: N >= 960.
-inline bool ar_eligible(const GemmKParams& p) {
-  static const int ar_env = CA_KNOB("CA_GEMM_AR", -1);
-  if (ar_env == 0 || !p.wf || !wres_eligible(p)) return false;
-  return p.c2 == 0 && p.n % 64 == 0 && p.alpha == 1.f && p.post == 1.f && p.act == CA_ACT_NONE && !p.row_sums && ((uintptr_t)p.wf & 15) == 0 &&
-         ((uintptr_t)p.c & 15) == 0 && p.ldc % 8 == 0 && (!p.res || (((uintptr_t)p.res & 15) == 0 && p.ld_res % 8 == 0 && !p.geglu && !p.ln_colsum)) &&
-         (!p.rowbias || (p.rows_per_group % 128 == 0 && !p.geglu)) && (!p.ln_inline || p.partial) &&
-         (ar_env == 1 || p.n >= 960);
-}
-
-// Dense GEMMs of the 8x8-latent level (M = 2048: 160 tiles of 128x128 for 256 CUs, each walking its 20..80 K tiles
-// alone at one DMA round trip per tile): the same slab schedule as the small convolutions.
-inline int splitk_plan_dense(int m, int n, int nt, int geglu, int out_f32) {
-  static const int env = CA_KNOB("CA_SPLITK_DENSE", -1);
-  if (env == 0 || geglu || out_f32 || n % 128 != 0) return 1;
-  const int64_t blocks = (int64_t)ceil_div_i(m, 128) * (n / 128);
-  // (measured: 2048x1280x5120, 80 K tiles: 55 vs 61 us; 2048x1280x1280, 20 K tiles: 34 vs 19 us -- the fp32 slabs and the
-  //  second launch cost more than a short K loop saves, hence the same threshold as the convolutions)
-  if (blocks > 192 || nt < 48) return 1;
-  int s = env > 0 ? env : (int)((960 + blocks - 1) / blocks);
-  if (s > 8) s = 8;
-  while (s > 1 && nt / s < 12) --s;
-  return s;
-}
-
-// ---- the launch plan: WHICH kernel instantiation a set of arguments runs, as a pure function of the arguments (the
-// product build has no environment knobs: CA_KNOB compiles to its default; experiment builds, -DCA_EXPERIMENTS, read
-// them for same-box A/B runs).  ca_gemm_plan_name / ca_conv3x3_plan_name report it without a launch;
-// tests/test_dispatch_plan.py pins every shape of the benchmark workload to its label.  (PlanKind: ca_gemm_core.h)
-struct GemmPlan {
-  PlanKind kind;
-  int bm, bn, nbuf;   // block tile; LDS stages of k_gemm_dma
-  int splits;       // K ranges (PK_*_SPLITK)
-  unsigned tiles;   // output tiles (x splits = blocks) of the ping-pong kernels
-};
-
-inline bool dma_capable(const GemmKParams& p) {
-  const int kc = p.c1 + p.c2;
-  return kc % BK == 0 && (p.c2 == 0 || p.c1 % BK == 0) && p.a_bytes != 0 && p.w_bytes != 0 && (p.c2 == 0 || p.a2_bytes != 0);
-}
-
-// Persistent streaming kernel (ca_gemm_ps.h): can this launch run on it?
-inline bool ps_capable(const GemmKParams& p) {
-  const int nt = p.taps * p.kc_tiles;
-  const bool fits32 = act_out_fit31(p) && p.w_bytes < FIT31;  // (the weights of a convolution or a wide projection can be large: bounded too)
-  const bool aligned = ((uintptr_t)p.c & 15) == 0 && (!p.res || ((uintptr_t)p.res & 15) == 0) && p.ldc % 8 == 0 && (!p.res || p.ld_res % 8 == 0);
-  return dma_capable(p) && p.n % 320 == 0 && nt >= 2 && p.splits <= 1 && !p.out_f32 && !p.ln_inline && (p.ln_parts <= 2 || p.ln_parts == 4) && fits32 && aligned &&
-         (!p.rowbias || p.rows_per_group % 64 == 0) && !(p.geglu && (p.res || p.row_sums)) && p.post == 1.f && p.act == CA_ACT_NONE;
-}
-
-// 256 x 320 streaming kernel (ca_gemm_pq.h): bias, row bias, alpha and residual only
-inline bool pq_capable(const GemmKParams& p, int mode) {
-  // (packed row state of the convolution gather: tap-0 pixel index in 24 signed bits, middle tap always inside the image)
-  const bool conv_ok = mode != 1 || (p.pad_lo == 1 && p.ups == 0 && p.hin >= 2 && p.win >= 2 && (int64_t)(p.m / (p.hout * p.wout) + 1) * p.hin * p.win < (1 << 23) &&
-                                     (p.hout - 1) * p.stride < p.hin && (p.wout - 1) * p.stride < p.win);
-  const bool epi1 = p.geglu || p.ln_colsum || p.ln_stats;  // the LayerNorm / GEGLU epilogue variant: dense, no residual
-  return ps_capable(p) && (!p.row_sums || (mode == 0 && !epi1)) && (mode == 1 || p.c2 == 0) && (!p.rowbias || p.rows_per_group % 128 == 0) && conv_ok &&
-         (!epi1 || (mode == 0 && !p.res && !p.rowbias && p.ln_parts == 0 && (!p.ln_colsum || p.ln_stats)));
-}
-
-inline GemmPlan plan_gemm(const GemmKParams& p, int mode) {
-  GemmPlan g{};
-  g.splits = 1;
-  const bool dma = dma_capable(p);
-  const int nt = p.taps * p.kc_tiles;
-  if (dma && p.splits > 1) {
-    // dense only: 128x320 ping-pong tiles -- the pipelined K loop needs fewer blocks to cover the DMA latency, so fewer
-    // (larger) K ranges and slabs: 2048x1280x5120 in 4 ranges x 64 tiles 45 vs 52 us.  (The 8x8-latent convolution
-    // 2048x1280x11520 measured 88 vs 82 us this way and stays on the 128x128 schedule.)
-    static const int pp_split_env = CA_KNOB("CA_SPLITK_PP", 1);
-    if (pp_split_env && mode == 0 && p.n % 320 == 0) {
-      const int tiles320 = ceil_div_i(p.m, 128) * (p.n / 320);
-      int s_eff = 256 / tiles320;
-      if (s_eff > p.splits) s_eff = p.splits;
-      if (s_eff >= 2 && tiles320 * s_eff >= 128 && nt / s_eff >= 12) {
-        g.kind = PK_PP2_SPLITK;
-        g.bm = 128, g.bn = 320, g.splits = s_eff, g.tiles = (unsigned)tiles320;
-        return g;
-      }
-    }
-    g.kind = PK_DMA_SPLITK;
-    g.bm = 128, g.bn = 128, g.nbuf = 1, g.splits = p.splits;
-    g.tiles = (unsigned)(ceil_div_i(p.m, 128) * (p.n / 128));
-    return g;
-  }
-  // Ping-pong kernels (8 waves, one block per CU, two wave groups alternating between an MFMA segment and a
-  // fragment-read / DMA-issue segment, counted vmcnt).  Measured: the 128x320 tile divides every
-  // channel count of the SD1.5 UNet exactly and wins where the 128x128 grid under-fills the chip (<= 2 rounds of tiles:
-  // the 16x16- and 32x32-latent levels, +10..19%); with many rounds the exposed epilogue of a one-block-per-CU kernel
-  // (35..45% of a K = 1280 GEMM) loses against 4 co-resident blocks of k_gemm_dma.
-  static const int pp_env = CA_KNOB("CA_GEMM_PP", -1);  // (experiment builds: 0 = never, 2 = whenever N % 320 == 0)
-  // Persistent streaming kernel (ca_gemm_ps.h): same main loop as the 128 x 320 ping-pong kernel, but no launch / prologue
-  // bubble per tile and an epilogue whose stores nothing waits for.  Measured against the kernel each shape had before
-  // (tools/ps_check.py --time, same box): 131072x320x1280 149 vs 180 us, 32768x640x640 50 vs 58, 8192x1280x1280 41.6 vs 43.3,
-  // 8192x10240x1280 GEGLU 261 vs 270, 2048x10240x1280 GEGLU 67.6 vs 71.0, 32768x5120x640 GEGLU 321 vs 327; behind on long K
-  // loops (its flag pieces cost ~5% of the main loop: 32768x640x2560 134 vs 122, 8192x1280x5120 114 vs 109), on wide plain
-  // outputs where four co-resident 128x128 blocks already hide their epilogues (32768x1920x640 116 vs 107) and on every
-  // convolution (-10..-25%).  Hence: dense, 2..20 K tiles, at least one tile per CU, GEGLU or at most four column tiles.
-  // CA_GEMM_PS (experiment builds): 0 = never, 1 = every launch it can take, 2 = the same except the weight-resident kernel's.
-  // 256 x 320 streaming kernel (ca_gemm_pq.h): 128 x 80 wave tiles take a quarter of the 128 x 320 kernels' LDS-port and
-  // global -> LDS traffic per FLOP; it needs one tile per CU and a long K loop, and has no LayerNorm / GEGLU / row-sum epilogue.
-  // Measured against the kernel each shape had before (tools/ps_check.py --time, one process, us): dense 32768x640x2560 106 vs
-  // 124, 131072x320x1280 136 vs 157, 32768x640x640 42 vs 52, 32768x1920x640 (folded LayerNorm) 90 vs 102, GEGLU projections
-  // 32768x5120x640 260 vs 331, 8192x10240x1280 210 vs 291 (1.02 PFLOP/s), 2048x10240x1280 58 vs 77; convolutions at 32x32
-  // latents 640->640 228 vs 290, 1280->640 433 vs 556; behind where the 256-row tiles leave CUs idle (M = 8192 x N = 1280: 128
-  // tiles, 154 vs 109; 8192x3840x1280: 384 tiles = 1.5 rounds, 107 vs 95) and on the 64x64-latent convolutions (320->320 296 vs
-  // 265).  Step, one box, knobs build: off 66.04 / 65.82, convolutions only 65.84 / 65.62, + GEGLU 64.95 / 64.79, + plain dense
-  // 64.37 / 64.34, + folded-LayerNorm projections 63.75 / 63.94.
-  // CA_GEMM_PQ (experiment builds): 0 = never, 1 = every launch it can take
-  static const int pq_env = CA_KNOB("CA_GEMM_PQ", -1);
-  if (pq_env != 0 && pq_capable(p, mode)) {
-    const int64_t tiles = (int64_t)ceil_div_i(p.m, 256) * (p.n / 320);
-    // (whole rounds of 256 tiles, or many: 8192x3840x1280 = 384 tiles measured 107 vs 95 us on the 128x128 kernel)
-    // (convolutions, clean build: 64x64 latents 640->320 468 vs 508, 640->640 908 vs 986, 32x32 1280->1280 820 vs 929; 320->320 at 64x64 -- N = 320, 45 K tiles -- 256 vs 251: not)
-    const bool dflt = mode == 1 ? (tiles >= 256 && (p.n >= 640 || nt >= 64)) : (tiles >= 256 && (tiles % 256 == 0 || tiles >= 1024) && nt >= 8 && !wres_eligible(p));
-    // (experiment builds, CA_GEMM_PQ: 2 = convolutions + GEGLU projections, 3 = convolutions only, 4 = 2 + plain dense, 5 = everything the rule allows)
-    const bool epi1 = p.geglu || p.ln_colsum || p.ln_stats;
-    const bool dflt2 = dflt && (mode == 1 || p.geglu), dflt3 = dflt && mode == 1, dflt4 = dflt && (mode == 1 || p.geglu || !epi1);
-    if ((pq_env < 0 && dflt) || pq_env == 1 || (pq_env == 2 && dflt2) || (pq_env == 3 && dflt3) || (pq_env == 4 && dflt4) || (pq_env == 5 && dflt)) {
-      g.kind = PK_PQ;
-      g.bm = 256, g.bn = 320, g.tiles = (unsigned)tiles;
-      return g;
-    }
-  }
-  static const int ps_env = CA_KNOB("CA_GEMM_PS", -1);
-  if (ps_env != 0 && ps_capable(p)) {
-    const int64_t tiles = (int64_t)ceil_div_i(p.m, 128) * (p.n / 320);
-    const bool dflt = mode == 0 && !wres_eligible(p) && nt <= 20 && tiles >= 256 && (p.geglu || p.n <= 1280);
-    if ((ps_env < 0 && dflt) || ps_env == 1 || (ps_env == 2 && !(mode == 0 && wres_eligible(p)))) {
-      g.kind = PK_PS;
-      g.bm = 128, g.bn = 320, g.tiles = (unsigned)tiles;
-      return g;
-    }
-  }
-  if (mode == 0 && dma && ar_eligible(p)) {
-    g.kind = PK_AR;
-    g.bm = 128, g.bn = 64;
-    return g;
-  }
-  if (mode == 0 && dma && wres_eligible(p)) {
-    g.kind = PK_WRES;
-    g.bm = 256, g.bn = 160;
-    return g;
-  }
-  if (dma && pp_env != 0 && nt >= 2 && p.n % 320 == 0 && p.splits <= 1) {  // 128 x 320 tiles
-    const int64_t tiles = (int64_t)ceil_div_i(p.m, 128) * (p.n / 320);
-    // (thresholds re-checked inside the step, same box, interleaved: dense 768 / 1024 tiles +0.25 ms, conv 512 +0.7, conv 128 +0.2)
-    if (p.row_sums || pp_env == 2 || (pp_env < 0 && tiles >= 128 && nt >= 10 && (tiles <= 256 || (tiles <= 512 && mode == 0)))) {
-      g.kind = PK_PP2;
-      g.bm = 128, g.bn = 320, g.tiles = (unsigned)tiles;
-      return g;
-    }
-  }
-  // 128x128 tiles unless N is not a multiple of 128 or the grid would leave CUs idle
-  // (8x8 / 16x16 latent levels: M = 2048 / 8192 rows -> < 2 blocks per CU with the big tile).
-  const bool wide = p.n % 128 == 0 && (int64_t)ceil_div_i(p.m, 128) * ceil_div_i(p.n, 128) >= 512;
-  const int64_t blocks = (int64_t)ceil_div_i(p.m, 128) * ceil_div_i(p.n, wide ? 128 : 64);
-  // LDS stages: ONE buffer (32 KB, two barriers per tile) lets 4 blocks share a CU, whose MFMA phases
-  // cover each other's transfer latency: measured +10..25% over double buffering (2 blocks per CU)
-  // and far better than 3-4 stage rings (1 block per CU).  Small grids (< 2 blocks per CU) have no
-  // co-resident blocks to overlap with: three stages (round 4; before that the double buffer) -- their K loops are chains of
-  // DMA round trips with 8 MFMAs per wave and tile in between; two tiles in flight instead of one: -0.3 ms per step, 62.0 vs
-  // 62.3 interleaved three times.  The 128 x 64 tile's ring is 74 KB: two blocks still share a CU.  Four stages (98 KB, one
-  // block per CU) lose.  (wide implies blocks >= 512: the 128 x 128 tile only ever runs single-buffered.)
-  const int nbuf = blocks >= 512 ? 1 : 3;
-  // N = 320 / 960 (every projection and conv of the 64x64-latent level): 128x160 tiles divide N
-  // exactly and read the A panel 2 / 6 times instead of 5 / 15 times
-  if (dma && !wide && p.n % 160 == 0 && (int64_t)ceil_div_i(p.m, 128) * (p.n / 160) >= 512) {
-    g.kind = PK_DMA;
-    g.bm = 128, g.bn = 160, g.nbuf = 1;
-    return g;
-  }
-  g.kind = dma ? PK_DMA : PK_REG;
-  g.bm = 128, g.bn = wide ? 128 : 64, g.nbuf = dma ? nbuf : 2;
-  return g;
-}
-
-// can the epilogue of this (dense) launch leave per-row sums of its output (ca_gemm_args.row_sums_out)?  Only the 128 x 320
-// tile kernels do; the answer is about the launch the arguments get WITHOUT the pointer.
-inline int row_sums_parts_of(GemmKParams p) {  // partial sums per row the launch can leave (0: none)
-  p.row_sums = nullptr;
-  if (p.geglu || p.out_f32) return 0;
-  const PlanKind k = plan_gemm(p, 0).kind;
-  if (k == PK_PP2 || k == PK_PS) return p.n / 320;          // one (sum, sum of squares) per 320-column tile
-  if (k == PK_PQ && !p.ln_colsum && !p.ln_stats) return 4 * (p.n / 320);  // the 256 x 320 kernel: one per 80-column wave quarter
-  return 0;
-}
-inline bool row_sums_capable(const GemmKParams& p) { return row_sums_parts_of(p) > 0; }
-
-inline void plan_label(const GemmPlan& g, char* buf, int len) {
-  switch (g.kind) {
-    case PK_WRES: snprintf(buf, len, "wres160"); break;
-    case PK_AR: snprintf(buf, len, "ar128x64"); break;
-    case PK_PP2: snprintf(buf, len, "pp128x320"); break;
-    case PK_PS: snprintf(buf, len, "ps128x320"); break;
-    case PK_PQ: snprintf(buf, len, "pq256x320"); break;
-    case PK_PP2_SPLITK: snprintf(buf, len, "pp128x320_splitk%d", g.splits); break;
-    case PK_DMA: snprintf(buf, len, "%dx%d%s", g.bm, g.bn, g.nbuf == 3 ? "_r3" : ""); break;
-    case PK_DMA_SPLITK: snprintf(buf, len, "128x128_splitk%d", g.splits); break;
-    case PK_REG: snprintf(buf, len, "reg_%dx%d", g.bm, g.bn); break;
-  }
-}
-
+// the plan (plan_gemm, ca_gemm_plan.h) -> the template instantiation it names
 template <int DT, int MODE>
-int launch_gemm(const GemmKParams& p, hipStream_t st) {
-  const GemmPlan g = plan_gemm(p, MODE);
+int launch_gemm(const GemmKParams& p, const GemmPlan& g, hipStream_t st) {
   const dim3 grid(ceil_div_i(p.m, g.bm) * ceil_div_i(p.n, g.bn));  // (the one-block-per-tile kernels below)
   switch (g.kind) {
     case PK_WRES: return ca_launch_gemm_pp(p, DT, MODE, PK_WRES, 0u, st);
@@ -706,275 +472,54 @@ int launch_gemm(const GemmKParams& p, hipStream_t st) {
   CA_FAIL(CA_ERR_LAUNCH, "ca_gemm: no kernel for plan kind %d, tile %dx%d, %d stages", (int)g.kind, g.bm, g.bn, g.nbuf);
 }
 
-// descriptor size in bytes, or 0 when the buffer is too large for 32-bit offsets (-> register variant)
-inline unsigned desc_bytes(int64_t elems) {
-  const int64_t b = elems * 2;
-  return (b > 0 && b < (int64_t)0xFFFFFF00ll) ? (unsigned)b : 0u;
-}
-
-int check_epilogue(const char* who, int n, int geglu, int out_f32, int64_t ldc, int64_t ld_res, const void* res) {
-  // N = 4 (conv_out) takes the direct 4-column epilogue; everything wider goes through the LDS-staged
-  // epilogue, which moves 8-column (16-byte) chunks: N, ldc and ld_res must then be multiples of 8
-  // (N = 12, 20, ... would store 8 values at column N-4: past the row end)
-  CA_REQUIRE(n == 4 || (n >= 8 && n % 8 == 0), "%s: N=%d must be 4 or a multiple of 8", who, n);
-  CA_REQUIRE(!geglu || n % 8 == 0, "%s: geglu needs N %% 8 == 0", who);
-  if (n >= 8) {
-    CA_REQUIRE(ldc % (geglu ? 4 : 8) == 0, "%s: ldc=%lld must be a multiple of %d", who, (long long)ldc, geglu ? 4 : 8);
-    CA_REQUIRE(!res || ld_res % 8 == 0, "%s: ld_res=%lld must be a multiple of 8", who, (long long)ld_res);
-  } else {
-    CA_REQUIRE(ldc % 4 == 0, "%s: ldc=%lld misaligned", who, (long long)ldc);
-    CA_REQUIRE(!res || ld_res % 4 == 0, "%s: ld_res=%lld misaligned", who, (long long)ld_res);
-  }
-  (void)out_f32;
-  return CA_OK;
-}
-
 }  // namespace
 
-static int gemm_fill(const ca_gemm_args* a, GemmKParams& p) {
-  CA_REQUIRE(a != nullptr, "ca_gemm: null args");
-  CA_REQUIRE(a->a && a->w && a->c, "ca_gemm: null operand");
-  CA_REQUIRE(a->m > 0 && a->k1 > 0 && a->k2 >= 0, "ca_gemm: bad sizes m=%d k1=%d k2=%d", a->m, a->k1, a->k2);
-  CA_REQUIRE(a->k1 % 8 == 0 && a->k2 % 8 == 0, "ca_gemm: k1=%d k2=%d must be multiples of 8", a->k1, a->k2);
-  CA_REQUIRE(a->lda % 8 == 0 && (a->k2 == 0 || (a->a2 && a->lda2 % 8 == 0)), "ca_gemm: lda/lda2 misaligned or a2 missing");
-  CA_REQUIRE(a->dtype == CA_BF16 || a->dtype == CA_F16, "ca_gemm: dtype %d", a->dtype);
-  CA_REQUIRE(!a->rowbias || a->rows_per_group > 0, "ca_gemm: rows_per_group");
-  CA_REQUIRE(!a->rowbias || a->ld_rowbias % 4 == 0, "ca_gemm: ld_rowbias misaligned");
-  int rc = check_epilogue("ca_gemm", a->n, a->geglu, a->out_f32, a->ldc, a->ld_res, a->residual);
-  if (rc) return rc;
-  p.a = (const u16*)a->a;
-  p.a2 = (const u16*)a->a2;
-  p.w = (const u16*)a->w;
-  p.c = a->c;
-  p.bias = a->bias;
-  p.rowbias = a->rowbias;
-  p.ln_stats = a->ln_stats;
-  p.ln_colsum = a->ln_colsum;
-  p.row_sums = a->row_sums_out;
-  p.ln_parts = a->ln_parts;
-  CA_REQUIRE(a->ln_parts >= 0 && a->ln_parts <= 16, "ca_gemm: ln_parts=%d", a->ln_parts);
-  CA_REQUIRE(a->ln_parts == 0 || (a->ln_stats && a->ln_colsum && a->ln_eps > 0.f), "ca_gemm: ln_parts needs ln_stats (the partial sums), ln_colsum and ln_eps > 0");
-  p.ln_inline = (a->ln_colsum && !a->ln_stats) ? 1 : 0;
-  p.ln_eps = a->ln_eps;
-  p.wf = (const u16*)a->w_frag;
-  CA_REQUIRE(!a->ln_stats || a->ln_colsum, "ca_gemm: ln_stats without ln_colsum");
-  CA_REQUIRE(!p.ln_inline || a->ln_eps > 0.f, "ca_gemm: ln_colsum without ln_stats asks for in-kernel statistics and needs ln_eps > 0");
-  CA_REQUIRE(!a->ln_colsum || (a->n >= 8 && a->k2 == 0), "ca_gemm: the folded LayerNorm needs N >= 8 and a single A source");
-  p.res = (const u16*)a->residual;
-  p.lda = a->lda;
-  p.lda2 = a->lda2;
-  p.ldc = a->ldc;
-  p.ld_res = a->ld_res;
-  p.ld_rowbias = a->ld_rowbias;
-  p.a_bytes = desc_bytes((int64_t)(a->m - 1) * a->lda + a->k1);
-  p.a2_bytes = a->k2 ? desc_bytes((int64_t)(a->m - 1) * a->lda2 + a->k2) : 0u;
-  p.w_bytes = desc_bytes((int64_t)a->n * (a->k1 + a->k2));
-  p.m = a->m;
-  p.n = a->n;
-  p.c1 = a->k1;
-  p.c2 = a->k2;
-  p.taps = 1;
-  p.kc_tiles = ceil_div_i(a->k1 + a->k2, BK);
-  p.rows_per_group = a->rows_per_group > 0 ? a->rows_per_group : 1;
-  p.alpha = a->alpha;
-  p.post = a->post_scale;
-  p.act = a->act;
-  p.geglu = a->geglu;
-  p.out_f32 = a->out_f32;
-  p.splits = 1;
-  return CA_OK;
-}
-
-// gemm_fill + the split-K decision: everything the plan depends on
-static int gemm_prepare(const ca_gemm_args* a, GemmKParams& p) {
-  int rc = gemm_fill(a, p);
-  if (rc) return rc;
-  {
-    const bool dma_ok = (a->k1 + a->k2) % BK == 0 && (a->k2 == 0 || a->k1 % BK == 0);
-    // (k_splitk_reduce and the weight-resident kernel read ln_stats as (mean, rstd): partial sums never take those plans)
-    const int s = dma_ok && !p.ln_inline && !p.row_sums && !p.ln_parts ? splitk_plan_dense(p.m, p.n, p.kc_tiles, p.geglu, p.out_f32) : 1;
-    if (s > 1 && a->workspace && a->workspace_bytes >= (int64_t)s * p.m * p.n * 4) {
-      p.splits = s;
-      p.partial = reinterpret_cast<float*>(a->workspace);
-    }
-  }
-  if (p.ln_inline && p.wf && a->workspace && a->workspace_bytes >= (int64_t)p.m * 8) p.partial = reinterpret_cast<float*>(a->workspace);  // (mean, rstd) scratch of k_gemm_ar
-  CA_REQUIRE(!p.row_sums || row_sums_capable(p), "ca_gemm: row_sums_out is not available for this launch: ask ca_gemm_row_sums_parts() first");
-  CA_REQUIRE(!p.ln_inline || wres_eligible(p), "ca_gemm: in-kernel LayerNorm statistics (ln_stats NULL) are not available for this launch: "
-             "ask ca_gemm_ln_inline_supported() first and pass ln_stats otherwise");
-  return CA_OK;
-}
-
 extern "C" int ca_gemm(const ca_gemm_args* a, void* stream) {
-  GemmKParams p{};
-  int rc = gemm_prepare(a, p);
+  DenseLaunch d;
+  int rc = gemm_prepare(a, d);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  rc = a->dtype == CA_BF16 ? launch_gemm<CA_BF16, 0>(p, st) : launch_gemm<CA_F16, 0>(p, st);
+  rc = a->dtype == CA_BF16 ? launch_gemm<CA_BF16, 0>(d.p, d.plan, st) : launch_gemm<CA_F16, 0>(d.p, d.plan, st);
   if (rc) return rc;
   CA_CHECK_LAUNCH("ca_gemm");
   return CA_OK;
 }
 
+// ---- questions about a dense launch, each over the same resolved view as ca_gemm itself (gemm_resolve, ca_gemm_plan.h)
 extern "C" int64_t ca_gemm_workspace_bytes(const ca_gemm_args* a) {
-  if (!a || a->m <= 0 || a->n <= 0 || a->k1 <= 0 || a->k2 < 0) return 0;
-  const int kc = a->k1 + a->k2;
-  if (a->ln_colsum && !a->ln_stats && a->w_frag && !a->ln_parts && !a->row_sums_out) {
-    // in-kernel LayerNorm statistics of the activation-resident kernel: (mean, rstd) per row
-    GemmKParams p{};
-    if (gemm_fill(a, p) != CA_OK) return 0;
-    p.partial = reinterpret_cast<float*>(uintptr_t(16));  // "a scratch is there": would the launch take that kernel?
-    return ar_eligible(p) ? (int64_t)a->m * 8 : 0;
-  }
-  if (kc % BK != 0 || (a->k2 != 0 && a->k1 % BK != 0) || (a->ln_colsum && !a->ln_stats) || a->ln_parts || a->row_sums_out) return 0;
-  const int s = splitk_plan_dense(a->m, a->n, ceil_div_i(kc, BK), a->geglu, a->out_f32);
-  return s > 1 ? (int64_t)s * a->m * a->n * 4 : 0;
+  DenseLaunch d;
+  return gemm_resolve(a, d) == CA_OK ? d.workspace : 0;
 }
 
 extern "C" int ca_gemm_row_sums_parts(const ca_gemm_args* a) {
-  GemmKParams p{};
-  if (!a || a->geglu || a->out_f32) return 0;
-  ca_gemm_args b = *a;
-  b.row_sums_out = nullptr;  // (the question is about the launch, whatever the pointer)
-  if (gemm_fill(&b, p) != CA_OK) return 0;
-  const int kc = a->k1 + a->k2;
-  const bool dma_ok = kc % BK == 0 && (a->k2 == 0 || a->k1 % BK == 0);
-  if (dma_ok && !p.ln_inline && !p.ln_parts && a->workspace && splitk_plan_dense(p.m, p.n, p.kc_tiles, p.geglu, p.out_f32) > 1) return 0;
-  return row_sums_parts_of(p);
+  DenseLaunch d;
+  DenseAsk ask{};
+  ask.without_row_sums = true;  // (the question is about the launch, whatever the pointer)
+  return gemm_resolve(a, d, ask) == CA_OK ? row_sums_parts_of(d.p) : 0;
 }
 
 extern "C" int ca_gemm_ln_inline_supported(const ca_gemm_args* a) {
-  GemmKParams p{};
-  if (!a || !a->ln_colsum || gemm_fill(a, p) != CA_OK) return 0;
-  return wres_eligible(p) ? 1 : 0;
+  DenseLaunch d;
+  return a && a->ln_colsum && gemm_resolve(a, d) == CA_OK && wres_eligible(d.p) ? 1 : 0;
 }
 
 // 1 if this launch, which hands over partial sums (ln_parts > 0), would run on a kernel that takes finished (mean, rstd) only
 // and is the faster one for the shape (the 256 x 320 streaming kernel): the caller then finishes the sums (ca_ln_finish_sums)
 // and passes ln_parts = 0.
 extern "C" int ca_gemm_wants_finished_stats(const ca_gemm_args* a) {
-  GemmKParams p{};
   if (!a || !a->ln_colsum || !a->ln_stats || a->ln_parts <= 0 || a->row_sums_out) return 0;
-  ca_gemm_args b = *a;
-  b.ln_parts = 0;
-  if (gemm_fill(&b, p) != CA_OK) return 0;
-  return plan_gemm(p, 0).kind == PK_PQ ? 1 : 0;
+  DenseLaunch d;
+  DenseAsk ask{};
+  ask.stats_finished = true;
+  return gemm_resolve(a, d, ask) == CA_OK && d.plan.kind == PK_PQ ? 1 : 0;
 }
 
-// The Winograd route of ca_conv3x3 (ca_conv_wino.h): 0 = not taken, else the workspace it needs (V [16][T][cin] + M [16][T][cout]).
-static int64_t wino_workspace_bytes(const ca_conv_args* a) {
-  if (!a || !a->w_wino || (a->dtype != CA_F16 && a->dtype != CA_BF16) || a->stride != 1 || a->pad_asym || a->out_f32) return 0;
-  if (a->upsample != 0 && a->upsample != 1) return 0;
-  if (a->x_is_wino_v && (a->cin2 != 0 || a->upsample)) return 0;
-  const int h = a->hin << a->upsample, w = a->win << a->upsample;  // logical input = output size
-  if (a->images <= 0 || h < 2 || w < 2 || (h & 1) || (w & 1)) return 0;
-  const int kc = a->cin1 + a->cin2;
-  static const int min_cin = CA_KNOB("CA_WINO_MIN_CIN", 1280);  // (experiments: where the route stops paying)
-  if (kc < 640 || kc % BK != 0 || a->cin1 % 8 != 0 || a->cin2 % 8 != 0 || a->cout % 320 != 0) return 0;
-  const int64_t tiles = (int64_t)a->images * (h / 2) * (w / 2);
-  // input channels: >= 1280 everywhere in the window; 640 .. 1279 only at <= 4096 tiles, where the direct form is short of tiles
-  // (32 x 16x16 640->1280: 100 vs 160 us; at 8192 tiles 640->640 254 vs 233-252, 960->640 318 vs 331: no / marginal gain)
-  if (kc < min_cin && !(min_cin == 1280 && tiles <= 4096)) return 0;
-  // whole 256-row tiles per transformed GEMM.  Measured (tools/wino_check.py, us, Winograd vs direct): 32 x 16x16 1280->1280 170 vs 276,
-  // 2560->1280 285 vs 529, 32 x 8x8 1280->1280 66 vs 87, 32 x 32x32 1920->640 510 vs 584, 1280->1280 634 vs 800; with 640 input channels
-  // the sixteen K = 640 GEMMs are epilogue-bound and the 4 x larger V / M tensors cost more than the saved MFMAs (no gain): >= 1280 only
-  static const int max_tiles = CA_KNOB("CA_WINO_MAX_TILES", 16384);
-  if (tiles % 256 != 0 || tiles > max_tiles) return 0;
-  if (16 * tiles * (int64_t)(kc > a->cout ? kc : a->cout) * 2 >= 0x7FFFFF00ll) return 0;  // 32-bit byte offsets in the GEMM
-  return 16 * tiles * (int64_t)((a->x_is_wino_v ? 0 : kc) + a->cout) * 2;  // V (unless the caller hands it over as x) + M
-}
-
-extern "C" int64_t ca_conv3x3_workspace_bytes(const ca_conv_args* a) {
-  if (!a || a->images <= 0 || a->hin <= 0 || a->win <= 0 || (a->stride != 1 && a->stride != 2)) return 0;
-  {
-    const int64_t wb = wino_workspace_bytes(a);
-    if (wb > 0) return wb;
-  }
-  const int hl = a->hin << a->upsample, wl = a->win << a->upsample;
-  const int pad = a->pad_asym ? 1 : 2;
-  const int64_t m = (int64_t)a->images * ((hl + pad - 3) / a->stride + 1) * ((wl + pad - 3) / a->stride + 1);
-  const int kc = a->cin1 + a->cin2;
-  if (m >= (1ll << 31) || kc % BK != 0 || (a->cin2 != 0 && a->cin1 % BK != 0)) return 0;
-  const int s = splitk_plan((int)m, a->cout, 9 * ceil_div_i(kc, BK), 0);
-  return s > 1 ? (int64_t)s * m * a->cout * 4 : 0;
-}
-
-static int conv_prepare(const ca_conv_args* a, GemmKParams& p) {
-  CA_REQUIRE(a != nullptr, "ca_conv3x3: null args");
-  CA_REQUIRE(a->x && a->w && a->y, "ca_conv3x3: null operand");
-  CA_REQUIRE(a->images > 0 && a->hin > 0 && a->win > 0, "ca_conv3x3: bad geometry");
-  CA_REQUIRE(a->cin1 > 0 && a->cin1 % 8 == 0 && a->cin2 >= 0 && a->cin2 % 8 == 0,
-             "ca_conv3x3: cin1=%d cin2=%d must be multiples of 8", a->cin1, a->cin2);
-  CA_REQUIRE(a->cin2 == 0 || a->x2, "ca_conv3x3: x2 missing");
-  CA_REQUIRE(a->stride == 1 || a->stride == 2, "ca_conv3x3: stride %d", a->stride);
-  CA_REQUIRE(a->upsample == 0 || a->upsample == 1, "ca_conv3x3: upsample %d", a->upsample);
-  CA_REQUIRE(a->dtype == CA_BF16 || a->dtype == CA_F16, "ca_conv3x3: dtype %d", a->dtype);
-  CA_REQUIRE(!a->rowbias || a->rows_per_group > 0, "ca_conv3x3: rows_per_group");
-  int rc = check_epilogue("ca_conv3x3", a->cout, 0, a->out_f32, a->cout, a->ld_res, a->residual);
-  if (rc) return rc;
-  const int hl = a->hin << a->upsample, wl = a->win << a->upsample;
-  CA_REQUIRE(a->pad_asym == 0 || a->pad_asym == 1, "ca_conv3x3: pad_asym %d", a->pad_asym);
-  const int pad = a->pad_asym ? 1 : 2;  // total padding per axis: 1+1, or 0 before / 1 after
-  const int hout = (hl + pad - 3) / a->stride + 1;
-  const int wout = (wl + pad - 3) / a->stride + 1;
-  const int64_t m64 = (int64_t)a->images * hout * wout;
-  CA_REQUIRE(m64 < (1ll << 31), "ca_conv3x3: too many output pixels");
-  p.a = (const u16*)a->x;
-  p.a2 = (const u16*)a->x2;
-  p.w = (const u16*)a->w;
-  p.c = a->y;
-  p.bias = a->bias;
-  p.rowbias = a->rowbias;
-  p.res = (const u16*)a->residual;
-  p.ldc = a->cout;
-  p.ld_res = a->ld_res;
-  p.ld_rowbias = a->ld_rowbias;
-  p.a_bytes = desc_bytes((int64_t)a->images * a->hin * a->win * a->cin1);
-  p.a2_bytes = a->cin2 ? desc_bytes((int64_t)a->images * a->hin * a->win * a->cin2) : 0u;
-  p.w_bytes = desc_bytes((int64_t)a->cout * 9 * (a->cin1 + a->cin2));
-  p.m = (int)m64;
-  p.n = a->cout;
-  p.c1 = a->cin1;
-  p.c2 = a->cin2;
-  p.taps = 9;
-  static const int tap_inner_env = CA_KNOB("CA_CONV_TAP_INNER", 1);
-  p.tap_inner = tap_inner_env;  // (0: taps outermost, the round-1 order -- A/B experiments)
-  p.kc_tiles = ceil_div_i(a->cin1 + a->cin2, BK);
-  p.hin = a->hin;
-  p.win = a->win;
-  p.hout = hout;
-  p.wout = wout;
-  p.stride = a->stride;
-  p.ups = a->upsample;
-  p.pad_lo = a->pad_asym ? 0 : 1;
-  p.rows_per_group = a->rows_per_group > 0 ? a->rows_per_group : 1;
-  p.alpha = a->alpha;
-  p.post = a->post_scale;
-  p.act = a->act;
-  p.geglu = 0;
-  p.out_f32 = a->out_f32;
-  p.splits = 1;
-  {
-    const int kc = a->cin1 + a->cin2;
-    const bool dma_ok = kc % BK == 0 && (a->cin2 == 0 || a->cin1 % BK == 0) && p.a_bytes && p.w_bytes && (a->cin2 == 0 || p.a2_bytes);
-    const int s = dma_ok ? splitk_plan(p.m, p.n, 9 * p.kc_tiles, 0) : 1;
-    if (s > 1 && a->workspace && a->workspace_bytes >= (int64_t)s * p.m * p.n * 4) {
-      p.splits = s;
-      p.partial = (float*)a->workspace;
-    }
-  }
-  return CA_OK;
-}
-
-static bool wino_taken(const ca_conv_args* a) {
-  const int64_t wb = wino_workspace_bytes(a);
-  return wb > 0 && a->workspace && a->workspace_bytes >= wb && (((uintptr_t)a->workspace | (uintptr_t)a->w_wino) & 15) == 0;
-}
+extern "C" int64_t ca_conv3x3_workspace_bytes(const ca_conv_args* a) { return conv_workspace_bytes(a); }
 
 static int launch_conv_wino(const ca_conv_args* a, const GemmKParams& cp, hipStream_t st) {
   const int kc = a->cin1 + a->cin2;
-  const int hl = a->hin << a->upsample, wl = a->win << a->upsample;
-  const int64_t tiles = (int64_t)a->images * (hl / 2) * (wl / 2);
+  const ConvGeom g = conv_geom(a);
+  const int64_t tiles = wino_tiles(a, g);
   WinoParams w{};
   w.x = (const u16*)a->x;
   w.x2 = (const u16*)a->x2;
@@ -987,7 +532,7 @@ static int launch_conv_wino(const ca_conv_args* a, const GemmKParams& cp, hipStr
   w.res = (const u16*)a->residual;
   w.ld_res = a->ld_res;
   w.ld_rowbias = a->ld_rowbias;
-  w.images = a->images, w.h = hl, w.w = wl, w.c1 = a->cin1, w.c2 = a->cin2, w.cout = a->cout;
+  w.images = a->images, w.h = g.hl, w.w = g.wl, w.c1 = a->cin1, w.c2 = a->cin2, w.cout = a->cout;
   w.ups = a->upsample;
   w.rows_per_group = cp.rows_per_group;
   w.alpha = a->alpha, w.post = a->post_scale, w.act = a->act;
@@ -1046,59 +591,10 @@ extern "C" int ca_conv3x3(const ca_conv_args* a, void* stream) {
   CA_REQUIRE(!a->x_is_wino_v, "ca_conv3x3: x_is_wino_v, but the Winograd route does not take these arguments (images=%d %dx%d cin=%d+%d cout=%d dtype=%d w_wino=%p "
              "workspace=%p of %lld bytes, needs %lld)", a->images, a->hin, a->win, a->cin1, a->cin2, a->cout, a->dtype, a->w_wino, a->workspace,
              (long long)a->workspace_bytes, (long long)wino_workspace_bytes(a));
-  rc = a->dtype == CA_BF16 ? launch_gemm<CA_BF16, 1>(p, st) : launch_gemm<CA_F16, 1>(p, st);
+  rc = a->dtype == CA_BF16 ? launch_gemm<CA_BF16, 1>(p, plan_gemm(p, 1), st) : launch_gemm<CA_F16, 1>(p, plan_gemm(p, 1), st);
   if (rc) return rc;
   CA_CHECK_LAUNCH("ca_conv3x3");
   return CA_OK;
-}
-
-// ---- nearest-x2 upsampling 3x3 convolution as four 2x2 phase convolutions in one launch (k_gemm_pq MODE 2, ca_gemm_pq.h).
-// An output pixel of parity (py, px) reads a 2x2 neighbourhood of the SOURCE image; the nine taps that land on the same source
-// pixel are summed at pack time (a->w = w_phase [4][cout][2][2][cin]): 4/9 of the multiply-adds of ca_conv3x3(upsample = 1).
-// up2_capable: what the kernel implements; up2_pays: where the form is taken by default (ca_conv_up2_phase_supported = both).
-static bool up2_capable(const ca_conv_args* a, GemmKParams& p) {
-  if (!a || !a->x || !a->w || !a->y || a->x2 || a->cin2 != 0 || a->images <= 0 || a->hin <= 0 || a->win <= 0) return false;
-  if (a->upsample != 1 || a->stride != 1 || a->pad_asym || a->out_f32 || a->x_is_wino_v || a->rowbias) return false;
-  if ((a->dtype != CA_F16 && a->dtype != CA_BF16) || a->act != CA_ACT_NONE || a->post_scale != 1.f) return false;
-  if (a->cin1 <= 0 || a->cin1 % BK != 0 || a->cout <= 0 || a->cout % 320 != 0) return false;
-  if ((((uintptr_t)a->x | (uintptr_t)a->w | (uintptr_t)a->y | (uintptr_t)a->residual) & 15) != 0) return false;
-  if (a->residual && (a->ld_res < a->cout || a->ld_res % 8 != 0)) return false;
-  const int64_t rows = (int64_t)a->images * a->hin * a->win;  // per phase: the source pixels
-  if (rows + a->win + 2 >= (1 << 23)) return false;           // packed row state of the gather: 24 signed bits of pixel index
-  p = GemmKParams{};
-  p.a = (const u16*)a->x;
-  p.w = (const u16*)a->w;
-  p.c = a->y;
-  p.bias = a->bias;
-  p.res = (const u16*)a->residual;
-  p.ldc = a->cout;
-  p.ld_res = a->ld_res;
-  p.a_bytes = desc_bytes(rows * a->cin1);
-  p.w_bytes = desc_bytes((int64_t)4 * a->cout * 4 * a->cin1);
-  p.n = a->cout;
-  p.c1 = a->cin1;
-  p.taps = 4;
-  p.tap_inner = 1;
-  p.kc_tiles = a->cin1 / BK;
-  p.hin = a->hin, p.win = a->win, p.hout = 2 * a->hin, p.wout = 2 * a->win;
-  p.stride = 1, p.ups = 1, p.pad_lo = 1;
-  p.rows_per_group = 1;
-  p.alpha = a->alpha, p.post = 1.f;
-  p.splits = 1;
-  p.up2_rows = (int)rows;
-  p.up2_tiles = ceil_div_i((int)rows, 256);
-  p.m = 4 * p.up2_tiles * 256;
-  p.up2_mag_w = a->win == 1 ? 0xFFFFFFFFu : (unsigned)((1ull << 32) / (unsigned)a->win);
-  p.up2_mag_h = a->hin == 1 ? 0xFFFFFFFFu : (unsigned)((1ull << 32) / (unsigned)a->hin);
-  p.w_group_stride = (unsigned)((int64_t)a->cout * 4 * a->cin1 * 2);
-  return p.a_bytes && p.w_bytes && act_out_fit31(p) && p.w_bytes < FIT31;
-}
-inline unsigned up2_tiles_total(const GemmKParams& p) { return (unsigned)(4 * p.up2_tiles * (p.n / 320)); }
-// Whole rounds of 256 tiles, or many (the rule of the 256 x 320 kernel's dense launches): 32 x 32x32 640->640 is 1024 tiles,
-// 32 x 16x16 1280->1280 is 512; 32 x 8x8 1280->1280 is 128 tiles -- half the chip -- and stays on the Winograd form.
-inline bool up2_pays(const GemmKParams& p) {
-  const unsigned tiles = up2_tiles_total(p);
-  return tiles >= 256 && (tiles % 256 == 0 || tiles >= 1024);
 }
 
 extern "C" int ca_conv_up2_phase_supported(const ca_conv_args* a) {
@@ -1128,10 +624,10 @@ extern "C" int ca_conv_up2_phase_plan_name(const ca_conv_args* a, char* buf, int
 // the launch requires them)
 extern "C" int ca_gemm_plan_name(const ca_gemm_args* a, char* buf, int32_t len) {
   CA_REQUIRE(buf && len > 0, "ca_gemm_plan_name: buffer");
-  GemmKParams p{};
-  int rc = gemm_prepare(a, p);
+  DenseLaunch d;
+  int rc = gemm_prepare(a, d);
   if (rc) return rc;
-  plan_label(plan_gemm(p, 0), buf, len);
+  plan_label(d.plan, buf, len);
   return CA_OK;
 }
 

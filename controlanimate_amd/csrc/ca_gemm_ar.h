@@ -26,7 +26,7 @@
 // once it has landed and leave (mean, rstd) in a caller-owned scratch of M x 8 bytes (ca_gemm_workspace_bytes), which the
 // epilogues read back (same block, behind a barrier).
 //
-// Requirements (ar_eligible in ca_gemm.hip): K = 320 from one source, N % 64 == 0, fp16 / bf16 output, alpha = post = 1, no
+// Requirements (ar_eligible in ca_gemm_plan.h): K = 320 from one source, N % 64 == 0, fp16 / bf16 output, alpha = post = 1, no
 // activation, no row sums, 32-bit byte offsets, row-bias groups of a multiple of 128 rows, GEGLU only without residual.
 
 // column (inside a wave's 64-column panel) of fragment row i of MFMA tile j: rows of a PAIR of tiles interleaved in fours so

@@ -391,7 +391,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmKParams& p, f32x4 (&acc)
 constexpr unsigned DMA_OOB = 0xFFFFFFF0u;  // beyond any descriptor size we accept -> hardware writes zeros
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-// The launch plan: WHICH kernel a set of arguments runs (plan_gemm in ca_gemm.hip decides, the launchers switch on it).
+// The launch plan: WHICH kernel a set of arguments runs (plan_gemm in ca_gemm_plan.h decides, the launchers switch on it).
 enum PlanKind {
   PK_WRES = 0,    // weight-resident streaming kernel, 160-column panels (ca_gemm_wres.h)
   PK_PP2,         // 128 x 320 ping-pong tiles (ca_gemm_pp2.h)

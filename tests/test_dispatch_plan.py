@@ -3,7 +3,7 @@
 
 The product library has no tuning environment variables (CA_KNOB compiles to its default), so the choice is a pure
 function of the arguments; `ca_gemm_plan_name` / `ca_conv3x3_plan_name` report it without a launch and this table pins it.
-A threshold edit in `plan_gemm` (csrc/ca_gemm.hip) that silently moves a headline shape to another kernel fails here --
+A threshold edit in `plan_gemm` (csrc/ca_gemm_plan.h) that silently moves a headline shape to another kernel fails here --
 and the network-level parity test at the headline size (tests/test_fullsize_gpu.py::test_config2_full_size_eps_vs_oracle)
 is what then has to be re-run on the GPU.
 """
@@ -186,7 +186,7 @@ RECT_UP2 = {(32, 8, 12, 1280, 1280): 0, (32, 16, 24, 1280, 1280): 1, (32, 32, 48
             (64, 12, 12, 1280, 1280): 0, (64, 24, 24, 1280, 1280): 1, (64, 48, 48, 640, 640): 1}
 
 
-# every name plan_label (csrc/ca_gemm.hip) can produce: the kernels a launch can reach.  (_splitkS: S = 2 .. 8 K ranges.)
+# every name plan_label (csrc/ca_gemm_plan.h) can produce: the kernels a launch can reach.  (_splitkS: S = 2 .. 8 K ranges.)
 PLAN_LABELS = ({"wres160", "ar128x64", "pp128x320", "ps128x320", "pq256x320", "wino_pq256x320", "128x160", "128x128", "128x64", "128x64_r3",
                 "reg_128x128", "reg_128x64"} | {f"{t}_splitk{s}" for t in ("pp128x320", "128x128") for s in range(2, 9)})
 
