@@ -144,6 +144,19 @@ class ConvNarrowArgs(C.Structure):  # ABI v14: ca_conv3x3_narrow_args (the RRDBN
     ]
 
 
+class PerceiverAttnArgs(C.Structure):  # ca_perceiver_attn_args (the IP-Adapter Plus Resampler)
+    _fields_ = [
+        ("q", C.c_void_p), ("x", C.c_void_p), ("l", C.c_void_p), ("o", C.c_void_p),
+        ("q_row", C.c_int64), ("q_batch", C.c_int64),
+        ("x_row", C.c_int64), ("x_batch", C.c_int64), ("x_v_off", C.c_int64),
+        ("l_row", C.c_int64), ("l_batch", C.c_int64), ("l_v_off", C.c_int64),
+        ("o_row", C.c_int64), ("o_batch", C.c_int64),
+        ("batches", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32),
+        ("nq", C.c_int32), ("n_x", C.c_int32), ("n_l", C.c_int32),
+        ("scale", C.c_float), ("dtype", C.c_int32),
+    ]
+
+
 # symbol -> (restype, argtypes); this table is also what tests/test_capi_symbols.py checks
 # against the declarations in include/controlanimate_hip.h.
 SYMBOLS = {
@@ -222,6 +235,8 @@ SYMBOLS = {
     "ca_conv_up2_phase_supported": (C.c_int, [C.POINTER(ConvArgs)]),
     "ca_conv_up2_phase": (C.c_int, [C.POINTER(ConvArgs), C.c_void_p]),
     "ca_conv_up2_phase_plan_name": (C.c_int, [C.POINTER(ConvArgs), C.c_char_p, C.c_int32]),
+    # added to ABI v16 likewise: the Resampler's attention over two key/value sources under one softmax (controlanimate_amd/resampler.py)
+    "ca_perceiver_attn": (C.c_int, [C.POINTER(PerceiverAttnArgs), C.c_void_p]),
 }
 
 _lib = None

@@ -280,8 +280,8 @@ class CLIPVisionModelWithProjection(_PackedModel):
         cfg.update(kw)
         return cls(**{k: v for k, v in cfg.items() if k in VISION_CONFIG})
 
-    @torch.no_grad()
-    def forward(self, pixel_values: torch.Tensor, output_attentions=None, output_hidden_states=None, return_dict=None):
+    def _embed(self, pixel_values: torch.Tensor):
+        """pixel_values [B,3,S,S] -> (pre_layrnorm(embeddings) [B*n, C], B, n): the input of encoder layer 0."""
         cfg = self.config
         if pixel_values.dim() != 4 or pixel_values.shape[1] != 3 or pixel_values.shape[2] != cfg.image_size or pixel_values.shape[3] != cfg.image_size:
             raise ValueError(f"expected [B,3,{cfg.image_size},{cfg.image_size}], got {tuple(pixel_values.shape)}")
@@ -297,13 +297,32 @@ class CLIPVisionModelWithProjection(_PackedModel):
         cls = vm.embeddings.class_embedding.to(self.act_dtype).expand(b, 1, -1)
         n = g * g + 1
         x = (torch.cat([cls, tok], 1).float() + vm.embeddings.position_embedding.weight).to(self.act_dtype).reshape(b * n, -1).contiguous()
-        x = vm.pre_layrnorm.run(x)
+        return vm.pre_layrnorm.run(x), b, n
+
+    @torch.no_grad()
+    def forward(self, pixel_values: torch.Tensor, output_attentions=None, output_hidden_states=None, return_dict=None):
+        """output_hidden_states=True adds `hidden_states` as transformers does: num_hidden_layers + 1 tensors [B, n, C], entry 0 the
+        output of pre_layrnorm, entry i the output of encoder layer i, the last one `last_hidden_state`."""
+        vm = self.vision_model
+        x, b, n = self._embed(pixel_values)
+        hidden = [x.view(b, n, -1)] if output_hidden_states else None
         for layer in vm.encoder.layers:
             x = layer.run(x, b, n, causal=False)
+            if hidden is not None:
+                hidden.append(x.view(b, n, -1))
         last = x.view(b, n, -1)
         pooled = vm.post_layernorm.run(last[:, 0].contiguous())
         embeds = self.visual_projection.run(pooled)
-        return _Out(image_embeds=embeds, last_hidden_state=last)
+        return _Out(image_embeds=embeds, last_hidden_state=last, hidden_states=None if hidden is None else tuple(hidden))
+
+    @torch.no_grad()
+    def penultimate_hidden_state(self, pixel_values: torch.Tensor) -> torch.Tensor:
+        """hidden_states[-2] [B, n, C] alone: every encoder layer but the last, no pooling, no projection (what IP-Adapter Plus
+        feeds its Resampler, modules/ip_adapter.py:368-380)."""
+        x, b, n = self._embed(pixel_values)
+        for layer in self.vision_model.encoder.layers[:-1]:
+            x = layer.run(x, b, n, causal=False)
+        return x.view(b, n, -1)
 
 
 # ------------------------------------------------------------------------------------------ host-side preprocessing

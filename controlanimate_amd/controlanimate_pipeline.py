@@ -21,6 +21,9 @@ Alternatively models are injected:
                       text_encoder=None | controlanimate_amd.clip.CLIPTextModel, tokenizer=None | CLIPTokenizer,
                       encode_prompt=None | callable(str)->Tensor[1,77,768]   (e.g. the reference's Compel object),
                       ip_adapter_ckpt=None|dict, image_encoder=None | clip.CLIPVisionModelWithProjection | callable)
+The IP-Adapter variant follows from the checkpoint (`ip_adapter_variant`): ip-adapter_sd15.bin gives the plain 4-token adapter,
+ip-adapter-plus_sd15.bin (config key `ipadapter_ckpt`, the reference's commented-out alternative at :80-81) gives IPAdapterPlus
+with the 16 tokens of the Resampler.
 With text_encoder + tokenizer and no encode_prompt the prompt is encoded unweighted (what Compel returns
 for a prompt without weighting syntax; Compel itself, :133-135, is third-party host code and not rebuilt).
 Checkpoint conversion / LoRA fusing: controlanimate_amd.weight_ingest.  With a VAE attached `animate`
@@ -35,7 +38,7 @@ import torch
 from .configs import NOISE_SCHEDULER_KWARGS
 from .controlanimation_pipeline import ControlAnimationPipeline
 from .controlresiduals_pipeline import MultiControlNetResidualsPipeline
-from .ip_adapter import IPAdapter
+from .ip_adapter import IPAdapter, IPAdapterPlus
 from .schedulers import get_scheduler
 
 
@@ -48,6 +51,20 @@ def _get(cfg, key, default=None):
 IP_IMAGE_ENCODER_PATH = "models/IP-Adapter/models/image_encoder/"   # modules/controlanimate_pipeline.py:80
 IP_CKPT_PATH = "models/IP-Adapter/models/ip-adapter_sd15.bin"       # :81
 TI_PATH = "models/TI/easynegative.safetensors"                       # :118
+
+
+def ip_adapter_variant(ckpt, cross_attention_dim: int):
+    """(class, num_tokens) from an IP-Adapter checkpoint's `image_proj` section: `latents` [1, n, dim] is the Resampler of IPAdapterPlus,
+    `proj.weight` [n * cross_attention_dim, clip_dim] the plain adapter's ImageProjModel; `proj.0.weight` is the MLPProjModel of
+    IPAdapterFull, which is not implemented."""
+    proj = ckpt["image_proj"]
+    if "latents" in proj:
+        return IPAdapterPlus, int(proj["latents"].shape[1])
+    if "proj.weight" in proj:
+        return IPAdapter, int(proj["proj.weight"].shape[0]) // int(cross_attention_dim)
+    if "proj.0.weight" in proj:
+        raise NotImplementedError("this checkpoint's image_proj is an MLPProjModel (proj.0.weight): IPAdapterFull is not implemented")
+    raise ValueError(f"unrecognised IP-Adapter checkpoint: image_proj keys {sorted(proj)[:4]}...")
 
 
 def components_from_config(config) -> Dict[str, Any]:
@@ -73,7 +90,7 @@ def components_from_config(config) -> Dict[str, Any]:
     comp["controlnets"] = [LM.load_controlnet(n) for n in names] if names else []
     if bool(_get(config, "use_ipadapter", 0)):
         comp["image_encoder"] = LM.load_image_encoder(IP_IMAGE_ENCODER_PATH)
-        comp["ip_adapter_ckpt"] = LM.read_checkpoint(IP_CKPT_PATH)
+        comp["ip_adapter_ckpt"] = LM.read_checkpoint(_get(config, "ipadapter_ckpt", None) or IP_CKPT_PATH)
     return comp
 
 
@@ -116,7 +133,9 @@ class ControlAnimatePipeline:
             self.encode_prompt = Compel(tokenizer=self.pipeline.tokenizer, text_encoder=self.pipeline.text_encoder, device=self.device)
         self.use_ipadapter = bool(_get(config, "use_ipadapter", 0))
         if self.use_ipadapter:
-            ip = IPAdapter(self.pipeline, components.get("image_encoder"), components.get("ip_adapter_ckpt"), self.device, num_tokens=4)
+            ckpt = components.get("ip_adapter_ckpt")
+            cls, num_tokens = (IPAdapter, 4) if ckpt is None else ip_adapter_variant(ckpt, unet.config.cross_attention_dim)
+            ip = cls(self.pipeline, components.get("image_encoder"), ckpt, self.device, num_tokens=num_tokens)
             self.pipeline.ip_adapter = ip
             if self.multicontrolnetresiduals_pipeline is not None:
                 ip.set_ip_adapter_4controlanimate(self.multicontrolnetresiduals_pipeline)

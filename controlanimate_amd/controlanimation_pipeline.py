@@ -365,6 +365,34 @@ class ControlAnimationPipeline:
             if torch.get_num_threads() != host_threads:
                 torch.set_num_threads(host_threads)
 
+    def _append_image_tokens(self, prompt_embeds, negative_prompt_embeds, device, last_output_frames, ipa_scale, kwargs):
+        """The context rows the IP-Adapter processors read after the text tokens (:698-710): a fixed image prompt, the previous window's
+        first frame, or -- a first window without either -- zeros; `self.ip_adapter.num_tokens` rows in every case."""
+        fixed_tok, fixed_untok = kwargs.get("image_prompt_embeds"), kwargs.get("uncond_image_prompt_embeds")
+        if fixed_tok is not None:
+            # a FIXED image prompt (the tokens `get_image_embeds_4controlanimate` returns, computed once by the caller): the
+            # window does not look at the previous window's output, so windows stay independent problems and can be
+            # sharded (vid2vid.run_video_sharded).  The reference's animate() has these two parameters
+            # (modules/controlanimate_pipeline.py:124-127) and never forwards them; here they are live.
+            if fixed_untok is None:
+                raise ValueError("image_prompt_embeds needs uncond_image_prompt_embeds (both outputs of get_image_embeds_4controlanimate)")
+            self.ip_adapter.set_scale(ipa_scale)
+            prompt_embeds = torch.cat([prompt_embeds, fixed_tok.to(device).float().view(1, -1, prompt_embeds.shape[-1])], dim=1)
+            negative_prompt_embeds = torch.cat([negative_prompt_embeds, fixed_untok.to(device).float().view(1, -1, prompt_embeds.shape[-1])], dim=1)
+        elif last_output_frames is not None or kwargs.get("clip_image_embeds") is not None:
+            img_tok, uncond_tok = self.ip_adapter.get_image_embeds_4controlanimate(
+                pil_image=None if last_output_frames is None else last_output_frames[0], scale=ipa_scale,
+                clip_image_embeds=kwargs.get("clip_image_embeds"))
+            prompt_embeds = torch.cat([prompt_embeds, img_tok.to(device).float()], dim=1)
+            negative_prompt_embeds = torch.cat([negative_prompt_embeds, uncond_tok.to(device).float()], dim=1)
+        else:
+            # as many zero tokens as the processors strip: the reference writes 4 (:709-710), which with its own IPAdapterPlus
+            # (16 tokens) would make them read 12 text tokens as image tokens (DESIGN: quirk notes)
+            z = torch.zeros((1, int(getattr(self.ip_adapter, "num_tokens", 4)), prompt_embeds.shape[-1]), device=device)
+            prompt_embeds = torch.cat([prompt_embeds, z], dim=1)
+            negative_prompt_embeds = torch.cat([negative_prompt_embeds, z], dim=1)
+        return prompt_embeds, negative_prompt_embeds
+
     def _denoise(self, video_length, input_frames, prompt, height, width, num_inference_steps, strength, guidance_scale,
                  negative_prompt, num_videos_per_prompt, eta, generator, latents, output_type, return_dict, callback,
                  callback_steps, overlaps, multicontrolnetresiduals_pipeline, multicontrolnetresiduals_overlap_pipeline,
@@ -388,27 +416,8 @@ class ControlAnimationPipeline:
 
         # IP-Adapter tokens (:698-710)
         if self.ip_adapter is not None:
-            fixed_tok, fixed_untok = kwargs.get("image_prompt_embeds"), kwargs.get("uncond_image_prompt_embeds")
-            if fixed_tok is not None:
-                # a FIXED image prompt (the tokens `get_image_embeds_4controlanimate` returns, computed once by the caller): the
-                # window does not look at the previous window's output, so windows stay independent problems and can be
-                # sharded (vid2vid.run_video_sharded).  The reference's animate() has these two parameters
-                # (modules/controlanimate_pipeline.py:124-127) and never forwards them; here they are live.
-                if fixed_untok is None:
-                    raise ValueError("image_prompt_embeds needs uncond_image_prompt_embeds (both outputs of get_image_embeds_4controlanimate)")
-                self.ip_adapter.set_scale(ipa_scale)
-                prompt_embeds = torch.cat([prompt_embeds, fixed_tok.to(device).float().view(1, -1, prompt_embeds.shape[-1])], dim=1)
-                negative_prompt_embeds = torch.cat([negative_prompt_embeds, fixed_untok.to(device).float().view(1, -1, prompt_embeds.shape[-1])], dim=1)
-            elif last_output_frames is not None or kwargs.get("clip_image_embeds") is not None:
-                img_tok, uncond_tok = self.ip_adapter.get_image_embeds_4controlanimate(
-                    pil_image=None if last_output_frames is None else last_output_frames[0], scale=ipa_scale,
-                    clip_image_embeds=kwargs.get("clip_image_embeds"))
-                prompt_embeds = torch.cat([prompt_embeds, img_tok.to(device).float()], dim=1)
-                negative_prompt_embeds = torch.cat([negative_prompt_embeds, uncond_tok.to(device).float()], dim=1)
-            else:
-                z = torch.zeros((1, 4, prompt_embeds.shape[-1]), device=device)
-                prompt_embeds = torch.cat([prompt_embeds, z], dim=1)
-                negative_prompt_embeds = torch.cat([negative_prompt_embeds, z], dim=1)
+            prompt_embeds, negative_prompt_embeds = self._append_image_tokens(prompt_embeds, negative_prompt_embeds, device, last_output_frames,
+                                                                              ipa_scale, kwargs)
         lcm_prompt_embeds = prompt_embeds.contiguous()
         cfg_prompt_embeds = torch.cat([negative_prompt_embeds, prompt_embeds]).contiguous() if do_cfg else lcm_prompt_embeds
 

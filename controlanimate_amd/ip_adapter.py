@@ -9,6 +9,9 @@ Follows the reference's modules/ip_adapter.py:
                                   positions whose key contains "attn2" -- order down 0-2 (x2), up 1-3
                                   (x3), mid
   set_scale (:200-203), ImageProjModel (:30-47), get_image_embeds(_4controlanimate) (:187-222)
+  IPAdapterPlus (:352-380)        init_proj builds the perceiver Resampler (resampler.py) with num_tokens queries; the image prompt is
+                                  the Resampler of the PENULTIMATE hidden state of the CLIP vision encoder, the unconditional one
+                                  that of an all-zero pixel tensor
 The CLIP vision encoder that produces `clip_image_embeds` [n,1024] runs once per window, not per
 step: pass `image_encoder=` a controlanimate_amd.clip.CLIPVisionModelWithProjection (HIP; the images go
 through clip_preprocess first), any callable (PIL -> [1,1024]), or the embeds themselves.
@@ -64,12 +67,16 @@ class IPAdapter:
         self.ip_ckpt = ip_ckpt
         self.num_tokens = num_tokens
         self.pipe = sd_pipe
+        self.clip_embeddings_dim = clip_embeddings_dim
         self.set_ip_adapter()
-        self.image_proj_model = ImageProjModel(cross_attention_dim=self.pipe.unet.config.cross_attention_dim,
-                                               clip_embeddings_dim=clip_embeddings_dim,
-                                               clip_extra_context_tokens=num_tokens).to(self.device)
+        self.image_proj_model = self.init_proj()
         if ip_ckpt is not None:
             self.load_ip_adapter()
+
+    def init_proj(self):
+        """The model that turns the image encoder's output into num_tokens context tokens (reference :77-81; subclasses override)."""
+        return ImageProjModel(cross_attention_dim=self.pipe.unet.config.cross_attention_dim, clip_embeddings_dim=self.clip_embeddings_dim,
+                              clip_extra_context_tokens=self.num_tokens).to(self.device)
 
     # ---- reference :95-127 --------------------------------------------------------------------
     def set_ip_adapter(self):
@@ -164,3 +171,55 @@ class IPAdapter:
         tokens = tokens.repeat(1, num_samples, 1).view(bs * num_samples, seq, -1)
         uncond = uncond.repeat(1, num_samples, 1).view(bs * num_samples, seq, -1)
         return tokens, uncond
+
+
+class IPAdapterPlus(IPAdapter):
+    """IP-Adapter Plus (reference :352-380; ip-adapter-plus_sd15.bin): num_tokens = 16 tokens from the perceiver Resampler over the
+    penultimate hidden state of the CLIP vision encoder.  Needs the HIP CLIPVisionModelWithProjection: the unconditional tokens come
+    from the encoder's pass over an all-zero image, which depends on the encoder's weights alone and is computed once per packed
+    arena (a new prepare() of the encoder makes a new arena and with it a new pass)."""
+
+    def __init__(self, sd_pipe, image_encoder, ip_ckpt, device, num_tokens=16):
+        if image_encoder is not None and not hasattr(image_encoder, "penultimate_hidden_state"):
+            raise TypeError("IPAdapterPlus needs the HIP CLIPVisionModelWithProjection as image_encoder (the unconditional tokens are its "
+                            f"pass over an all-zero image), got {type(image_encoder).__name__}")
+        self._zero_state = None  # (the encoder's arena, penultimate state of the all-zero image [1, tokens, hidden])
+        super().__init__(sd_pipe, image_encoder, ip_ckpt, device, num_tokens=num_tokens)
+
+    def init_proj(self):
+        from .clip import VISION_CONFIG
+        from .resampler import Resampler
+        hidden = self.image_encoder.config.hidden_size if self.image_encoder is not None else VISION_CONFIG["hidden_size"]
+        dim = self.pipe.unet.config.cross_attention_dim
+        return Resampler(dim=dim, depth=4, dim_head=64, heads=12, num_queries=self.num_tokens, embedding_dim=hidden, output_dim=dim,
+                         ff_mult=4).to(self.device)
+
+    def zero_image_state(self) -> torch.Tensor:
+        enc = self.image_encoder
+        if enc is None:
+            raise RuntimeError("IPAdapterPlus has no image_encoder attached: the unconditional tokens need its pass over an all-zero image")
+        if enc.arena is None or self._zero_state is None or self._zero_state[0] is not enc.arena:
+            size = enc.config.image_size
+            state = enc.penultimate_hidden_state(torch.zeros((1, 3, size, size), device=self.device))  # (packs the encoder if need be)
+            self._zero_state = (enc.arena, state)
+        return self._zero_state[1]
+
+    @torch.no_grad()
+    def get_image_embeds(self, pil_image=None, clip_image_embeds=None):
+        """clip_image_embeds: penultimate hidden states [n, tokens, hidden] (not the pooled embedding of the plain adapter)."""
+        if self.image_encoder is None:
+            raise RuntimeError("IPAdapterPlus has no image_encoder attached: the unconditional tokens need its pass over an all-zero image")
+        if pil_image is not None:
+            from .clip import clip_preprocess
+            px = clip_preprocess(pil_image, self.image_encoder.config.image_size)
+            clip_image_embeds = self.image_encoder.penultimate_hidden_state(px.to(self.device))
+        elif clip_image_embeds is None:
+            raise ValueError("pass pil_image or clip_image_embeds")
+        elif clip_image_embeds.dim() != 3:
+            raise ValueError(f"IPAdapterPlus takes penultimate hidden states [n, tokens, hidden], got {tuple(clip_image_embeds.shape)}")
+        proj = self.image_proj_model
+        states = clip_image_embeds.to(device=self.device, dtype=proj.act_dtype)
+        n = states.shape[0]
+        zero = self.zero_image_state().to(proj.act_dtype).expand(n, -1, -1)
+        out = proj(torch.cat([states, zero], 0))  # one batch through the Resampler
+        return out[:n], out[n:]

@@ -12,7 +12,7 @@ import torch
 
 from . import _capi
 from .context import dispatch
-from ._capi import (AttnArgs, ConvArgs, ConvNarrowArgs, FfArgs, TattnArgs, XattnArgs, GemmArgs, GroupNormArgs, LayerNormArgs, CA_ACT_NONE,
+from ._capi import (AttnArgs, ConvArgs, ConvNarrowArgs, FfArgs, PerceiverAttnArgs, TattnArgs, XattnArgs, GemmArgs, GroupNormArgs, LayerNormArgs, CA_ACT_NONE,
                     CA_ACT_SILU, CA_BF16, CA_F16, check, lib)
 
 ACT_NONE, ACT_SILU = CA_ACT_NONE, CA_ACT_SILU
@@ -557,6 +557,34 @@ def attention_temporal(qkv: torch.Tensor, b: int, frames: int, tokens: int, head
                   k_strides=(frames * tokens * ld, ld, tokens * ld), inner_count=tokens, kv_inner_count=tokens,
                   kv_div=1, batches=b * tokens, heads=heads, head_dim=d, nq=frames, nk=frames, scale=d ** -0.5)
     return o
+
+
+def perceiver_attn(q: torch.Tensor, x_k: torch.Tensor, x_v: torch.Tensor, l_k: torch.Tensor, l_v: torch.Tensor, heads: int, *,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """o = softmax(head_dim^-0.5 q [k_x ; k_l]^T) [v_x ; v_l] per (batch, head) under ONE softmax (ca_perceiver_attn: the Resampler of
+    IP-Adapter Plus).  q [B, nq, heads * 64]; x_k / x_v [B, n_x, heads * 64] views of one buffer with the same strides (a column slice of
+    the all-layers K|V GEMM), l_k / l_v [B, n_l, heads * 64] likewise (the layer's q|k|v GEMM); the last dimension contiguous.  Returns
+    [B, nq, heads * 64] (`out`: any view with a contiguous last dimension)."""
+    _req_cuda(q, x_k, x_v, l_k, l_v, out)
+    b, nq, inner = q.shape
+    for t in (q, x_k, x_v, l_k, l_v):
+        assert t.dim() == 3 and t.shape[0] == b and t.shape[2] == inner and t.stride(2) == 1 and t.dtype == q.dtype
+    assert x_k.shape == x_v.shape and x_k.stride() == x_v.stride() and l_k.shape == l_v.shape and l_k.stride() == l_v.stride()
+    assert inner % heads == 0
+    if out is None:
+        out = torch.empty((b, nq, inner), device=q.device, dtype=q.dtype)
+    assert out.shape == (b, nq, inner) and out.stride(2) == 1 and out.dtype == q.dtype
+    d = inner // heads
+    es = q.element_size()
+    args = PerceiverAttnArgs(q=_p(q), x=_p(x_k), l=_p(l_k), o=_p(out), q_row=q.stride(1), q_batch=q.stride(0),
+                             x_row=x_k.stride(1), x_batch=x_k.stride(0), x_v_off=(x_v.data_ptr() - x_k.data_ptr()) // es,
+                             l_row=l_k.stride(1), l_batch=l_k.stride(0), l_v_off=(l_v.data_ptr() - l_k.data_ptr()) // es,
+                             o_row=out.stride(1), o_batch=out.stride(0), batches=b, heads=heads, head_dim=d, nq=nq, n_x=x_k.shape[1],
+                             n_l=l_k.shape[1], scale=float(d ** -0.5), dtype=dt_code(q.dtype))
+    if _plan_sink is not None:
+        _plan_sink.append("perceiver_attn")
+    check(lib().ca_perceiver_attn(C.byref(args), _stream()), "ca_perceiver_attn")
+    return out
 
 
 def add_bcast(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -704,6 +704,31 @@ int ca_canny_link_stage(int32_t images, int32_t h, int32_t w, void* workspace, i
 int ca_canny_emit(int32_t images, int32_t h, int32_t w, const void* workspace, int64_t workspace_bytes, uint8_t* edges,
                   void* control, int32_t rep, int32_t control_dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * ca_perceiver_attn (added to ABI v16: no struct or existing function changes, the number stays): the attention of the
+ * IP-Adapter Plus Resampler (PerceiverAttention, modules/resampler.py:49-78).  For batch b and head h:
+ *   Q    = rows 0 .. nq-1 of q + b*q_batch, columns h*64 .. h*64+63
+ *   keys = the n_x rows of x + b*x_batch followed by the n_l rows of l + b*l_batch, the same columns; the values are the
+ *          same rows x_v_off / l_v_off elements further on
+ *   o + b*o_batch, rows 0 .. nq-1, the same columns = softmax_fp32(scale * Q K^T) V  -- ONE softmax over both sources
+ * (ca_attention's `accumulate` adds two separately normalised attentions, a different function).  Every tensor has its own row
+ * and batch stride in elements.  head_dim == 64, 1 <= nq <= 16, n_x >= 1, n_l >= 1, pointers 16-byte aligned, strides multiples
+ * of 8 elements; anything else is CA_ERR_INVALID_ARG before any launch.  One block per (batch, head); the partial softmaxes of
+ * its waves are merged in a fixed order, without atomics: two runs give the same bits.
+ * ------------------------------------------------------------------------------------ */
+typedef struct ca_perceiver_attn_args {
+  const void* q; const void* x; const void* l; void* o;
+  int64_t q_row, q_batch;
+  int64_t x_row, x_batch, x_v_off;
+  int64_t l_row, l_batch, l_v_off;
+  int64_t o_row, o_batch;
+  int32_t batches, heads, head_dim;
+  int32_t nq, n_x, n_l;
+  float scale;          /* softmax scale (head_dim^-0.5), applied in fp32 to the logits */
+  int32_t dtype;
+} ca_perceiver_attn_args;
+int ca_perceiver_attn(const ca_perceiver_attn_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
