@@ -12,8 +12,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CA_HIP_LIB") or os.path.join(_HERE, "csrc", "libcontrolanimate_hip.so")  # (CA_HIP_LIB: another build of the same ABI, for same-box A/B timing)
 
 CA_BF16, CA_F16 = 0, 1
-CA_F32 = 2  # output of ca_canny_emit only
+CA_F32 = 2  # control tensor of ca_canny_emit / ca_hed_fuse only
 CA_ACT_NONE, CA_ACT_SILU = 0, 1
+CA_ACT_RELU = 4  # the VGG stack of the HED annotator (hed.py)
 ABI_VERSION = 16
 
 
@@ -237,6 +238,10 @@ SYMBOLS = {
     "ca_conv_up2_phase_plan_name": (C.c_int, [C.POINTER(ConvArgs), C.c_char_p, C.c_int32]),
     # added to ABI v16 likewise: the Resampler's attention over two key/value sources under one softmax (controlanimate_amd/resampler.py)
     "ca_perceiver_attn": (C.c_int, [C.POINTER(PerceiverAttnArgs), C.c_void_p]),
+    # added to ABI v16 likewise: the stages of the HED annotator around its convolutions (controlanimate_amd/hed.py)
+    "ca_hed_prep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ca_hed_pool_side": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ca_hed_fuse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
 }
 
 _lib = None

@@ -6,8 +6,10 @@
 non-maximum suppression with OpenCV's fixed-point tan(22.5 deg) sector test; hysteresis (strong > high,
 weak > low connected through the 8-neighbourhood).  OpenCV is a THIRD-PARTY dependency that is absent here, so
 this restatement is UNPINNED (no cv2 output to compare with); tests check the algorithmic properties.
-The learned detectors (openpose, hed, lineart, mlsd, depth: controlnet_aux / transformers models, :56-61) are
-not rebuilt: plug them in through `MultiControlNetResidualsPipeline(annotators={...})`.
+Of the learned detectors (controlnet_aux / transformers models, :56-61) HED, the sample config's, is rebuilt: `HedAnnotator` (hed.py,
+re-exported here) runs ControlNetHED for a whole window on the GPU from a local ControlNetHED.pth, opt-in through
+`annotators={"hed": HedAnnotator.from_pretrained(path)}`.  The others (openpose, lineart, mlsd, depth) are not rebuilt: plug them in
+through `MultiControlNetResidualsPipeline(annotators={...})`.
 
 `CannyAnnotator` is the same function for a whole window of frames on the GPU (ABI v16, csrc/ca_canny.hip): opt-in through
 `annotators={"canny": CannyAnnotator(device)}`; `canny` stays the default.  `canny_edges` is its specification: the device result
@@ -21,6 +23,8 @@ try:
     from PIL import Image
 except Exception:  # pragma: no cover
     Image = None
+
+from .hed import HedAnnotator  # noqa: E402,F401  (the learned HED detector on the GPU; torch is imported when it is used)
 
 
 def _sobel(ch: np.ndarray):

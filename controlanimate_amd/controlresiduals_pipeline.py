@@ -11,8 +11,9 @@ Same call surface as the reference's modules/controlresiduals_pipeline.py:
 
 The returned residuals are [b,C,f,h,w] VIEWS of channels-last storage, which the UNet consumes
 without a copy (unet.py `_to_nhwc`).  Annotators (reference :97-150): canny is built in
-(controlanimate_amd/annotators.py, a numpy restatement of cv2.Canny(img, 100, 200)); the learned detectors
-(openpose / hed / lineart / mlsd / depth) are third-party models outside the loop and are NOT rebuilt: pass
+(controlanimate_amd/annotators.py, a numpy restatement of cv2.Canny(img, 100, 200)); HED, the sample config's detector, runs on
+the GPU from the user's ControlNetHED.pth through `annotators={"hed": HedAnnotator.from_pretrained(path)}` (controlanimate_amd/hed.py);
+the other learned detectors (openpose / lineart / mlsd / depth) are third-party models outside the loop and are NOT rebuilt: pass
 already-annotated control images, or plug callables in through `annotators`.
 """
 from __future__ import annotations

@@ -1,0 +1,294 @@
+"""The HED edge annotator of the reference's sample config (configs/prompts/SampleConfig.yaml: lllyasviel/sd-controlnet-hed, whose
+control frames come from controlnet_aux's HEDdetector, modules/controlresiduals_pipeline.py:58, 116-117) on the GPU, for a whole
+window of frames at once.
+
+The network (ControlNetHED_Apache2: a learned per-channel `norm` subtracted from float RGB in 0..255; five blocks of 3x3
+convolutions + ReLU, 3->64 x2, 64->128 x2, 128->256 x3, 256->512 x3, 512->512 x3, blocks 2..5 behind a 2x2 max pool; a 1x1
+projection to a one-channel side map per block) runs as: ca_hed_prep (uint8 -> NHWC with 8 channels), thirteen ca_conv3x3 with
+CA_ACT_RELU on two ping-pong buffers, ca_hed_pool_side after each block (the side map and the pooled tensor in one pass over the
+block's output), and one ca_hed_fuse (the five bilinear resizes, mean, sigmoid, quantisation -> the uint8 map and / or the control
+tensor the ControlNets hold).  No device-to-host read anywhere: the chain can be captured in a hipGraph.
+
+The specification is tests/hed_ref.py (the fp32 torch network and the numpy detector, restated from the published code).
+controlnet_aux and OpenCV are third-party packages that are absent here, and no ControlNetHED.pth is available: parity with them is
+UNPINNED.  In particular the fp16 range on the trained checkpoint is unmeasured -- the activations of a VGG fed 0..255 inputs can
+reach the thousands (fp16 overflows at 65504, and the MFMA accumulates in fp32 but stores fp16): `dtype=torch.bfloat16` is the
+escape.
+
+Scope of sizes: frames for which both of the detector's `resize_image` calls are the identity, min(H, W) == detect_resolution ==
+image_resolution with H and W multiples of 64 (512 x 512, 512 x 768: the sizes this project measures).  Anything else raises
+NotImplementedError: the INTER_AREA / INTER_LANCZOS4 resamplings of the detector are not rebuilt.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+
+try:
+    from PIL import Image
+except Exception:  # pragma: no cover
+    Image = None
+
+HED_BLOCKS = ((3, 64, 2), (64, 128, 2), (128, 256, 3), (256, 512, 3), (512, 512, 3))  # (in, out, layers) of block1 .. block5
+WEIGHTS_NAME = "ControlNetHED.pth"
+_CIN_PAD = 8  # ca_conv3x3 takes input channels in multiples of 8: the first convolution's weight is zero-padded, ca_hed_prep writes zeros
+
+
+def hed_key_shapes() -> dict:
+    """The 37 tensors of ControlNetHED.pth: name -> shape."""
+    out = {"norm": (1, 3, 1, 1)}
+    for b, (cin, cout, layers) in enumerate(HED_BLOCKS, start=1):
+        for i in range(layers):
+            out[f"block{b}.convs.{i}.weight"] = (cout, cin if i == 0 else cout, 3, 3)
+            out[f"block{b}.convs.{i}.bias"] = (cout,)
+        out[f"block{b}.projection.weight"] = (1, cout, 1, 1)
+        out[f"block{b}.projection.bias"] = (1,)
+    return out
+
+
+def check_state_dict(sd) -> None:
+    """KeyError naming a missing tensor, ValueError naming one that is unexpected or has the wrong shape."""
+    want = hed_key_shapes()
+    for k in want:
+        if k not in sd:
+            raise KeyError(f"HED state dict: '{k}' is missing ({len(want)} tensors expected: norm, block1..5.convs.*.weight|bias, block1..5.projection.weight|bias)")
+    for k in sd:
+        if k not in want:
+            raise ValueError(f"HED state dict: unexpected tensor '{k}'")
+    for k, shape in want.items():
+        if tuple(sd[k].shape) != shape:
+            raise ValueError(f"HED state dict: '{k}' has shape {tuple(sd[k].shape)}, expected {shape}")
+
+
+class HedAnnotator:
+    """`HedAnnotator(weights)(image)` has the contract of `annotators.canny(image)` (PIL RGB in, PIL RGB with three equal channels out;
+    an array in, an array out), so it plugs into `MultiControlNetResidualsPipeline(annotators={"hed": HedAnnotator.from_pretrained(path)})`,
+    whose `prep_control_images` then calls `annotate_batch` once per list of frames.  Nothing makes it a default: the weights are the
+    user's file.  Non-uint8 input raises TypeError, frames of different sizes ValueError, sizes out of scope NotImplementedError -- all
+    before the device is touched; without the library or a GPU a call raises CAHipUnavailable (there is no CPU fallback)."""
+
+    # the largest activation of a chunk of frames (block 1's output, 64 channels at full size) stays below what ca_conv3x3's kernels
+    # address with 32-bit byte offsets (conv_prepare: operands below 0x7FFFFF00 bytes keep every plan available)
+    max_activation_bytes = 0x7FFFFF00 - 1
+
+    def __init__(self, state_dict_or_path, device=None, dtype=None, detect_resolution: int = 512, image_resolution: int = 512):
+        import torch
+        dtype = torch.float16 if dtype is None else dtype
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise TypeError(f"dtype must be torch.float16 or torch.bfloat16, got {dtype}")
+        sd = self._load(state_dict_or_path) if isinstance(state_dict_or_path, (str, os.PathLike)) else state_dict_or_path
+        check_state_dict(sd)
+        self.device, self.dtype = device, dtype
+        self.detect_resolution, self.image_resolution = int(detect_resolution), int(image_resolution)
+        # packed once, on the host: [cout][3][3][cin] in `dtype` (cin zero-padded to 8 for the first), fp32 biases, projections as fp32 rows
+        self._host = {"norm": sd["norm"].detach().float().reshape(3).contiguous(), "blocks": []}
+        for b, (cin, cout, layers) in enumerate(HED_BLOCKS, start=1):
+            convs = []
+            for i in range(layers):
+                w = sd[f"block{b}.convs.{i}.weight"].detach().float().permute(0, 2, 3, 1)
+                if w.shape[3] % _CIN_PAD:
+                    w = torch.nn.functional.pad(w, (0, _CIN_PAD - w.shape[3] % _CIN_PAD))
+                convs.append((w.contiguous().to(dtype), sd[f"block{b}.convs.{i}.bias"].detach().float().contiguous()))
+            self._host["blocks"].append((convs, sd[f"block{b}.projection.weight"].detach().float().reshape(cout).contiguous(),
+                                         sd[f"block{b}.projection.bias"].detach().float().reshape(1).contiguous()))
+        self._dev = None
+        self._ws = {}
+        self.timings = None  # a dict: receives (start, end) torch events per launch under "prep", "conv", "pool_side", "fuse" -- tools/bench_hed.py
+
+    @staticmethod
+    def _load(path):
+        import torch
+        path = os.fspath(path)
+        if os.path.isdir(path):
+            path = os.path.join(path, WEIGHTS_NAME)
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"{path}: no such file (a local {WEIGHTS_NAME}, or a directory that holds it; nothing is ever downloaded)")
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        if not isinstance(sd, dict):
+            raise ValueError(f"{path}: not a state dict")
+        return sd
+
+    @classmethod
+    def from_pretrained(cls, path, **kwargs):
+        """path: a local ControlNetHED.pth or a directory that holds it (no network access, ever)."""
+        return cls(cls._load(path), **kwargs)
+
+    # ---- device state ----------------------------------------------------------------------------------------------------------
+    def _device(self):
+        import torch
+        from . import _capi
+        _capi.lib()  # CAHipUnavailable when the extension is not built
+        if not torch.cuda.is_available():
+            raise _capi.CAHipUnavailable("HedAnnotator needs a GPU (there is no CPU fallback)")
+        return torch.device(self.device if self.device is not None else "cuda")
+
+    def _weights(self, dev):
+        if self._dev is None or self._dev["norm"].device != dev:
+            self._dev = {"norm": self._host["norm"].to(dev),
+                         "blocks": [([(w.to(dev), b.to(dev)) for w, b in convs], pw.to(dev), pb.to(dev)) for convs, pw, pb in self._host["blocks"]]}
+        return self._dev
+
+    def chunk_frames(self, h: int, w: int) -> int:
+        """Frames per pass through the network: as many as keep block 1's output within max_activation_bytes."""
+        per_frame = h * w * 64 * 2
+        if per_frame > self.max_activation_bytes:
+            raise ValueError(f"a {h} x {w} frame alone exceeds what the convolutions address ({per_frame} > {self.max_activation_bytes} bytes)")
+        return self.max_activation_bytes // per_frame
+
+    def workspace(self, n: int, h: int, w: int):
+        """(two ping-pong activation buffers for a chunk of frames, the five float32 side maps [n, h >> k, w >> k]) of a call with n frames
+        of h x w pixels, cached per (n, h, w); contents are never assumed."""
+        import torch
+        key = (n, h, w)
+        if key not in self._ws:
+            dev = self._device()
+            elems = min(n, self.chunk_frames(h, w)) * h * w * 64
+            self._ws[key] = ([torch.empty(elems, dtype=self.dtype, device=dev) for _ in range(2)],
+                             [torch.empty((n, h >> k, w >> k), dtype=torch.float32, device=dev) for k in range(5)])
+        return self._ws[key]
+
+    def _stage(self, name):
+        import torch
+        if self.timings is None:
+            return None
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        self.timings.setdefault(name, []).append(ev)
+        ev[0].record()
+        return ev
+
+    # ---- input checks ----------------------------------------------------------------------------------------------------------
+    def _check_size(self, h: int, w: int) -> None:
+        if not (min(h, w) == self.detect_resolution == self.image_resolution and h % 64 == 0 and w % 64 == 0):
+            raise NotImplementedError(
+                f"HedAnnotator takes frames for which both resize_image calls of the detector are the identity: min(H, W) == detect_resolution == "
+                f"image_resolution and H % 64 == W % 64 == 0; got {h} x {w} with detect_resolution={self.detect_resolution}, "
+                f"image_resolution={self.image_resolution} (the INTER_AREA / INTER_LANCZOS4 resamplings are not rebuilt)")
+
+    def _frames(self, frames):
+        """-> uint8 device tensor [n, H, W, 3].  The type, size and scope checks come before the device is touched.  A PIL image is taken
+        as np.asarray gives it, so its mode must be L or RGB (a grey frame is repeated to three channels, as the detector's HWC3 does)."""
+        import torch
+        if isinstance(frames, torch.Tensor):
+            if frames.dtype != torch.uint8:
+                raise TypeError(f"frames must be uint8, got {frames.dtype}")
+            if frames.dim() == 3:
+                frames = frames[..., None]
+            if frames.dim() != 4 or frames.shape[3] not in (1, 3):
+                raise ValueError(f"frames tensor must be [n, H, W] or [n, H, W, C] with C = 1 or 3, got {tuple(frames.shape)}")
+            self._check_size(frames.shape[1], frames.shape[2])
+            dev = self._device()
+            if frames.shape[3] == 1:
+                frames = frames.expand(-1, -1, -1, 3)
+            return frames.to(dev).contiguous()
+        host = []
+        for fr in frames:
+            a = np.asarray(fr)
+            if a.dtype != np.uint8:
+                raise TypeError(f"frames must be uint8, got {a.dtype}")
+            if a.ndim == 2:
+                a = a[:, :, None]
+            if a.ndim != 3 or a.shape[2] not in (1, 3):
+                raise ValueError(f"a frame must be [H, W] or [H, W, C] with C = 1 or 3 (PIL mode L or RGB: convert RGBA or palette "
+                                 f"frames with .convert('RGB') first), got {a.shape}" + (f" from PIL mode {fr.mode}" if hasattr(fr, "mode") else ""))
+            host.append(a)
+        if not host:
+            raise ValueError("no frames")
+        if any(a.shape != host[0].shape for a in host):
+            raise ValueError("all frames of a call must share one size")
+        self._check_size(host[0].shape[0], host[0].shape[1])
+        dev = self._device()
+        stack = np.stack(host)
+        if stack.shape[3] == 1:
+            stack = np.repeat(stack, 3, axis=3)
+        return torch.from_numpy(stack).to(dev)
+
+    # ---- the chain -------------------------------------------------------------------------------------------------------------
+    def _network(self, src, bufs, sides, i0: int) -> None:
+        """The network for the frames `src` (a chunk), side maps into sides[k][i0 : i0 + len(src)]."""
+        from . import kernels as K
+        wts = self._weights(src.device)
+        n, h, w, _ = src.shape
+        cur, other = bufs
+
+        def view(buf, hh, ww, c):
+            return buf[: n * hh * ww * c].view(n, hh, ww, c)
+
+        ev = self._stage("prep")
+        x = K.hed_prep(src, wts["norm"], view(cur, h, w, _CIN_PAD))
+        if ev:
+            ev[1].record()
+        hh, ww = h, w
+        for k, (convs, pw, pb) in enumerate(wts["blocks"]):
+            for wt, bias in convs:
+                cur, other = other, cur
+                ev = self._stage("conv")
+                x = K.conv3x3(x, wt, bias=bias, act=K.ACT_RELU, out=view(cur, hh, ww, wt.shape[0]))
+                if ev:
+                    ev[1].record()
+            last = k == len(wts["blocks"]) - 1
+            pooled = None if last else view(other, hh // 2, ww // 2, x.shape[3])
+            ev = self._stage("pool_side")
+            K.hed_pool_side(x, pw, pb, sides[k][i0:i0 + n], pooled)
+            if ev:
+                ev[1].record()
+            if not last:
+                cur, other = other, cur
+                x, hh, ww = pooled, hh // 2, ww // 2
+
+    def _run(self, src, edges, control, rep):
+        from . import kernels as K
+        n, h, w, _ = src.shape
+        bufs, sides = self.workspace(n, h, w)
+        step = self.chunk_frames(h, w)
+        for i0 in range(0, n, step):
+            self._network(src[i0:i0 + step], bufs, sides, i0)
+        if edges is not None or control is not None:
+            ev = self._stage("fuse")
+            K.hed_fuse(sides, edges=edges, control=control, rep=rep)
+            if ev:
+                ev[1].record()
+        return sides
+
+    def side_maps(self, frames):
+        """-> the five float32 side maps [n, H >> k, W >> k] on the device (the logits before resize, mean and sigmoid), as new tensors."""
+        src = self._frames(frames)
+        return [s.clone() for s in self._run(src, None, None, 1)]
+
+    def edges(self, frames, out=None):
+        """frames: a list of PIL images / uint8 arrays of one size, or a uint8 tensor [n, H, W, C] (no host copy when it is on the
+        device) -> uint8 device tensor [n, H, W] (the detector's map, 0 .. 255), written into `out` when given."""
+        import torch
+        src = self._frames(frames)
+        n, h, w, _ = src.shape
+        if out is None:
+            out = torch.empty((n, h, w), dtype=torch.uint8, device=src.device)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w) or out.device != src.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint8 tensor {(n, h, w)} on {src.device}")
+        if n:
+            self._run(src, out, None, 1)
+        return out
+
+    def annotate_batch(self, frames, out=None, rep: int = 1, dtype=None):
+        """-> the control tensor [rep * n, 3, H, W] on the device, level / 255 with three equal channels; rep = 2 writes the n frames
+        twice (torch.cat([ctrl] * 2) of classifier-free guidance).  Written into `out` (and `out` returned) when given."""
+        import torch
+        if rep not in (1, 2):
+            raise ValueError(f"rep={rep} (1 or 2)")
+        want = out.dtype if out is not None and dtype is None else (dtype if dtype is not None else torch.float32)
+        if want not in (torch.float32, torch.float16):
+            raise TypeError(f"the control tensor is float32 or float16, got {want}")
+        src = self._frames(frames)
+        n, h, w, _ = src.shape
+        if out is None:
+            out = torch.empty((rep * n, 3, h, w), dtype=want, device=src.device)
+        elif tuple(out.shape) != (rep * n, 3, h, w) or out.device != src.device or not out.is_contiguous() or out.dtype != want:
+            raise ValueError(f"out must be a contiguous {want} tensor {(rep * n, 3, h, w)} on {src.device}")
+        if n:
+            self._run(src, None, out, rep)
+        return out
+
+    def __call__(self, image):
+        e = self.edges([image])[0].cpu().numpy()
+        rgb = np.repeat(e[:, :, None], 3, axis=2)
+        return Image.fromarray(rgb) if Image is not None and not isinstance(image, np.ndarray) else rgb

@@ -17,6 +17,7 @@ from ._capi import (AttnArgs, ConvArgs, ConvNarrowArgs, FfArgs, PerceiverAttnArg
 
 ACT_NONE, ACT_SILU = CA_ACT_NONE, CA_ACT_SILU
 ACT_QUICK_GELU, ACT_GELU = 2, 3  # CA_ACT_QUICK_GELU / CA_ACT_GELU (CLIP MLPs)
+ACT_RELU = _capi.CA_ACT_RELU     # the VGG stack of the HED annotator (hed.py)
 
 
 def dt_code(dtype: torch.dtype) -> int:
@@ -296,8 +297,10 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, *, x2: Optional[torch.Tensor] = No
             bias: Optional[torch.Tensor] = None, rowbias: Optional[torch.Tensor] = None,
             rows_per_group: int = 0, residual: Optional[torch.Tensor] = None, stride: int = 1,
             upsample: bool = False, alpha: float = 1.0, post_scale: float = 1.0, act: int = ACT_NONE,
-            out_f32: bool = False, pad_asym: bool = False, w_wino: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """x: [images, H, W, Cin1] (+x2 [.., Cin2]); w: [Cout, 3, 3, Cin1+Cin2]; returns NHWC.
+            out_f32: bool = False, pad_asym: bool = False, w_wino: Optional[torch.Tensor] = None,
+            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x: [images, H, W, Cin1] (+x2 [.., Cin2]); w: [Cout, 3, 3, Cin1+Cin2]; returns NHWC (written into `out` when given: a
+    contiguous tensor of the output's shape and dtype that overlaps no operand).
     pad_asym: pad (0 before, 1 after) instead of 1/1 -- diffusers Downsample2D(padding=0).
     w_wino: the weight once more in Winograd form [16, Cout, Cin] (layers.HipConv3x3._winograd_weight / ca_pack_w_wino): the library
     then runs the shapes it names as F(2x2, 3x3) (ca_conv_args.w_wino, ABI v12)."""
@@ -313,7 +316,12 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, *, x2: Optional[torch.Tensor] = No
     hl, wl = (hin * 2, win * 2) if upsample else (hin, win)
     pad = 1 if pad_asym else 2
     hout, wout = (hl + pad - 3) // stride + 1, (wl + pad - 3) // stride + 1
-    y = torch.empty((images, hout, wout, cout), device=x.device, dtype=torch.float32 if out_f32 else x.dtype)
+    if out is None:
+        y = torch.empty((images, hout, wout, cout), device=x.device, dtype=torch.float32 if out_f32 else x.dtype)
+    else:
+        _req_cuda(out)
+        assert tuple(out.shape) == (images, hout, wout, cout) and out.is_contiguous() and out.dtype == (torch.float32 if out_f32 else x.dtype)
+        y = out
     ld_res = 0
     if residual is not None:
         assert residual.dtype == x.dtype and residual.is_contiguous() and residual.numel() == images * hout * wout * cout, \
@@ -921,3 +929,49 @@ def canny_emit(images: int, h: int, w: int, ws: torch.Tensor, edges: Optional[to
         assert tuple(control.shape) == (rep * images, 3, h, w) and control.is_contiguous()
         dt = _CANNY_DT[control.dtype]
     check(lib().ca_canny_emit(images, h, w, _p(ws), _ws_bytes(ws), _p(edges), _p(control), int(rep), dt, _stream()), "ca_canny_emit")
+
+
+# ---- added to ABI v16: the stages of the HED annotator around its convolutions (controlanimate_amd/hed.py: HedAnnotator) -----------
+
+def hed_prep(frames: torch.Tensor, norm: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """uint8 RGB [images, H, W, 3] -> NHWC `out` [images, H, W, 8] fp16 / bf16: (float)frames - norm in channels 0..2, zeros in 3..7
+    (ca_hed_prep).  norm: float32 [3] on the device."""
+    _req_cuda(frames, norm, out)
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
+    n, h, w, _ = frames.shape
+    assert norm.dtype == torch.float32 and norm.numel() == 3 and norm.is_contiguous()
+    assert tuple(out.shape) == (n, h, w, 8) and out.is_contiguous()
+    check(lib().ca_hed_prep(_p(frames), _p(norm), _p(out), n, h, w, dt_code(out.dtype), _stream()), "ca_hed_prep")
+    return out
+
+
+def hed_pool_side(x: torch.Tensor, proj_w: torch.Tensor, proj_bias: torch.Tensor, side: torch.Tensor, pooled: Optional[torch.Tensor] = None) -> None:
+    """One pass over a block's output x [images, h, w, C]: side [images, h, w] float32 = proj_bias + x . proj_w (fp32 accumulation)
+    and, when `pooled` [images, h / 2, w / 2, C] is given, the 2x2 / stride-2 max pool (ca_hed_pool_side)."""
+    _req_cuda(x, proj_w, proj_bias, side, pooled)
+    assert x.dim() == 4 and x.is_contiguous()
+    n, h, w, c = x.shape
+    assert proj_w.dtype == torch.float32 and proj_w.numel() == c and proj_w.is_contiguous() and proj_bias.dtype == torch.float32 and proj_bias.numel() == 1
+    assert side.dtype == torch.float32 and tuple(side.shape) == (n, h, w) and side.is_contiguous()
+    if pooled is not None:
+        assert pooled.dtype == x.dtype and tuple(pooled.shape) == (n, h // 2, w // 2, c) and pooled.is_contiguous()
+    check(lib().ca_hed_pool_side(_p(x), _p(proj_w), _p(proj_bias), _p(side), _p(pooled), n, h, w, c, dt_code(x.dtype), _stream()), "ca_hed_pool_side")
+
+
+def hed_fuse(sides, edges: Optional[torch.Tensor] = None, control: Optional[torch.Tensor] = None, rep: int = 1) -> None:
+    """The five float32 side maps [images, H >> k, W >> k] -> the uint8 edge map [images, H, W] and / or the control tensor
+    [rep * images, 3, H, W] (float32 / float16, level / 255): bilinear resize, mean, sigmoid and quantisation in one launch (ca_hed_fuse)."""
+    assert len(sides) == 5
+    _req_cuda(*sides, edges, control)
+    n, h, w = sides[0].shape
+    for k, s in enumerate(sides):
+        assert s.dtype == torch.float32 and s.is_contiguous() and tuple(s.shape) == (n, h >> k, w >> k), f"side map {k}: {tuple(s.shape)} {s.dtype}"
+    if edges is not None:
+        assert edges.dtype == torch.uint8 and tuple(edges.shape) == (n, h, w) and edges.is_contiguous()
+    dt = _capi.CA_F32
+    if control is not None:
+        if control.dtype not in _CANNY_DT:
+            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
+        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
+        dt = _CANNY_DT[control.dtype]
+    check(lib().ca_hed_fuse(*[_p(s) for s in sides], n, h, w, _p(edges), _p(control), int(rep), dt, _stream()), "ca_hed_fuse")

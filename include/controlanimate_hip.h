@@ -31,7 +31,7 @@ extern "C" {
 /* element types */
 #define CA_BF16 0
 #define CA_F16 1
-#define CA_F32 2 /* output of ca_canny_emit only (ABI v16) */
+#define CA_F32 2 /* control tensor of ca_canny_emit / ca_hed_fuse only (ABI v16) */
 
 /* error codes */
 #define CA_OK 0
@@ -44,6 +44,7 @@ extern "C" {
 #define CA_ACT_SILU 1
 #define CA_ACT_QUICK_GELU 2 /* x * sigmoid(1.702 x): CLIP ViT-L text/vision MLPs */
 #define CA_ACT_GELU 3       /* erf GELU: CLIP ViT-H vision MLP (IP-Adapter image encoder) */
+#define CA_ACT_RELU 4       /* max(x, 0): the VGG stack of the HED annotator (added to ABI v16) */
 
 int ca_abi_version(void);
 const char* ca_last_error(void);
@@ -728,6 +729,38 @@ typedef struct ca_perceiver_attn_args {
   int32_t dtype;
 } ca_perceiver_attn_args;
 int ca_perceiver_attn(const ca_perceiver_attn_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * The HED edge annotator (added to ABI v16: no struct or existing function changes, the number stays).  The reference's sample
+ * config annotates every frame with controlnet_aux's HEDdetector (modules/controlresiduals_pipeline.py:58, 116-117): a VGG-style
+ * stack of thirteen 3x3 convolutions with ReLU in five blocks, a 1x1 projection to a one-channel side map per block, a 2x2 max
+ * pool between blocks; the side maps are resized to the frame with cv2.resize(INTER_LINEAR), averaged, and squashed by a sigmoid.
+ * The convolutions are ca_conv3x3 with act = CA_ACT_RELU; the three entry points below are the stages around them
+ * (controlanimate_amd/hed.py: HedAnnotator; the specification is tests/hed_ref.py).  Every launch is a function of its arguments
+ * alone, with no device-to-host read: the chain can be captured in a hipGraph.  Anything outside the stated ranges is
+ * CA_ERR_INVALID_ARG before any launch.  images * h * w < 2^31 everywhere.
+ * ------------------------------------------------------------------------------------ */
+
+/* dst [images, h, w, 8] of dtype (CA_F16 / CA_BF16, 16-byte aligned): channel c < 3 = (float)src[.., c] - norm[c] in fp32, rounded
+ * once to dtype; channels 3 .. 7 = 0 (the first convolution's weight is zero-padded to cin = 8).  src uint8 RGB [images, h, w, 3],
+ * norm fp32 [3] on the device. */
+int ca_hed_prep(const uint8_t* src, const float* norm, void* dst, int32_t images, int32_t h, int32_t w, int32_t dtype, void* stream);
+
+/* One pass over a block's output x [images, h, w, c] (dtype CA_F16 / CA_BF16; c a multiple of 8 in 64 .. 512; h and w even):
+ * side [images, h, w] fp32 = proj_bias[0] + sum_c x[p, c] * proj_w[c], accumulated in fp32 (proj_w fp32 [c], proj_bias fp32 [1],
+ * both on the device), and, when pooled is not NULL, pooled [images, h / 2, w / 2, c] = the 2x2 / stride-2 maximum.  x, pooled and
+ * proj_w 16-byte aligned, side 8-byte aligned.  The sum's order is fixed: two runs give the same bits. */
+int ca_hed_pool_side(const void* x, const float* proj_w, const float* proj_bias, float* side, void* pooled, int32_t images, int32_t h,
+                     int32_t w, int32_t c, int32_t dtype, void* stream);
+
+/* The five side maps (side_k fp32 [images, h >> k, w >> k]; h and w multiples of 16) -> per output pixel: each map sampled as
+ * cv2.resize(INTER_LINEAR) to (h, w) samples float32 (f = (d + 0.5) * src / dst - 0.5, s = floor(f), f -= s; s < 0: s = 0, f = 0;
+ * s >= src - 1: s = src - 1, f = 0; weights 1 - f and f in fp32, columns combined first, then rows, every product and sum rounded),
+ * the fp32 mean (sum k = 0 .. 4, divided by 5), 1 / (1 + exp(-mean)) in float64, x 255, truncated to uint8.  Writes either or both
+ * of: edges, uint8 [images, h, w] (4-byte aligned); control, [rep * images, 3, h, w] of control_dtype (CA_F16 or CA_F32, aligned
+ * to four elements) with level / 255, the three channels equal and, with rep = 2, the frames written twice (as ca_canny_emit). */
+int ca_hed_fuse(const float* side0, const float* side1, const float* side2, const float* side3, const float* side4, int32_t images,
+                int32_t h, int32_t w, uint8_t* edges, void* control, int32_t rep, int32_t control_dtype, void* stream);
 
 #ifdef __cplusplus
 }
