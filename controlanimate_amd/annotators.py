@@ -8,8 +8,10 @@ weak > low connected through the 8-neighbourhood).  OpenCV is a THIRD-PARTY depe
 this restatement is UNPINNED (no cv2 output to compare with); tests check the algorithmic properties.
 Of the learned detectors (controlnet_aux / transformers models, :56-61) HED, the sample config's, is rebuilt: `HedAnnotator` (hed.py,
 re-exported here) runs ControlNetHED for a whole window on the GPU from a local ControlNetHED.pth, opt-in through
-`annotators={"hed": HedAnnotator.from_pretrained(path)}`.  The others (openpose, lineart, mlsd, depth) are not rebuilt: plug them in
-through `MultiControlNetResidualsPipeline(annotators={...})`.
+`annotators={"hed": HedAnnotator.from_pretrained(path)}`.  So is lineart, the IP-Adapter sample config's: `LineartAnnotator`
+(lineart.py, re-exported here) runs the "informative drawings" generator of controlnet_aux's LineartDetector from a local
+sk_model.pth / sk_model2.pth, opt-in through `annotators={"lineart": LineartAnnotator.from_pretrained(path)}`.  The others (openpose,
+lineart_anime, mlsd, depth) are not rebuilt: plug them in through `MultiControlNetResidualsPipeline(annotators={...})`.
 
 `CannyAnnotator` is the same function for a whole window of frames on the GPU (ABI v16, csrc/ca_canny.hip): opt-in through
 `annotators={"canny": CannyAnnotator(device)}`; `canny` stays the default.  `canny_edges` is its specification: the device result
@@ -25,6 +27,7 @@ except Exception:  # pragma: no cover
     Image = None
 
 from .hed import HedAnnotator  # noqa: E402,F401  (the learned HED detector on the GPU; torch is imported when it is used)
+from .lineart import LineartAnnotator  # noqa: E402,F401  (the learned lineart detector on the GPU, likewise)
 
 
 def _sobel(ch: np.ndarray):

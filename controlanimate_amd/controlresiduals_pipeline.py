@@ -12,9 +12,12 @@ Same call surface as the reference's modules/controlresiduals_pipeline.py:
 The returned residuals are [b,C,f,h,w] VIEWS of channels-last storage, which the UNet consumes
 without a copy (unet.py `_to_nhwc`).  Annotators (reference :97-150): canny is built in
 (controlanimate_amd/annotators.py, a numpy restatement of cv2.Canny(img, 100, 200)); HED, the sample config's detector, runs on
-the GPU from the user's ControlNetHED.pth through `annotators={"hed": HedAnnotator.from_pretrained(path)}` (controlanimate_amd/hed.py);
-the other learned detectors (openpose / lineart / mlsd / depth) are third-party models outside the loop and are NOT rebuilt: pass
-already-annotated control images, or plug callables in through `annotators`.
+the GPU from the user's ControlNetHED.pth through `annotators={"hed": HedAnnotator.from_pretrained(path)}` (controlanimate_amd/hed.py),
+and lineart, the IP-Adapter sample config's, from the user's sk_model.pth through `annotators={"lineart":
+LineartAnnotator.from_pretrained(path)}` (controlanimate_amd/lineart.py); the other learned detectors (openpose / lineart_anime / mlsd /
+depth) are third-party models outside the loop and are NOT rebuilt: pass already-annotated control images, or plug callables in
+through `annotators`.  Of the keys contained in a ControlNet's name the longest wins (the reference tests `lineart_anime` before
+`lineart`): a `lineart` annotator never serves a `lineart_anime` net.
 """
 from __future__ import annotations
 
@@ -79,23 +82,30 @@ class MultiControlNetResidualsPipeline:
         self.lanes_used = 0  # HIP streams the ControlNet bodies of the last residuals_nhwc_async call were spread over
 
     # ------------------------------------------------------------------------------------------
+    def _annotator_for(self, controlnet_model: str):
+        """The annotator whose key is contained in the name; of several the longest key wins, the first of equal length (with one
+        matching key: that one, as ever).  The key `lineart` is no candidate for a name that contains `lineart_anime`, a different
+        detector (the reference tests `lineart_anime` first, controlresiduals_pipeline.py:125-134); other contained keys still are."""
+        best = None
+        for key, fn in self.annotators.items():
+            if key == "lineart" and "lineart_anime" in controlnet_model:
+                continue
+            if key in controlnet_model and (best is None or len(key) > len(best[0])):
+                best = (key, fn)
+        return None if best is None else best[1]
+
     def prepare_controlnet_input_image(self, controlnet_model: str, image):
         if isinstance(image, torch.Tensor):
             return image  # tensors are control images that are already annotated / preprocessed
-        for key, fn in self.annotators.items():
-            if key in controlnet_model:
-                return fn(image)
-        return image  # already annotated
+        fn = self._annotator_for(controlnet_model)
+        return fn(image) if fn is not None else image  # no annotator: already annotated
 
     def _batch_annotator(self, controlnet_model: str, src):
         """annotate_batch of the annotator that `prepare_controlnet_input_image` would call per frame, when it has one and `src` is a
         non-empty list of frames that are not tensors; else None (the per-frame path)."""
         if not isinstance(src, (list, tuple)) or not src or any(isinstance(im, torch.Tensor) for im in src):
             return None
-        for key, fn in self.annotators.items():
-            if key in controlnet_model:
-                return getattr(fn, "annotate_batch", None)
-        return None
+        return getattr(self._annotator_for(controlnet_model), "annotate_batch", None)
 
     def prep_control_images(self, images, control_image_processor=None, epoch=0, output_dir="tmp/output",
                             save_outputs=False, do_classifier_free_guidance=True, guess_mode=False):

@@ -975,3 +975,93 @@ def hed_fuse(sides, edges: Optional[torch.Tensor] = None, control: Optional[torc
         assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
         dt = _CANNY_DT[control.dtype]
     check(lib().ca_hed_fuse(*[_p(s) for s in sides], n, h, w, _p(edges), _p(control), int(rep), dt, _stream()), "ca_hed_fuse")
+
+
+# ---- added to ABI v16: the lineart annotator's stages beside conv3x3 / gemm (controlanimate_amd/lineart.py: LineartAnnotator) -----------
+
+def lineart_conv_in(frames: torch.Tensor, w_packed: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """uint8 RGB [images, H, W, 3] -> `out` [images, H, W, 64] fp16 / bf16: the 7x7 convolution behind reflection padding 3 of
+    frames / 255, without bias (ca_lineart_conv_in).  w_packed: [64, 160] of out's dtype (lineart.pack_conv_in)."""
+    _req_cuda(frames, w_packed, out)
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
+    n, h, w, _ = frames.shape
+    assert tuple(w_packed.shape) == (64, 160) and w_packed.is_contiguous() and w_packed.dtype == out.dtype
+    assert tuple(out.shape) == (n, h, w, 64) and out.is_contiguous()
+    check(lib().ca_lineart_conv_in(_p(frames), _p(w_packed), _p(out), n, h, w, dt_code(out.dtype), _stream()), "ca_lineart_conv_in")
+    return out
+
+
+def instance_norm(x: torch.Tensor, *, relu: bool = False, residual: Optional[torch.Tensor] = None, in_ring: bool = False, res_ring: bool = False,
+                  out_pad: bool = False, eps: float = 1e-5, out: Optional[torch.Tensor] = None, partials: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """InstanceNorm2d(affine=False) of NHWC x per (image, channel), then optional ReLU, then optional residual add (ca_instnorm_stats +
+    ca_instnorm_apply).  in_ring / res_ring: that operand is stored as [images, H + 2, W + 2, C] and its outermost pixels are ignored.
+    out_pad: the result is written as [images, H + 2, W + 2, C], padded by reflection of one pixel.  C is 64, 128 or 256."""
+    _req_cuda(x, residual, out, partials)
+    assert x.dim() == 4 and x.is_contiguous()
+    n, hs, ws, c = x.shape
+    h, w = (hs - 2, ws - 2) if in_ring else (hs, ws)
+    if residual is not None:
+        assert residual.dtype == x.dtype and residual.is_contiguous() and tuple(residual.shape) == ((n, h + 2, w + 2, c) if res_ring else (n, h, w, c))
+    oshape = (n, h + 2, w + 2, c) if out_pad else (n, h, w, c)
+    if out is None:
+        out = torch.empty(oshape, dtype=x.dtype, device=x.device)
+    assert tuple(out.shape) == oshape and out.is_contiguous() and out.dtype == x.dtype and out.data_ptr() != x.data_ptr()
+    floats = int(lib().ca_instnorm_partials_floats(n, h, w, c))
+    if floats <= 0:
+        raise _capi.CAHipError(f"ca_instnorm: images={n} h={h} w={w} c={c} is out of range (c is 64, 128 or 256)")
+    if partials is None:
+        partials = torch.empty(floats, dtype=torch.float32, device=x.device)
+    assert partials.dtype == torch.float32 and partials.is_contiguous() and partials.numel() >= floats
+    dt = dt_code(x.dtype)
+    check(lib().ca_instnorm_stats(_p(x), _p(partials), n, h, w, c, int(in_ring), dt, _stream()), "ca_instnorm_stats")
+    check(lib().ca_instnorm_apply(_p(x), _p(partials), _p(residual), _p(out), n, h, w, c, int(in_ring), int(res_ring), int(out_pad), int(relu),
+                                  float(eps), dt, _stream()), "ca_instnorm_apply")
+    return out
+
+
+def conv_transpose3x3s2(x: torch.Tensor, w_taps: torch.Tensor, *, taps: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ConvTranspose2d(Cin, Cout, 3, stride=2, padding=1, output_padding=1) without bias: x [images, H, W, Cin] -> [images, 2H, 2W, Cout].
+    One gemm with N = 9 * Cout (w_taps [3, 3, Cout, Cin]: lineart.pack_convt_phases) into `taps`, then ca_convt3x3s2_gather."""
+    _req_cuda(x, w_taps, taps, out)
+    assert x.dim() == 4 and x.is_contiguous() and w_taps.dim() == 4 and w_taps.is_contiguous() and w_taps.dtype == x.dtype
+    n, h, w, cin = x.shape
+    cout = w_taps.shape[2]
+    assert tuple(w_taps.shape) == (3, 3, cout, cin)
+    if taps is None:
+        taps = torch.empty((n * h * w, 9 * cout), dtype=x.dtype, device=x.device)
+    assert tuple(taps.shape) == (n * h * w, 9 * cout) and taps.is_contiguous() and taps.dtype == x.dtype
+    if out is None:
+        out = torch.empty((n, 2 * h, 2 * w, cout), dtype=x.dtype, device=x.device)
+    assert tuple(out.shape) == (n, 2 * h, 2 * w, cout) and out.is_contiguous() and out.dtype == x.dtype
+    gemm(x.view(n * h * w, cin), w_taps.view(9 * cout, cin), out=taps)
+    check(lib().ca_convt3x3s2_gather(_p(taps), _p(out), n, h, w, cout, dt_code(x.dtype), _stream()), "ca_convt3x3s2_gather")
+    return out
+
+
+def lineart_conv_out(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
+    """x [images, H, W, 64] -> `logits` float32 [images, H, W]: the 7x7 convolution to one channel behind reflection padding 3
+    (ca_lineart_conv_out).  wt: float32 [7, 7, 64]; bias: float32 [1]."""
+    _req_cuda(x, wt, bias, logits)
+    assert x.dim() == 4 and x.shape[3] == 64 and x.is_contiguous()
+    n, h, w, _ = x.shape
+    assert wt.dtype == torch.float32 and tuple(wt.shape) == (7, 7, 64) and wt.is_contiguous() and bias.dtype == torch.float32 and bias.numel() == 1
+    assert logits.dtype == torch.float32 and tuple(logits.shape) == (n, h, w) and logits.is_contiguous()
+    check(lib().ca_lineart_conv_out(_p(x), _p(wt), _p(bias), _p(logits), n, h, w, dt_code(x.dtype), _stream()), "ca_lineart_conv_out")
+    return logits
+
+
+def lineart_finish(logits: torch.Tensor, edges: Optional[torch.Tensor] = None, control: Optional[torch.Tensor] = None, rep: int = 1) -> None:
+    """float32 logits [images, H, W] -> the uint8 map 255 - trunc(sigmoid * 255) [images, H, W] and / or the control tensor
+    [rep * images, 3, H, W] (float32 / float16, map / 255) in one launch (ca_lineart_finish)."""
+    _req_cuda(logits, edges, control)
+    assert logits.dtype == torch.float32 and logits.dim() == 3 and logits.is_contiguous()
+    n, h, w = logits.shape
+    if edges is not None:
+        assert edges.dtype == torch.uint8 and tuple(edges.shape) == (n, h, w) and edges.is_contiguous()
+    dt = _capi.CA_F32
+    if control is not None:
+        if control.dtype not in _CANNY_DT:
+            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
+        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
+        dt = _CANNY_DT[control.dtype]
+    check(lib().ca_lineart_finish(_p(logits), n, h, w, _p(edges), _p(control), int(rep), dt, _stream()), "ca_lineart_finish")

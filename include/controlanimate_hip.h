@@ -762,6 +762,58 @@ int ca_hed_pool_side(const void* x, const float* proj_w, const float* proj_bias,
 int ca_hed_fuse(const float* side0, const float* side1, const float* side2, const float* side3, const float* side4, int32_t images,
                 int32_t h, int32_t w, uint8_t* edges, void* control, int32_t rep, int32_t control_dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * The lineart annotator (added to ABI v16: no struct or existing function changes, the number stays).  The reference's
+ * SampleConfigIPAdapter.yaml annotates frames for control_v11p_sd15_lineart with controlnet_aux's LineartDetector
+ * (modules/controlresiduals_pipeline.py:60, 125-129): the "informative drawings" Generator -- a 7x7 convolution behind reflection
+ * padding, two stride-2 convolutions, three residual blocks of reflection-padded 3x3 convolutions, two transposed convolutions, a
+ * 7x7 convolution to one channel and a sigmoid, with a non-affine InstanceNorm after every convolution but the last.  The stride-2
+ * and residual-block convolutions are the 3x3 convolution entry point above; the entry points below are the rest
+ * (controlanimate_amd/lineart.py: LineartAnnotator; the specification is tests/lineart_ref.py).  Tensors are NHWC, CA_F16 or CA_BF16.
+ * Every launch is a function of its arguments alone, with no device-to-host read and no atomics: the chain can be captured in a
+ * hipGraph and two runs give the same bits.  Anything outside the stated ranges is CA_ERR_INVALID_ARG before any launch.
+ * ------------------------------------------------------------------------------------ */
+
+/* dst [images, h, w, 64] = Conv2d(3, 64, 7)(ReflectionPad2d(3)(src / 255)) without its bias (a bias in front of a non-affine
+ * InstanceNorm cancels).  src uint8 RGB [images, h, w, 3]; w_packed [64][160] of dtype: column ky * 21 + kx * 3 + c holds
+ * weight[o][c][ky][kx], columns 147 .. 159 zero.  The sum over the bytes runs in fp32 (MFMA), is divided by 255 and rounded once.
+ * h, w >= 4; images * h * w < 2^31; w_packed and dst 16-byte aligned. */
+int ca_lineart_conv_in(const uint8_t* src, const void* w_packed, void* dst, int32_t images, int32_t h, int32_t w, int32_t dtype, void* stream);
+
+/* InstanceNorm2d(affine = False) over h x w per (image, channel), biased variance.  x is [images, h, w, c], or, with in_ring = 1,
+ * [images, h + 2, w + 2, c] whose outermost pixels are ignored; c is 64, 128 or 256; images * (h + 2) * (w + 2) < 2^31.  The
+ * statistics pass writes fp32 partial sums (of x minus the image's first pixel, per chunk of pixels) into `partials`, which holds
+ * the number of floats the first function returns (0 for arguments out of range); the apply pass adds them in a fixed order and
+ * writes y = relu?((x - mean) / sqrt(var + eps)) + residual?, rounded once.  residual (may be NULL) has x's shape, stored with a
+ * ring when res_ring = 1.  With out_pad = 1 y is [images, h + 2, w + 2, c], the result padded by reflection of one pixel
+ * (h, w >= 2; the ring is bit-equal to the mirrored interior); else [images, h, w, c].  x, residual and y 16-byte aligned; y must
+ * not overlap x or residual. */
+int64_t ca_instnorm_partials_floats(int32_t images, int32_t h, int32_t w, int32_t c);
+int ca_instnorm_stats(const void* x, float* partials, int32_t images, int32_t h, int32_t w, int32_t c, int32_t in_ring, int32_t dtype, void* stream);
+int ca_instnorm_apply(const void* x, const float* partials, const void* residual, void* y, int32_t images, int32_t h, int32_t w, int32_t c,
+                      int32_t in_ring, int32_t res_ring, int32_t out_pad, int32_t relu, float eps, int32_t dtype, void* stream);
+
+/* The second half of ConvTranspose2d(cin, cout, 3, stride = 2, padding = 1, output_padding = 1) without bias.  The first half is one
+ * GEMM: taps [images * h * w, 9 * cout] = x [images * h * w, cin] times the weight packed as [ky][kx][cout][cin].  This gathers
+ * y [images, 2 h, 2 w, cout]: with T(i, j, ky, kx) the cout values of tap (ky, kx) of input pixel (i, j), zero outside the image,
+ *   y[2i, 2j] = T(i,j,1,1)                          y[2i, 2j+1] = T(i,j,1,2) + T(i,j+1,1,0)
+ *   y[2i+1, 2j] = T(i,j,2,1) + T(i+1,j,0,1)         y[2i+1, 2j+1] = T(i,j,2,2) + T(i,j+1,2,0) + T(i+1,j,0,2) + T(i+1,j+1,0,0)
+ * added in fp32 in this order and rounded once.  cout a multiple of 8 up to 1024; images * 2 h * 2 w < 2^31; both 16-byte aligned. */
+int ca_convt3x3s2_gather(const void* taps, void* y, int32_t images, int32_t h, int32_t w, int32_t cout, int32_t dtype, void* stream);
+
+/* logits [images, h, w] fp32 = Conv2d(64, 1, 7)(ReflectionPad2d(3)(x)), x [images, h, w, 64] of dtype; wt fp32 [7][7][64]
+ * (weight[0][c][ky][kx] at [ky][kx][c]) and bias fp32 [1] on the device; fp32 accumulation in a fixed order.  h, w >= 4;
+ * images * h * w < 2^31; x 16-byte aligned. */
+int ca_lineart_conv_out(const void* x, const float* wt, const float* bias, float* logits, int32_t images, int32_t h, int32_t w, int32_t dtype,
+                        void* stream);
+
+/* Per pixel: level = 255 - trunc(clip(sigmoid(logit) * 255, 0, 255)), the sigmoid in float64.  Writes either or both of: map, uint8
+ * [images, h, w] (4-byte aligned); control, [rep * images, 3, h, w] of control_dtype (CA_F16 or CA_F32, aligned to four elements)
+ * with level / 255, the three channels equal and, with rep = 2, the frames written twice (the contract of the HED fuse above).
+ * h * w a multiple of 4; logits 16-byte aligned. */
+int ca_lineart_finish(const float* logits, int32_t images, int32_t h, int32_t w, uint8_t* map, void* control, int32_t rep, int32_t control_dtype,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
