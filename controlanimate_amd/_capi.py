@@ -15,6 +15,8 @@ CA_BF16, CA_F16 = 0, 1
 CA_F32 = 2  # control tensor of ca_canny_emit / ca_hed_fuse only
 CA_ACT_NONE, CA_ACT_SILU = 0, 1
 CA_ACT_RELU = 4  # the VGG stack of the HED annotator (hed.py)
+CA_ACT_RELU6 = 5  # the MobileNetV2 backbone of the M-LSD annotator (mlsd.py)
+CA_MLSD_TOPK = 200
 ABI_VERSION = 16
 
 
@@ -251,6 +253,14 @@ SYMBOLS = {
     "ca_convt3x3s2_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ca_lineart_conv_out": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ca_lineart_finish": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    # added to ABI v16 likewise: the M-LSD annotator's stages beside ca_conv3x3 / ca_gemm / ca_add_bcast (controlanimate_amd/mlsd.py)
+    "ca_mlsd_prep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ca_dwconv3x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ca_upsample2x_bilinear_ac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "ca_conv3x3_dil": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ca_mlsd_decode_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "ca_mlsd_decode": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ca_mlsd_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
 }
 
 _lib = None

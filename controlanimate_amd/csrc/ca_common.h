@@ -175,6 +175,7 @@ __device__ __forceinline__ float act_f(float x, int act) {
   if (act == CA_ACT_QUICK_GELU) return x * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * x));
   if (act == CA_ACT_GELU) return gelu_erf_f(x);
   if (act == CA_ACT_RELU) return fmaxf(x, 0.0f);
+  if (act == CA_ACT_RELU6) return fminf(fmaxf(x, 0.0f), 6.0f);
   return x;
 }
 

@@ -18,6 +18,7 @@ from ._capi import (AttnArgs, ConvArgs, ConvNarrowArgs, FfArgs, PerceiverAttnArg
 ACT_NONE, ACT_SILU = CA_ACT_NONE, CA_ACT_SILU
 ACT_QUICK_GELU, ACT_GELU = 2, 3  # CA_ACT_QUICK_GELU / CA_ACT_GELU (CLIP MLPs)
 ACT_RELU = _capi.CA_ACT_RELU     # the VGG stack of the HED annotator (hed.py)
+ACT_RELU6 = _capi.CA_ACT_RELU6   # the MobileNetV2 backbone of the M-LSD annotator (mlsd.py)
 
 
 def dt_code(dtype: torch.dtype) -> int:
@@ -1065,3 +1066,107 @@ def lineart_finish(logits: torch.Tensor, edges: Optional[torch.Tensor] = None, c
         assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
         dt = _CANNY_DT[control.dtype]
     check(lib().ca_lineart_finish(_p(logits), n, h, w, _p(edges), _p(control), int(rep), dt, _stream()), "ca_lineart_finish")
+
+
+# ---- added to ABI v16: the M-LSD annotator's stages beside conv3x3 / gemm / add_bcast (controlanimate_amd/mlsd.py: MlsdAnnotator) -----------
+MLSD_TOPK = _capi.CA_MLSD_TOPK
+
+
+def mlsd_prep(frames: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """uint8 RGB [images, H, W, 3] -> NHWC `out` [images, H, W, 8] fp16 / bf16: frames / 127.5 - 1 in channels 0..2, 1 / 127.5 - 1 in
+    channel 3 (the detector's channel of ones), zeros in 4..7 (ca_mlsd_prep)."""
+    _req_cuda(frames, out)
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
+    n, h, w, _ = frames.shape
+    assert tuple(out.shape) == (n, h, w, 8) and out.is_contiguous()
+    check(lib().ca_mlsd_prep(_p(frames), _p(out), n, h, w, dt_code(out.dtype), _stream()), "ca_mlsd_prep")
+    return out
+
+
+def dwconv3x3(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, stride: int = 1, relu6: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Depthwise 3x3 convolution of NHWC x [images, H, W, C] (ca_dwconv3x3).  w: [9, C] of x's dtype (tap ky * 3 + kx of every channel:
+    mlsd.pack_depthwise), bias float32 [C].  stride 1: padding 1; stride 2: F.pad(x, (0, 1, 0, 1)) and padding 0, even H and W."""
+    _req_cuda(x, w, bias, out)
+    assert x.dim() == 4 and x.is_contiguous()
+    n, h, ww, c = x.shape
+    assert tuple(w.shape) == (9, c) and w.is_contiguous() and w.dtype == x.dtype and bias.dtype == torch.float32 and bias.numel() == c and bias.is_contiguous()
+    oshape = (n, h // stride, ww // stride, c) if stride in (1, 2) else None
+    if out is None and oshape is not None:
+        out = torch.empty(oshape, dtype=x.dtype, device=x.device)
+    assert oshape is None or (tuple(out.shape) == oshape and out.is_contiguous() and out.dtype == x.dtype and out.data_ptr() != x.data_ptr())
+    check(lib().ca_dwconv3x3(_p(x), _p(w), _p(bias), _p(out), n, h, ww, c, int(stride), int(relu6), dt_code(x.dtype), _stream()), "ca_dwconv3x3")
+    return out
+
+
+def upsample2x_bilinear_ac(x: torch.Tensor, out: torch.Tensor, col0: int = 0) -> torch.Tensor:
+    """F.interpolate(scale_factor=2, mode="bilinear", align_corners=True) of NHWC x [images, h, w, C] into channels col0 .. col0 + C - 1 of
+    `out` [images, 2h, 2w, ld]; the other channels of `out` are left as they are (ca_upsample2x_bilinear_ac)."""
+    _req_cuda(x, out)
+    assert x.dim() == 4 and x.is_contiguous() and out.dim() == 4 and out.is_contiguous() and out.dtype == x.dtype
+    n, h, w, c = x.shape
+    assert tuple(out.shape[:3]) == (n, 2 * h, 2 * w)
+    check(lib().ca_upsample2x_bilinear_ac(_p(x), _p(out), n, h, w, c, out.shape[3], int(col0), dt_code(x.dtype), _stream()), "ca_upsample2x_bilinear_ac")
+    return out
+
+
+def conv3x3_dil(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, dilation: int = 5, relu: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Conv2d(64, 64, 3, dilation=5, padding=5) + bias (+ ReLU) of NHWC x [images, H, W, 64] on the MFMA (ca_conv3x3_dil).
+    w: [64, 3, 3, 64] of x's dtype (the layout conv3x3 takes), bias float32 [64]."""
+    _req_cuda(x, w, bias, out)
+    assert x.dim() == 4 and x.is_contiguous() and w.is_contiguous() and w.dtype == x.dtype
+    n, h, ww, c = x.shape
+    assert tuple(w.shape) == (c, 3, 3, c) and bias.dtype == torch.float32 and bias.numel() == c and bias.is_contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    assert tuple(out.shape) == tuple(x.shape) and out.is_contiguous() and out.dtype == x.dtype
+    check(lib().ca_conv3x3_dil(_p(x), _p(w), _p(bias), _p(out), n, h, ww, c, int(dilation), int(relu), dt_code(x.dtype), _stream()), "ca_conv3x3_dil")
+    return out
+
+
+def mlsd_decode_workspace_bytes(images: int, h: int, w: int) -> int:
+    n = int(lib().ca_mlsd_decode_workspace_bytes(images, h, w))
+    if n <= 0:
+        raise _capi.CAHipError(f"ca_mlsd_decode_workspace_bytes: images={images} h={h} w={w} is out of range")
+    return n
+
+
+def mlsd_decode(tp: torch.Tensor, thr_v: float = 0.1, thr_d: float = 0.1, *, segments: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
+                ws: Optional[torch.Tensor] = None):
+    """tp float32 [images, h, w, 8] (channel 0 the centre logit, 1..4 the displacements) -> (segments int32 [images, 200, 4] at full
+    resolution in rank order, count int32 [images]): sigmoid, plateau-keeping 3x3 maximum test, exact top 200, distance test, float64
+    endpoints in one launch, no host read (ca_mlsd_decode)."""
+    _req_cuda(tp, segments, count, ws)
+    assert tp.dtype == torch.float32 and tp.dim() == 4 and tp.shape[3] == 8 and tp.is_contiguous()
+    n, h, w, _ = tp.shape
+    if segments is None:
+        segments = torch.empty((n, MLSD_TOPK, 4), dtype=torch.int32, device=tp.device)
+    if count is None:
+        count = torch.empty((n,), dtype=torch.int32, device=tp.device)
+    assert segments.dtype == torch.int32 and tuple(segments.shape) == (n, MLSD_TOPK, 4) and segments.is_contiguous()
+    assert count.dtype == torch.int32 and tuple(count.shape) == (n,) and count.is_contiguous()
+    if ws is None:
+        ws = torch.empty(mlsd_decode_workspace_bytes(n, h, w), dtype=torch.uint8, device=tp.device)
+    check(lib().ca_mlsd_decode(_p(tp), n, h, w, float(thr_v), float(thr_d), _p(ws), _ws_bytes(ws), _p(segments), _p(count), _stream()), "ca_mlsd_decode")
+    return segments, count
+
+
+def mlsd_draw(segments: torch.Tensor, count: torch.Tensor, h: int, w: int, edges: Optional[torch.Tensor] = None, control: Optional[torch.Tensor] = None,
+              rep: int = 1) -> torch.Tensor:
+    """cv2.line(map, (xs, ys), (xe, ye), 255, 1) of the first count[i] segments of every image on a zeroed uint8 map [images, h, w]
+    (`edges`, allocated when None, returned) and, when given, the control tensor [rep * images, 3, h, w] (float32 / float16) = map / 255
+    (ca_mlsd_draw)."""
+    _req_cuda(segments, count, edges, control)
+    n = segments.shape[0]
+    assert segments.dtype == torch.int32 and tuple(segments.shape) == (n, MLSD_TOPK, 4) and segments.is_contiguous()
+    assert count.dtype == torch.int32 and tuple(count.shape) == (n,) and count.is_contiguous()
+    if edges is None:
+        edges = torch.empty((n, h, w), dtype=torch.uint8, device=segments.device)
+    assert edges.dtype == torch.uint8 and tuple(edges.shape) == (n, h, w) and edges.is_contiguous()
+    dt = _capi.CA_F32
+    if control is not None:
+        if control.dtype not in _CANNY_DT:
+            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
+        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
+        dt = _CANNY_DT[control.dtype]
+    check(lib().ca_mlsd_draw(_p(segments), _p(count), n, h, w, _p(edges), _p(control), int(rep), dt, _stream()), "ca_mlsd_draw")
+    return edges

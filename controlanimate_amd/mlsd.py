@@ -1,0 +1,505 @@
+"""The M-LSD straight-line annotator of the reference's sample configs (SampleConfig.yaml, SampleConfigLCMLoRA.yaml and
+SampleConfigIPAdapter.yaml list lllyasviel/control_v11p_sd15_mlsd, the last one sd-controlnet-mlsd as well; their control frames come
+from controlnet_aux's MLSDdetector, modules/controlresiduals_pipeline.py:56, 101-105) on the GPU, for a whole window of frames at once.
+
+The detector, as the reference calls it (thr_v = 0.1, thr_d = 0.1, detect_resolution = image_resolution = 512):
+
+    input    [H, W, 4]: RGB and a channel of ones, x / 127.5 - 1 on all four
+    network  MobileV2_MLSD_Large: a MobileNetV2 backbone (features.0 .. 13; ConvBNReLU = Conv2d, BatchNorm, ReLU6, with F.pad(x, (0, 1, 0, 1))
+             and padding 0 at stride 2; InvertedResidual = [1x1 expansion], depthwise 3x3, linear 1x1, skip when the shapes allow), taps
+             c1 .. c5 after features 1, 3, 6, 10, 13, and a decoder of blocks A (two 1x1 convolutions + BN + ReLU, one side upsampled x2
+             bilinearly with align_corners, concatenated), B (conv2(conv1(x) + x), 3x3 + BN + ReLU each) and C (3x3 with dilation 5, 3x3,
+             1x1 to 16 channels) at half resolution; channels 7 .. 11 of the 16 are read: the centre logit and (dx_s, dy_s, dx_e, dy_e)
+    decode   sigmoid, 3x3 maximum test that keeps plateaus, the top 200 of the map, score > thr_v, then |start - end| > thr_d (a dropped
+             point is not replaced), endpoints 2 * (pixel + displacement) in float64 truncated by int()
+    draw     cv2.line(map, start, end, 255, 1) on a zeroed map; three equal channels
+
+It runs as (the names are the keys of `timings`, the numbers the stages of that name per pass):
+
+    prep       1   ca_mlsd_prep: uint8 frames -> 8 channels (the stem's weight is zero-padded to 8 input channels)
+    stem       1   ca_conv3x3, stride 2, pad_asym, CA_ACT_RELU6
+    pointwise  33  ca_gemm with the folded bias: CA_ACT_RELU6 (expansions), none + residual (projections), CA_ACT_RELU (block A, whose
+                   conv2 writes columns 0 .. 63 of the 128-wide concatenation through ldc = 128)
+    depthwise  13  ca_dwconv3x3
+    upsample   3   ca_upsample2x_bilinear_ac into columns 64 .. 127 of the concatenation
+    conv       9   ca_conv3x3 with CA_ACT_RELU: the two convolutions of every block B and the second of block C
+    add        4   ca_add_bcast: block B's conv1(x) + x is ReLU THEN add, which the convolution's residual epilogue (add, then activation)
+                   does not compute -- one more pass over a 128-channel tensor at the block's resolution
+    dilated    1   ca_conv3x3_dil
+    head       1   ca_gemm, N = 8: rows 7 .. 11 of block23.conv3, zero-padded, fp32 output -- the tpMap [n, H/2, W/2, 8]
+    decode     1   ca_mlsd_decode -> segments int32 [n, 200, 4], count int32 [n]
+    draw       1   ca_mlsd_draw -> the uint8 map and / or the control tensor the ControlNets hold
+
+Eval-mode BatchNorm (eps 1e-5) is folded into the convolution before it once, on the host, in fp32.  No device-to-host read anywhere:
+the chain can be captured in a hipGraph.
+
+The specification is tests/mlsd_ref.py (the fp32 torch network, the numpy decode and line iterator).  Key names and arithmetic are
+restated from memory of the published code (mbv2_mlsd_large.py, utils.py of controlnet_aux's mlsd, OpenCV's clipLine / LineIterator)
+and are UNPINNED: controlnet_aux and OpenCV are third-party packages that are absent here, and no mlsd_large_512_fp32.pth is available.
+torch.topk's order among equal scores is unspecified; here it is score descending, then flat index ascending.
+
+Scope of sizes: min(H, W) == detect_resolution == image_resolution with H and W multiples of 64, for which both resize_image calls, the
+INTER_AREA resize inside pred_lines and the final INTER_LINEAR resize are the identity (512 x 512, 512 x 768, 768 x 512 at the default
+512); anything else raises NotImplementedError.  MobileV2_MLSD_Tiny is not part of this.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+
+try:
+    from PIL import Image
+except Exception:  # pragma: no cover
+    Image = None
+
+WEIGHTS_NAME = "mlsd_large_512_fp32.pth"
+EPS = 1e-5
+TOPK = 200
+# (t, c, n, s) of the backbone behind features.0, as far as the taps reach (features.1 .. features.13)
+SETTINGS = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1))
+TAPS = (1, 3, 6, 10, 13)
+STAGES = {"prep": 1, "stem": 1, "pointwise": 33, "depthwise": 13, "upsample": 3, "conv": 9, "add": 4, "dilated": 1, "head": 1, "decode": 1, "draw": 1}
+
+
+def backbone_blocks():
+    """[(features index, cin, hidden, cout, stride, expands, skips)] of features.1 .. features.13."""
+    out, cin, idx = [], 32, 1
+    for t, c, n, s in SETTINGS:
+        for i in range(n):
+            stride = s if i == 0 else 1
+            out.append((idx, cin, cin * t, c, stride, t != 1, stride == 1 and cin == c))
+            cin, idx = c, idx + 1
+    return out
+
+
+def _bn(prefix: str, c: int) -> dict:
+    return {f"{prefix}.weight": (c,), f"{prefix}.bias": (c,), f"{prefix}.running_mean": (c,), f"{prefix}.running_var": (c,)}
+
+
+def mlsd_key_shapes() -> dict:
+    """Every tensor of mlsd_large_512_fp32.pth that the chain uses: name -> shape."""
+    out = {"backbone.features.0.0.weight": (32, 4, 3, 3), **_bn("backbone.features.0.1", 32)}
+    for idx, cin, hid, c, _, expands, _ in backbone_blocks():
+        p, j = f"backbone.features.{idx}.conv", 0
+        if expands:
+            out[f"{p}.0.0.weight"] = (hid, cin, 1, 1)
+            out.update(_bn(f"{p}.0.1", hid))
+            j = 1
+        out[f"{p}.{j}.0.weight"] = (hid, 1, 3, 3)
+        out.update(_bn(f"{p}.{j}.1", hid))
+        out[f"{p}.{j + 1}.weight"] = (c, hid, 1, 1)
+        out.update(_bn(f"{p}.{j + 2}", c))
+
+    def conv_bn(prefix, cout, cin, k):
+        out[f"{prefix}.0.weight"], out[f"{prefix}.0.bias"] = (cout, cin, k, k), (cout,)
+        out.update(_bn(f"{prefix}.1", cout))
+
+    for blk, (c_a, c_b) in ((15, (64, 96)), (17, (32, 64)), (19, (24, 64)), (21, (16, 64))):   # A(a, b): conv1 takes b, conv2 takes a
+        conv_bn(f"block{blk}.conv1", 64, c_b, 1)
+        conv_bn(f"block{blk}.conv2", 64, c_a, 1)
+        conv_bn(f"block{blk + 1}.conv1", 128, 128, 3)
+        conv_bn(f"block{blk + 1}.conv2", 64, 128, 3)
+    conv_bn("block23.conv1", 64, 64, 3)
+    conv_bn("block23.conv2", 64, 64, 3)
+    out["block23.conv3.weight"], out["block23.conv3.bias"] = (16, 64, 1, 1), (16,)
+    return out
+
+
+def check_state_dict(sd) -> None:
+    """KeyError naming a missing tensor, ValueError naming one that is unexpected or has the wrong shape.  num_batches_tracked and any
+    further backbone. key (layers past features.13 that a checkpoint may keep) are ignored."""
+    want = mlsd_key_shapes()
+    for k in want:
+        if k not in sd:
+            raise KeyError(f"mlsd state dict: '{k}' is missing ({len(want)} tensors expected: backbone.features.0 .. 13 and block15 .. block23 "
+                           f"of MobileV2_MLSD_Large)")
+    for k in sd:
+        if k not in want and not k.endswith("num_batches_tracked") and not k.startswith("backbone."):
+            raise ValueError(f"mlsd state dict: unexpected tensor '{k}'")
+    for k, shape in want.items():
+        if tuple(sd[k].shape) != shape:
+            raise ValueError(f"mlsd state dict: '{k}' has shape {tuple(sd[k].shape)}, expected {shape}")
+
+
+def fold_bn(sd, conv: str, bn: str):
+    """(weight, bias) in fp32 of the convolution `conv` followed by the eval-mode BatchNorm `bn`: w * g / sqrt(var + eps) per output
+    channel, (b - mean) * g / sqrt(var + eps) + beta."""
+    import torch
+    w = sd[conv + ".weight"].detach().float()
+    b = sd[conv + ".bias"].detach().float() if conv + ".bias" in sd else torch.zeros(w.shape[0])
+    scale = sd[bn + ".weight"].detach().float() / torch.sqrt(sd[bn + ".running_var"].detach().float() + EPS)
+    return w * scale.view(-1, 1, 1, 1), (b - sd[bn + ".running_mean"].detach().float()) * scale + sd[bn + ".bias"].detach().float()
+
+
+def folded_layers(sd) -> dict:
+    """The network as fp32 (weight, bias) pairs in PyTorch layout, BatchNorm folded: what the device chain and the folding test read.
+    "stem"; "features": [{"expand"?, "dw", "project"}]; "A": [(conv1, conv2)] and "B": [(conv1, conv2)] for blocks 15 / 17 / 19 / 21 and
+    16 / 18 / 20 / 22; "C": (conv1, conv2, conv3)."""
+    out = {"stem": fold_bn(sd, "backbone.features.0.0", "backbone.features.0.1"), "features": [], "A": [], "B": []}
+    for idx, _, _, _, _, expands, _ in backbone_blocks():
+        p, j, blk = f"backbone.features.{idx}.conv", 0, {}
+        if expands:
+            blk["expand"] = fold_bn(sd, f"{p}.0.0", f"{p}.0.1")
+            j = 1
+        blk["dw"] = fold_bn(sd, f"{p}.{j}.0", f"{p}.{j}.1")
+        blk["project"] = fold_bn(sd, f"{p}.{j + 1}", f"{p}.{j + 2}")
+        out["features"].append(blk)
+    for blk in (15, 17, 19, 21):
+        out["A"].append(tuple(fold_bn(sd, f"block{blk}.conv{k}.0", f"block{blk}.conv{k}.1") for k in (1, 2)))
+        out["B"].append(tuple(fold_bn(sd, f"block{blk + 1}.conv{k}.0", f"block{blk + 1}.conv{k}.1") for k in (1, 2)))
+    out["C"] = (fold_bn(sd, "block23.conv1.0", "block23.conv1.1"), fold_bn(sd, "block23.conv2.0", "block23.conv2.1"),
+                (sd["block23.conv3.weight"].detach().float(), sd["block23.conv3.bias"].detach().float()))
+    return out
+
+
+def pack_depthwise(w):
+    """Depthwise weight [C, 1, 3, 3] -> [9, C]: tap ky * 3 + kx of every channel (ca_dwconv3x3)."""
+    if w.dim() != 4 or tuple(w.shape[1:]) != (1, 3, 3):
+        raise ValueError(f"a depthwise weight [C, 1, 3, 3] is expected, got {tuple(w.shape)}")
+    return w.detach().reshape(w.shape[0], 9).t().contiguous()
+
+
+class MlsdAnnotator:
+    """`MlsdAnnotator(weights)(image)` has the contract of `annotators.canny(image)` (PIL in, PIL RGB with three equal channels out; an
+    array in, an array out), so it plugs into `MultiControlNetResidualsPipeline(annotators={"mlsd": MlsdAnnotator.from_pretrained(path)})`,
+    whose `prep_control_images` then calls `annotate_batch` once per list of frames.  Nothing makes it a default: the weights are the
+    user's file.  Non-uint8 input raises TypeError, frames of different sizes ValueError, sizes out of scope NotImplementedError -- all
+    before the device is touched; without the library or a GPU a call raises CAHipUnavailable (there is no CPU fallback)."""
+
+    # the largest operand of a chunk of frames (the 128-channel concatenation at half resolution: 64 bytes per frame pixel) stays below
+    # what the GEMM and convolution kernels address with 32-bit byte offsets
+    max_activation_bytes = 0x7FFFFF00 - 1
+    _bytes_per_pixel = 64
+
+    def __init__(self, state_dict_or_path, device=None, dtype=None, detect_resolution: int = 512, image_resolution: int = 512,
+                 thr_v: float = 0.1, thr_d: float = 0.1):
+        import torch
+        dtype = torch.float16 if dtype is None else dtype
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise TypeError(f"dtype must be torch.float16 or torch.bfloat16, got {dtype}")
+        if detect_resolution != image_resolution or detect_resolution < 64 or detect_resolution % 64:
+            raise NotImplementedError(f"MlsdAnnotator takes detect_resolution == image_resolution, a multiple of 64 (no resampling); got "
+                                      f"{detect_resolution} and {image_resolution}")
+        if not (0.0 <= thr_v < 1.0) or not (0.0 <= thr_d < float("inf")):
+            raise ValueError(f"thr_v={thr_v} (0 <= thr_v < 1), thr_d={thr_d} (>= 0)")
+        sd = self._load(state_dict_or_path) if isinstance(state_dict_or_path, (str, os.PathLike)) else state_dict_or_path
+        check_state_dict(sd)
+        self.device, self.dtype = device, dtype
+        self.resolution, self.thr_v, self.thr_d = int(detect_resolution), float(thr_v), float(thr_d)
+        f = folded_layers(sd)
+
+        def conv(wb):  # [Cout, Cin, 3, 3] -> [Cout, 3, 3, Cin]
+            return wb[0].permute(0, 2, 3, 1).contiguous().to(dtype), wb[1].contiguous()
+
+        def lin(wb):   # [Cout, Cin, 1, 1] -> [Cout, Cin]
+            return wb[0].reshape(wb[0].shape[0], -1).contiguous().to(dtype), wb[1].contiguous()
+
+        stem_w = torch.nn.functional.pad(f["stem"][0], (0, 0, 0, 0, 0, 4))  # 4 -> 8 input channels, the new ones zero
+        head_w, head_b = f["C"][2][0].reshape(16, 64)[7:12], f["C"][2][1][7:12]
+        # packed once, on the host
+        self._host = {
+            "stem": conv((stem_w, f["stem"][1])),
+            "features": [{k: ((pack_depthwise(v[0]).to(dtype), v[1].contiguous()) if k == "dw" else lin(v)) for k, v in blk.items()} for blk in f["features"]],
+            "A": [(lin(a), lin(b)) for a, b in f["A"]],
+            "B": [(conv(a), conv(b)) for a, b in f["B"]],
+            "C": (conv(f["C"][0]), conv(f["C"][1])),
+            "head": (torch.nn.functional.pad(head_w, (0, 0, 0, 3)).contiguous().to(dtype), torch.nn.functional.pad(head_b, (0, 3)).contiguous()),
+        }
+        self._dev = None
+        self._ws = {}
+        self.timings = None  # a dict: receives (start, end) torch events per stage under the keys of STAGES -- tools/bench_mlsd.py
+
+    @staticmethod
+    def _weights_path(path) -> str:
+        path = os.fspath(path)
+        if os.path.isdir(path):
+            path = os.path.join(path, WEIGHTS_NAME)
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"{path}: no such file (a local {WEIGHTS_NAME}, or a directory that holds it; nothing is ever downloaded)")
+        return path
+
+    @classmethod
+    def _load(cls, path):
+        import torch
+        path = cls._weights_path(path)
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        if not isinstance(sd, dict):
+            raise ValueError(f"{path}: not a state dict")
+        return sd
+
+    @classmethod
+    def from_pretrained(cls, path, **kwargs):
+        """path: a local mlsd_large_512_fp32.pth or a directory that holds it (no network access, ever)."""
+        return cls(cls._load(path), **kwargs)
+
+    # ---- device state ----------------------------------------------------------------------------------------------------------
+    def _device(self):
+        import torch
+        from . import _capi
+        _capi.lib()  # CAHipUnavailable when the extension is not built
+        if not torch.cuda.is_available():
+            raise _capi.CAHipUnavailable("MlsdAnnotator needs a GPU (there is no CPU fallback)")
+        return torch.device(self.device if self.device is not None else "cuda")
+
+    def _weights(self, dev):
+        import torch
+
+        def move(o):
+            if isinstance(o, torch.Tensor):
+                return o.to(dev)
+            if isinstance(o, dict):
+                return {k: move(v) for k, v in o.items()}
+            return type(o)(move(v) for v in o)
+
+        if self._dev is None or self._dev["head"][1].device != dev:
+            self._dev = move(self._host)
+        return self._dev
+
+    def chunk_frames(self, h: int, w: int) -> int:
+        """Frames per pass through the network: as many as keep the largest operand within max_activation_bytes."""
+        per_frame = h * w * self._bytes_per_pixel
+        if per_frame > self.max_activation_bytes:
+            raise ValueError(f"a {h} x {w} frame alone exceeds what the kernels address ({per_frame} > {self.max_activation_bytes} bytes)")
+        return self.max_activation_bytes // per_frame
+
+    def workspace(self, n: int, h: int, w: int) -> dict:
+        """The buffers of a call with n frames of h x w pixels, cached per (n, h, w): the tpMap float32 [n, h/2, w/2, 8], the segments, the
+        counts, the candidate list of the decode, the map that is drawn when only the control tensor is asked for, and a pool of
+        activation buffers that the layers of a pass take and give back in a fixed order (contents are never assumed; the first pass
+        allocates them -- the largest chunk comes first -- and every later pass reuses the same ones)."""
+        import torch
+        from . import kernels as K
+        key = (n, h, w)
+        if key not in self._ws:
+            dev = self._device()
+            self._ws[key] = {"tp": torch.empty((n, h // 2, w // 2, 8), dtype=torch.float32, device=dev),
+                             "segments": torch.empty((n, TOPK, 4), dtype=torch.int32, device=dev),
+                             "count": torch.empty((n,), dtype=torch.int32, device=dev),
+                             "decode": torch.empty(K.mlsd_decode_workspace_bytes(n, h // 2, w // 2), dtype=torch.uint8, device=dev),
+                             "map": torch.empty((n, h, w), dtype=torch.uint8, device=dev),
+                             "pool": [], "plan": [], "planned": False}
+        return self._ws[key]
+
+    def _stage(self, name):
+        import torch
+        if self.timings is None:
+            return None
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        self.timings.setdefault(name, []).append(ev)
+        ev[0].record()
+        return ev
+
+    # ---- input checks ----------------------------------------------------------------------------------------------------------
+    def _check_size(self, h: int, w: int) -> None:
+        r = self.resolution
+        if min(h, w) != r or h % 64 or w % 64:
+            raise NotImplementedError(
+                f"MlsdAnnotator takes frames with min(H, W) == detect_resolution == image_resolution (= {r}) and H % 64 == W % 64 == 0, for "
+                f"which every resampling of the detector is the identity; got {h} x {w}")
+
+    def _frames(self, frames):
+        """-> uint8 device tensor [n, H, W, 3].  The type, size and scope checks come before the device is touched.  A PIL image is taken
+        as np.asarray gives it, so its mode must be L or RGB (a grey frame is repeated to three channels, as the detector's HWC3 does)."""
+        import torch
+        if isinstance(frames, torch.Tensor):
+            if frames.dtype != torch.uint8:
+                raise TypeError(f"frames must be uint8, got {frames.dtype}")
+            if frames.dim() == 3:
+                frames = frames[..., None]
+            if frames.dim() != 4 or frames.shape[3] not in (1, 3):
+                raise ValueError(f"frames tensor must be [n, H, W] or [n, H, W, C] with C = 1 or 3, got {tuple(frames.shape)}")
+            self._check_size(frames.shape[1], frames.shape[2])
+            dev = self._device()
+            if frames.shape[3] == 1:
+                frames = frames.expand(-1, -1, -1, 3)
+            return frames.to(dev).contiguous()
+        host = []
+        for fr in frames:
+            a = np.asarray(fr)
+            if a.dtype != np.uint8:
+                raise TypeError(f"frames must be uint8, got {a.dtype}")
+            if a.ndim == 2:
+                a = a[:, :, None]
+            if a.ndim != 3 or a.shape[2] not in (1, 3):
+                raise ValueError(f"a frame must be [H, W] or [H, W, C] with C = 1 or 3 (PIL mode L or RGB: convert RGBA or palette "
+                                 f"frames with .convert('RGB') first), got {a.shape}" + (f" from PIL mode {fr.mode}" if hasattr(fr, "mode") else ""))
+            host.append(a)
+        if not host:
+            raise ValueError("no frames")
+        if any(a.shape != host[0].shape for a in host):
+            raise ValueError("all frames of a call must share one size")
+        self._check_size(host[0].shape[0], host[0].shape[1])
+        dev = self._device()
+        stack = np.stack(host)
+        if stack.shape[3] == 1:
+            stack = np.repeat(stack, 3, axis=3)
+        return torch.from_numpy(stack).to(dev)
+
+    # ---- the chain -------------------------------------------------------------------------------------------------------------
+    def _network(self, src, ws, i0: int) -> None:
+        """The network for the frames `src` (a chunk), the tpMap into ws["tp"][i0 : i0 + len(src)]."""
+        import torch
+        from . import kernels as K
+        wts = self._weights(src.device)
+        n, h, w, _ = src.shape
+        pool, plan = ws["pool"], ws["plan"]  # [[flat buffer, taken]]; the slot of the i-th take of a pass, fixed by the first pass
+        replay, cursor = ws["planned"], [0]
+        if not replay:
+            plan.clear()   # (a first pass that did not finish starts over)
+
+        def take(*shape):
+            numel = int(np.prod(shape))
+            if replay:   # the same buffers in the same order on every pass: nothing is allocated after the first one (a captured graph stays valid)
+                slot = pool[plan[cursor[0]]]
+                cursor[0] += 1
+                assert not slot[1] and slot[0].numel() >= numel
+            else:
+                free = [i for i, sl in enumerate(pool) if not sl[1] and sl[0].numel() >= numel]
+                if not free:
+                    pool.append([torch.empty(numel, dtype=self.dtype, device=src.device), False])
+                    free = [len(pool) - 1]
+                plan.append(min(free, key=lambda i: pool[i][0].numel()))
+                slot = pool[plan[-1]]
+            slot[1] = True
+            return slot[0][:numel].view(*shape)
+
+        def give(t):
+            for slot in pool:
+                if slot[0].data_ptr() == t.data_ptr():
+                    slot[1] = False
+                    return
+            raise AssertionError("not a pool buffer")
+
+        def timed(name, fn, *args, **kw):
+            ev = self._stage(name)
+            out = fn(*args, **kw)
+            if ev:
+                ev[1].record()
+            return out
+
+        def pw(x, wb, act, out2d=None, residual=None, name="pointwise", out_f32=False):
+            """1x1 convolution of NHWC x as a GEMM over its pixels; out2d: a [pixels, N] view (possibly of a wider tensor)."""
+            nn, hh, ww, cc = x.shape
+            m = nn * hh * ww
+            ret = None
+            if out2d is None:
+                ret = take(nn, hh, ww, wb[0].shape[0])
+                out2d = ret.view(m, wb[0].shape[0])
+            timed(name, K.gemm, x.view(m, cc), wb[0], bias=wb[1], act=act, residual=None if residual is None else residual.view(m, -1), out=out2d,
+                  out_f32=out_f32)
+            return ret
+
+        for slot in pool:
+            slot[1] = False
+        x = timed("prep", K.mlsd_prep, src, take(n, h, w, 8))
+        y = timed("stem", K.conv3x3, x, wts["stem"][0], bias=wts["stem"][1], stride=2, pad_asym=True, act=K.ACT_RELU6, out=take(n, h // 2, w // 2, 32))
+        give(x)
+        x, taps = y, {}
+        for (idx, _, hid, c, stride, expands, skips), blk in zip(backbone_blocks(), wts["features"]):
+            t = pw(x, blk["expand"], K.ACT_RELU6) if expands else x
+            hh, ww = t.shape[1] // stride, t.shape[2] // stride
+            d = timed("depthwise", K.dwconv3x3, t, blk["dw"][0], blk["dw"][1], stride=stride, relu6=True, out=take(n, hh, ww, hid))
+            if expands:
+                give(t)
+            y = pw(d, blk["project"], K.ACT_NONE, residual=x if skips else None)
+            give(d)
+            if idx - 1 in TAPS:   # x is the output of features[idx - 1]: a tap stays until its block A has read it
+                taps[idx - 1] = x
+            else:
+                give(x)
+            x = y
+            if idx == TAPS[-1]:
+                taps[idx] = x
+        c1, c2, c3, c4, c5 = (taps[i] for i in TAPS)
+        x = c5
+        for level, (a, up) in enumerate(((c4, False), (c3, True), (c2, True), (c1, True))):
+            (w1, w2), (b1, b2) = wts["A"][level], wts["B"][level]
+            nn, hh, ww, _ = a.shape
+            cat = take(nn, hh, ww, 128)
+            cat2d = cat.view(nn * hh * ww, 128)
+            pw(a, w2, K.ACT_RELU, out2d=cat2d[:, :64])
+            if up:
+                t = pw(x, w1, K.ACT_RELU)
+                timed("upsample", K.upsample2x_bilinear_ac, t, cat, 64)
+                give(t)
+            else:
+                pw(x, w1, K.ACT_RELU, out2d=cat2d[:, 64:])
+            give(a)
+            give(x)
+            t = timed("conv", K.conv3x3, cat, b1[0], bias=b1[1], act=K.ACT_RELU, out=take(nn, hh, ww, 128))
+            timed("add", K.add_bcast, t, cat, out=t)   # ReLU, then the skip
+            give(cat)
+            x = timed("conv", K.conv3x3, t, b2[0], bias=b2[1], act=K.ACT_RELU, out=take(nn, hh, ww, 64))
+            give(t)
+        (d1, d2) = wts["C"]
+        t = timed("dilated", K.conv3x3_dil, x, d1[0], d1[1], dilation=5, relu=True, out=take(*x.shape))
+        give(x)
+        x = timed("conv", K.conv3x3, t, d2[0], bias=d2[1], act=K.ACT_RELU, out=take(*t.shape))
+        give(t)
+        tp = ws["tp"][i0:i0 + n]
+        pw(x, wts["head"], K.ACT_NONE, out2d=tp.view(-1, 8), name="head", out_f32=True)
+        give(x)
+        ws["planned"] = True
+
+    def _run(self, src, edges, control, rep):
+        from . import kernels as K
+        n, h, w, _ = src.shape
+        ws = self.workspace(n, h, w)
+        step = self.chunk_frames(h, w)
+        for i0 in range(0, n, step):
+            self._network(src[i0:i0 + step], ws, i0)
+        if edges is not None or control is not None:
+            ev = self._stage("decode")
+            K.mlsd_decode(ws["tp"], self.thr_v, self.thr_d, segments=ws["segments"], count=ws["count"], ws=ws["decode"])
+            if ev:
+                ev[1].record()
+            ev = self._stage("draw")
+            K.mlsd_draw(ws["segments"], ws["count"], h, w, edges=edges if edges is not None else ws["map"], control=control, rep=rep)
+            if ev:
+                ev[1].record()
+        return ws["tp"]
+
+    def tpmap(self, frames):
+        """-> float32 [n, H/2, W/2, 8] on the device, as a new tensor: channel 0 the centre logit, channels 1 .. 4 the displacements
+        (dx_s, dy_s, dx_e, dy_e) -- channels 7 .. 11 of the network's output; channels 5 .. 7 are zero."""
+        src = self._frames(frames)
+        return self._run(src, None, None, 1).clone()
+
+    def edges(self, frames, out=None):
+        """frames: a list of PIL images / uint8 arrays of one size, or a uint8 tensor [n, H, W, C] (no host copy when it is on the
+        device) -> uint8 device tensor [n, H, W] (the detector's map: 0, lines 255), written into `out` when given."""
+        import torch
+        src = self._frames(frames)
+        n, h, w, _ = src.shape
+        if out is None:
+            out = torch.empty((n, h, w), dtype=torch.uint8, device=src.device)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w) or out.device != src.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint8 tensor {(n, h, w)} on {src.device}")
+        if n:
+            self._run(src, out, None, 1)
+        return out
+
+    def annotate_batch(self, frames, out=None, rep: int = 1, dtype=None):
+        """-> the control tensor [rep * n, 3, H, W] on the device, map / 255 with three equal channels; rep = 2 writes the n frames
+        twice (torch.cat([ctrl] * 2) of classifier-free guidance).  Written into `out` (and `out` returned) when given."""
+        import torch
+        if rep not in (1, 2):
+            raise ValueError(f"rep={rep} (1 or 2)")
+        want = out.dtype if out is not None and dtype is None else (dtype if dtype is not None else torch.float32)
+        if want not in (torch.float32, torch.float16):
+            raise TypeError(f"the control tensor is float32 or float16, got {want}")
+        src = self._frames(frames)
+        n, h, w, _ = src.shape
+        if out is None:
+            out = torch.empty((rep * n, 3, h, w), dtype=want, device=src.device)
+        elif tuple(out.shape) != (rep * n, 3, h, w) or out.device != src.device or not out.is_contiguous() or out.dtype != want:
+            raise ValueError(f"out must be a contiguous {want} tensor {(rep * n, 3, h, w)} on {src.device}")
+        if n:
+            self._run(src, None, out, rep)
+        return out
+
+    def __call__(self, image):
+        e = self.edges([image])[0].cpu().numpy()
+        rgb = np.repeat(e[:, :, None], 3, axis=2)
+        return Image.fromarray(rgb) if Image is not None and not isinstance(image, np.ndarray) else rgb

@@ -45,6 +45,7 @@ extern "C" {
 #define CA_ACT_QUICK_GELU 2 /* x * sigmoid(1.702 x): CLIP ViT-L text/vision MLPs */
 #define CA_ACT_GELU 3       /* erf GELU: CLIP ViT-H vision MLP (IP-Adapter image encoder) */
 #define CA_ACT_RELU 4       /* max(x, 0): the VGG stack of the HED annotator (added to ABI v16) */
+#define CA_ACT_RELU6 5      /* min(max(x, 0), 6): the MobileNetV2 backbone of the M-LSD annotator (added to ABI v16) */
 
 int ca_abi_version(void);
 const char* ca_last_error(void);
@@ -813,6 +814,60 @@ int ca_lineart_conv_out(const void* x, const float* wt, const float* bias, float
  * h * w a multiple of 4; logits 16-byte aligned. */
 int ca_lineart_finish(const float* logits, int32_t images, int32_t h, int32_t w, uint8_t* map, void* control, int32_t rep, int32_t control_dtype,
                       void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * The M-LSD straight-line annotator (added to ABI v16: no struct or existing function changes, the number stays).  Every sample
+ * config of the reference with ControlNets lists control_v11p_sd15_mlsd, whose frames come from controlnet_aux's MLSDdetector
+ * (modules/controlresiduals_pipeline.py:56, 101-105): MobileV2_MLSD_Large (a MobileNetV2 backbone and an FPN-style decoder), a
+ * top-200 decode of its centre map and cv2.line.  The stem and the plain 3x3 convolutions are ca_conv3x3 (act = CA_ACT_RELU6 /
+ * CA_ACT_RELU), every 1x1 convolution ca_gemm, the ReLU-then-add of the decoder ca_add_bcast; the entry points below are the rest
+ * (controlanimate_amd/mlsd.py: MlsdAnnotator; the specification is tests/mlsd_ref.py).  Tensors are NHWC, CA_F16 or CA_BF16.  Every
+ * launch is a function of its arguments alone with no device-to-host read: the chain can be captured in a hipGraph, and two runs
+ * give the same bits.  Anything outside the stated ranges is CA_ERR_INVALID_ARG before any launch.
+ * ------------------------------------------------------------------------------------ */
+#define CA_MLSD_TOPK 200
+
+/* dst [images, h, w, 8] of dtype (16-byte aligned): channel c < 3 = src[.., c] / 127.5 - 1 in fp32, rounded once; channel 3 =
+ * 1 / 127.5 - 1 (the detector's fourth input channel of ones); channels 4 .. 7 = 0.  src uint8 RGB [images, h, w, 3]. */
+int ca_mlsd_prep(const uint8_t* src, void* dst, int32_t images, int32_t h, int32_t w, int32_t dtype, void* stream);
+
+/* Depthwise 3x3 convolution: y[n, oy, ox, ch] = act(bias[ch] + sum_{ky,kx} wt[ky * 3 + kx][ch] * x[n, oy * stride + ky - p, ox * stride + kx - p, ch]),
+ * zero outside the image.  stride 1: p = 1, output h x w.  stride 2: p = 0 with one row and column of zeros after the image
+ * (F.pad(x, (0, 1, 0, 1)) + Conv2d(padding = 0)), h and w even, output h / 2 x w / 2.  wt [9][c] of dtype, bias fp32 [c];
+ * relu6 = 1 clamps to [0, 6].  c a multiple of 8 in 16 .. 576; fp32 accumulation, rounded once; x, wt, y 16-byte aligned. */
+int ca_dwconv3x3(const void* x, const void* wt, const float* bias, void* y, int32_t images, int32_t h, int32_t w, int32_t c, int32_t stride,
+                 int32_t relu6, int32_t dtype, void* stream);
+
+/* Bilinear x2 upsampling with align_corners = True (F.interpolate): x [images, h, w, c] -> columns col0 .. col0 + c - 1 of
+ * y [images, 2 h, 2 w, ld]; the other columns of y are never touched (one half of a channel concatenation).  Per axis
+ * src = dst * (in - 1) / (out - 1) in fp32 (the integer product divided once), i0 = trunc(src), f = src - i0; the columns are combined
+ * first (a * (1 - f) + b * f), then the rows, in fp32, rounded once.  c, ld and col0 multiples of 8; both 16-byte aligned. */
+int ca_upsample2x_bilinear_ac(const void* x, void* y, int32_t images, int32_t h, int32_t w, int32_t c, int64_t ld, int32_t col0, int32_t dtype,
+                              void* stream);
+
+/* y [images, h, w, 64] = act(bias + Conv2d(64, 64, 3, dilation = 5, padding = 5)(x)), x [images, h, w, 64]; wt [64][3][3][64]
+ * (the layout of ca_conv_args.w) of dtype, bias fp32 [64]; relu = 1: max(., 0).  c must be 64 and dilation 5 (what the kernel is built
+ * for).  MFMA with fp32 accumulation, rounded once.  x, wt, y 16-byte aligned; y must not be x. */
+int ca_conv3x3_dil(const void* x, const void* wt, const float* bias, void* y, int32_t images, int32_t h, int32_t w, int32_t c, int32_t dilation,
+                   int32_t relu, int32_t dtype, void* stream);
+
+/* tp fp32 [images, h, w, 8]: channel 0 the centre logit, channels 1 .. 4 the displacements (dx_s, dy_s, dx_e, dy_e), 5 .. 7 unused.
+ * heat = 1 / (1 + exp(-logit)) in fp32; a pixel is a candidate when heat > thr_v and no 3x3 neighbour inside the map has a larger heat
+ * (plateaus keep every pixel).  The CA_MLSD_TOPK candidates first by (heat descending, flat index ascending) are the points; a point
+ * with sqrt((dx_s - dx_e)^2 + (dy_s - dy_e)^2) > thr_d (fp32) is a line -- a dropped point is not replaced.  segments int32
+ * [images, CA_MLSD_TOPK, 4] = (xs, ys, xe, ye) = trunc(2 * (x + dx_s)), ... in float64, pinned to +-2^30, in rank order, the unused tail
+ * zero; count int32 [images].  workspace: ca_mlsd_decode_workspace_bytes bytes (the candidate list, h * w keys per image: a saturated
+ * plateau cannot overflow it; 0 for sizes out of range), 8-byte aligned.  0 <= thr_v < 1, thr_d >= 0. */
+int64_t ca_mlsd_decode_workspace_bytes(int32_t images, int32_t h, int32_t w);
+int ca_mlsd_decode(const float* tp, int32_t images, int32_t h, int32_t w, float thr_v, float thr_d, void* workspace, int64_t workspace_bytes,
+                   int32_t* segments, int32_t* count, void* stream);
+
+/* map uint8 [images, h, w] = zeros, then cv2.line(map, (xs, ys), (xe, ye), 255, 1) for the first min(count, CA_MLSD_TOPK) segments of
+ * every image: OpenCV's clipLine to the image and its 8-connected left-to-right line iterator.  With control != NULL also
+ * control [rep * images, 3, h, w] of control_dtype (CA_F16 or CA_F32, aligned to four elements) = map / 255, the three channels equal
+ * and, with rep = 2, the frames written twice (the contract of ca_canny_emit).  h * w a multiple of 4; map 4-byte aligned. */
+int ca_mlsd_draw(const int32_t* segments, const int32_t* count, int32_t images, int32_t h, int32_t w, uint8_t* map, void* control, int32_t rep,
+                 int32_t control_dtype, void* stream);
 
 #ifdef __cplusplus
 }
