@@ -46,6 +46,7 @@ class Dispatch:
     ln_fold = True        # LayerNorm folded into the projection it feeds
     cfg_shared = True     # the prompt-independent prefix of the two CFG halves runs once
     cn_cfg_dedup = True   # ControlNet under non-guess CFG: the reference's prompt tiling makes its two batch halves the same problem -- solved once
+    pdc_block_fused = True  # ca_pdc_block for the C = 64 blocks of the softedge annotator (else ca_dwconv_k + ca_gemm with the skip as its residual)
     controlnet_streams = 2  # HIP streams the bodies of a stack of >= 3 ControlNets are spread over (independent up to the summed residuals)
 
 

@@ -16,8 +16,9 @@ the GPU from the user's ControlNetHED.pth through `annotators={"hed": HedAnnotat
 and lineart, the IP-Adapter sample config's, from the user's sk_model.pth through `annotators={"lineart":
 LineartAnnotator.from_pretrained(path)}` (controlanimate_amd/lineart.py), and M-LSD, which every sample config with ControlNets lists,
 from the user's mlsd_large_512_fp32.pth through `annotators={"mlsd": MlsdAnnotator.from_pretrained(path)}` (controlanimate_amd/mlsd.py; the
-key serves control_v11p_sd15_mlsd and sd-controlnet-mlsd); the other learned detectors (openpose / lineart_anime / softedge /
-depth) are third-party models outside the loop and are NOT rebuilt: pass already-annotated control images, or plug callables in
+key serves control_v11p_sd15_mlsd and sd-controlnet-mlsd), and softedge, the IP-Adapter sample config's, from the user's table5_pidinet.pth
+through `annotators={"softedge": SoftedgeAnnotator.from_pretrained(path)}` (controlanimate_amd/softedge.py); the other learned detectors
+(openpose / lineart_anime / depth) are third-party models outside the loop and are NOT rebuilt: pass already-annotated control images, or plug callables in
 through `annotators`.  Of the keys contained in a ControlNet's name the longest wins (the reference tests `lineart_anime` before
 `lineart`): a `lineart` annotator never serves a `lineart_anime` net.
 """

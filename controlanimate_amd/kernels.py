@@ -1170,3 +1170,147 @@ def mlsd_draw(segments: torch.Tensor, count: torch.Tensor, h: int, w: int, edges
         dt = _CANNY_DT[control.dtype]
     check(lib().ca_mlsd_draw(_p(segments), _p(count), n, h, w, _p(edges), _p(control), int(rep), dt, _stream()), "ca_mlsd_draw")
     return edges
+
+
+# ---- added to ABI v16: the softedge (PiDiNet) annotator's stages beside conv3x3 / gemm (controlanimate_amd/softedge.py: SoftedgeAnnotator) -----------
+
+def softedge_prep(frames: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """uint8 RGB [images, H, W, 3] -> NHWC `out` [images, H, W, 8] fp16 / bf16: frames / 255 in channels 0..2, zeros in 3..7
+    (ca_softedge_prep)."""
+    _req_cuda(frames, out)
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
+    n, h, w, _ = frames.shape
+    assert tuple(out.shape) == (n, h, w, 8) and out.is_contiguous()
+    check(lib().ca_softedge_prep(_p(frames), _p(out), n, h, w, dt_code(out.dtype), _stream()), "ca_softedge_prep")
+    return out
+
+
+def relu(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """max(x, 0) of a contiguous fp16 / bf16 tensor whose element count is a multiple of 8 (ca_relu); `out` may be x."""
+    _req_cuda(x, out)
+    assert x.is_contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.is_contiguous() and out.dtype == x.dtype and out.numel() == x.numel()
+    check(lib().ca_relu(_p(x), _p(out), x.numel(), dt_code(x.dtype), _stream()), "ca_relu")
+    return out
+
+
+def _ksize_of(w: torch.Tensor, c: int) -> int:
+    assert w.dim() == 2 and w.shape[1] == c and w.shape[0] in (9, 25) and w.is_contiguous(), f"depthwise taps [9 or 25, {c}], got {tuple(w.shape)}"
+    return 3 if w.shape[0] == 9 else 5
+
+
+def dwconv_k(x: torch.Tensor, w: torch.Tensor, *, relu: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Depthwise 3x3 (padding 1) or 5x5 (padding 2) convolution of NHWC x [images, H, W, C], stride 1, no bias, optional ReLU
+    (ca_dwconv_k).  w: [9, C] or [25, C] of x's dtype (tap ky * ksize + kx of every channel: softedge.pack_depthwise)."""
+    _req_cuda(x, w, out)
+    assert x.dim() == 4 and x.is_contiguous() and w.dtype == x.dtype
+    n, h, ww, c = x.shape
+    ks = _ksize_of(w, c)
+    if out is None:
+        out = torch.empty_like(x)
+    assert tuple(out.shape) == tuple(x.shape) and out.is_contiguous() and out.dtype == x.dtype
+    check(lib().ca_dwconv_k(_p(x), _p(w), _p(out), n, h, ww, c, ks, int(relu), dt_code(x.dtype), _stream()), "ca_dwconv_k")
+    return out
+
+
+def maxpool2x2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """MaxPool2d(2, 2) of NHWC x [images, H, W, C], H and W even (ca_maxpool2x2)."""
+    _req_cuda(x, out)
+    assert x.dim() == 4 and x.is_contiguous()
+    n, h, w, c = x.shape
+    if out is None:
+        out = torch.empty((n, h // 2, w // 2, c), dtype=x.dtype, device=x.device)
+    assert out.is_contiguous() and out.dtype == x.dtype and (h % 2 or w % 2 or tuple(out.shape) == (n, h // 2, w // 2, c))
+    check(lib().ca_maxpool2x2(_p(x), _p(out), n, h, w, c, dt_code(x.dtype), _stream()), "ca_maxpool2x2")
+    return out
+
+
+def pdc_block_supported(c: int, ksize: int) -> bool:
+    """Does ca_pdc_block take this width and kernel size (no launch, no device access)?"""
+    return bool(lib().ca_pdc_block_supported(int(c), int(ksize)))
+
+
+def pdc_block(x: torch.Tensor, w_dw: torch.Tensor, w2: torch.Tensor, *, out: Optional[torch.Tensor] = None, fused: Optional[bool] = None,
+              tmp: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = x + W2 . relu(dw(x)) of NHWC x [images, H, W, C]: one stride-1 block of PiDiNet.  w_dw: [9 or 25, C]; w2: [C, C] ([cout, cin]).
+    fused (default: context.dispatch.pdc_block_fused where the library takes the width): ONE launch (ca_pdc_block); otherwise
+    dwconv_k(relu) into `tmp` and gemm(residual = x)."""
+    _req_cuda(x, w_dw, w2, out, tmp)
+    assert x.dim() == 4 and x.is_contiguous() and w_dw.dtype == x.dtype and w2.dtype == x.dtype
+    n, h, w, c = x.shape
+    ks = _ksize_of(w_dw, c)
+    assert tuple(w2.shape) == (c, c) and w2.is_contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    assert tuple(out.shape) == tuple(x.shape) and out.is_contiguous() and out.dtype == x.dtype
+    if fused is None:
+        fused = dispatch.pdc_block_fused and pdc_block_supported(c, ks)
+    if fused:
+        check(lib().ca_pdc_block(_p(x), _p(w_dw), _p(w2), _p(out), n, h, w, c, ks, dt_code(x.dtype), _stream()), "ca_pdc_block")
+        return out
+    d = dwconv_k(x, w_dw, relu=True, out=tmp)
+    m = n * h * w
+    gemm(d.view(m, c), w2, residual=x.view(m, c), out=out.view(m, c))
+    return out
+
+
+def cdcm_dil4(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The four dilated 3x3 convolutions (5, 7, 9, 11) of a CDCM, summed: NHWC x [images, H, W, 32] -> [images, H, W, 32] in one launch
+    (ca_cdcm_dil4).  w: [4, 32, 3, 3, 32] of x's dtype ([dilation index, cout, ky, kx, cin])."""
+    _req_cuda(x, w, out)
+    assert x.dim() == 4 and x.is_contiguous() and w.is_contiguous() and w.dtype == x.dtype
+    n, h, ww, c = x.shape
+    assert tuple(w.shape) == (4, c, 3, 3, c)
+    if out is None:
+        out = torch.empty_like(x)
+    assert tuple(out.shape) == tuple(x.shape) and out.is_contiguous() and out.dtype == x.dtype
+    check(lib().ca_cdcm_dil4(_p(x), _p(w), _p(out), n, h, ww, c, dt_code(x.dtype), _stream()), "ca_cdcm_dil4")
+    return out
+
+
+def csam_reduce(f: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, wr: torch.Tensor, br: torch.Tensor, *,
+                side: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """f [images, H, W, 32] -> side float32 [images, H, W] = br + sigmoid(conv3x3(b1 + W1 relu(f))) * (wr . f) (ca_csam_reduce).
+    Float32 operands: w1 [4, 32], b1 [4], w2 [3, 3, 4], wr [32], br [1]; scratch: float32, 5 * images * H * W elements."""
+    _req_cuda(f, w1, b1, w2, wr, br, side, scratch)
+    assert f.dim() == 4 and f.is_contiguous()
+    n, h, w, c = f.shape
+    for t, shape in ((w1, (4, c)), (b1, (4,)), (w2, (3, 3, 4)), (wr, (c,)), (br, (1,))):
+        assert t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous()
+    px = n * h * w
+    if side is None:
+        side = torch.empty((n, h, w), dtype=torch.float32, device=f.device)
+    if scratch is None:
+        scratch = torch.empty(5 * px, dtype=torch.float32, device=f.device)
+    assert side.dtype == torch.float32 and tuple(side.shape) == (n, h, w) and side.is_contiguous()
+    assert scratch.dtype == torch.float32 and scratch.is_contiguous() and scratch.numel() >= 5 * px
+    check(lib().ca_csam_reduce(_p(f), _p(w1), _p(b1), _p(w2), _p(wr), _p(br), _p(scratch), scratch.data_ptr() + 16 * px, _p(side), n, h, w, c,
+                               dt_code(f.dtype), _stream()), "ca_csam_reduce")
+    return side
+
+
+def softedge_fuse(sides, classifier: torch.Tensor, *, safe: bool = False, logit: Optional[torch.Tensor] = None, edges: Optional[torch.Tensor] = None,
+                  control: Optional[torch.Tensor] = None, rep: int = 1) -> None:
+    """The four float32 side maps [images, H >> k, W >> k] and the classifier (float32 [5]: four weights, the bias) -> any of the float32
+    fused logit [images, H, W], the uint8 map [images, H, W] and the control tensor [rep * images, 3, H, W] (float32 / float16, level / 255):
+    bilinear resize (align_corners = False), classifier, sigmoid, the optional safe step and quantisation in one launch (ca_softedge_fuse)."""
+    assert len(sides) == 4
+    _req_cuda(*sides, classifier, logit, edges, control)
+    n, h, w = sides[0].shape
+    for k, s in enumerate(sides):
+        assert s.dtype == torch.float32 and s.is_contiguous() and tuple(s.shape) == (n, h >> k, w >> k), f"side map {k}: {tuple(s.shape)} {s.dtype}"
+    assert classifier.dtype == torch.float32 and classifier.numel() == 5 and classifier.is_contiguous()
+    if logit is not None:
+        assert logit.dtype == torch.float32 and tuple(logit.shape) == (n, h, w) and logit.is_contiguous()
+    if edges is not None:
+        assert edges.dtype == torch.uint8 and tuple(edges.shape) == (n, h, w) and edges.is_contiguous()
+    dt = _capi.CA_F32
+    if control is not None:
+        if control.dtype not in _CANNY_DT:
+            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
+        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
+        dt = _CANNY_DT[control.dtype]
+    check(lib().ca_softedge_fuse(*[_p(s) for s in sides], _p(classifier), n, h, w, int(safe), _p(logit), _p(edges), _p(control), int(rep), dt, _stream()),
+          "ca_softedge_fuse")

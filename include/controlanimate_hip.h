@@ -869,6 +869,78 @@ int ca_mlsd_decode(const float* tp, int32_t images, int32_t h, int32_t w, float 
 int ca_mlsd_draw(const int32_t* segments, const int32_t* count, int32_t images, int32_t h, int32_t w, uint8_t* map, void* control, int32_t rep,
                  int32_t control_dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * The softedge annotator (added to ABI v16: no struct or existing function changes, the number stays).  The reference's
+ * SampleConfigIPAdapter.yaml lists control_v11p_sd15_softedge, whose frames come from controlnet_aux's PidiNetDetector
+ * (modules/controlresiduals_pipeline.py:62, 134-138): PiDiNet(60, carv4, dil = 24, sa = True) -- fifteen blocks of a depthwise
+ * pixel-difference convolution, ReLU, a 1x1 convolution and a skip at four resolutions, and per resolution a CDCM (ReLU, 1x1, four
+ * dilated 3x3 convolutions summed), a CSAM (a one-channel spatial attention) and a 1x1 reduction to a side map; the four side maps
+ * are resized to the frame, mixed by a 1x1 classifier and passed through a sigmoid.  The pixel-difference operators are linear and
+ * are folded into plain 3x3 / 5x5 kernels on the host; channels are zero-padded to 64 / 128 / 256 / 32.  The init_block is
+ * ca_conv3x3, every 1x1 convolution ca_gemm; the entry points below are the rest (controlanimate_amd/softedge.py: SoftedgeAnnotator;
+ * the specification is tests/softedge_ref.py).  Tensors are NHWC, CA_F16 or CA_BF16.  Every launch is a function of its arguments
+ * alone, with no device-to-host read and no atomics: the chain can be captured in a hipGraph and two runs give the same bits.
+ * Anything outside the stated ranges is CA_ERR_INVALID_ARG before any launch.  images * h * w < 2^31 everywhere.
+ * ------------------------------------------------------------------------------------ */
+
+/* dst [images, h, w, 8] of dtype (16-byte aligned): channel c < 3 = src[.., c] / 255 in fp32, rounded once; channels 3 .. 7 = 0
+ * (the init_block's weight is zero-padded to 8 input channels).  src uint8 RGB [images, h, w, 3]. */
+int ca_softedge_prep(const uint8_t* src, void* dst, int32_t images, int32_t h, int32_t w, int32_t dtype, void* stream);
+
+/* y = max(x, 0) over numel elements of dtype (numel a multiple of 8; both 16-byte aligned; y may be x): the ReLU in front of a
+ * CDCM's 1x1 convolution, which is no epilogue of the block that produced x (the next block reads x itself). */
+int ca_relu(const void* x, void* y, int64_t numel, int32_t dtype, void* stream);
+
+/* Depthwise ksize x ksize convolution, stride 1, padding ksize / 2, no bias:
+ * y[n, oy, ox, ch] = act(sum_{ky,kx} wt[ky * ksize + kx][ch] * x[n, oy + ky - p, ox + kx - p, ch]), zero outside the image.
+ * ksize is 3 or 5; wt [ksize * ksize][c] of dtype; relu = 1: max(., 0); c a multiple of 8 up to 256.  The fp32 sum has a fixed
+ * order -- kernel rows ascending, inside a row w0 * v0 and then fma over the columns ascending, each row's sum added to the total --
+ * and is rounded once.  x, wt, y 16-byte aligned; y must not overlap x.  (ca_dwconv3x3 is the form with a bias, ReLU6 and stride 2.) */
+int ca_dwconv_k(const void* x, const void* wt, void* y, int32_t images, int32_t h, int32_t w, int32_t c, int32_t ksize, int32_t relu, int32_t dtype,
+                void* stream);
+
+/* y [images, h / 2, w / 2, c] = the 2x2 / stride-2 maximum of x [images, h, w, c]; h and w even, c a multiple of 8 up to 1024;
+ * both 16-byte aligned. */
+int ca_maxpool2x2(const void* x, void* y, int32_t images, int32_t h, int32_t w, int32_t c, int32_t dtype, void* stream);
+
+/* A stride-1 block of the network in one launch: y = x + W2 . relu(dw(x)), x and y [images, h, w, c]; dw is the depthwise
+ * convolution of ca_dwconv_k with the same wt_dw [ksize * ksize][c] (ksize 3 or 5) and the same order of operations, its result
+ * rounded once to dtype (where the two-launch form, ca_dwconv_k and then ca_gemm with residual = x, stores it); w2 [c][c] of dtype
+ * ([cout][cin]) multiplies it on the MFMA with fp32 accumulation; the product is rounded to dtype, x added in fp32 and the sum rounded
+ * (the two roundings of ca_gemm's residual epilogue, which are those of an fp16 pipeline: conv2's output, then + x).  c must be 64
+ * (ca_pdc_block_supported(c, ksize) != 0: no launch, no device access; other widths run as the two launches).  x is read once
+ * plus a halo of ksize / 2 pixels around every 16 x 16 tile, y written once.  All four 16-byte aligned; y must not overlap x. */
+int ca_pdc_block_supported(int32_t c, int32_t ksize);
+int ca_pdc_block(const void* x, const void* wt_dw, const void* w2, void* y, int32_t images, int32_t h, int32_t w, int32_t c, int32_t ksize, int32_t dtype,
+                 void* stream);
+
+/* y [images, h, w, 32] = sum over d in (5, 7, 9, 11) of Conv2d(32, 32, 3, dilation = d, padding = d, bias = False)(x), zero outside
+ * the image, as one MFMA accumulation over K = 4 * 9 * 32 in fp32, rounded once.  wt [4][32][3][3][32] of dtype: [dilation index]
+ * [cout][ky][kx][cin].  c must be 32.  Maps smaller than a dilation are legal (the taps that miss the map add nothing).  x, wt, y
+ * 16-byte aligned; y must not overlap x. */
+int ca_cdcm_dil4(const void* x, const void* wt, void* y, int32_t images, int32_t h, int32_t w, int32_t c, int32_t dtype, void* stream);
+
+/* The CSAM and the 1x1 reduction behind it, from f [images, h, w, 32] of dtype (c must be 32), in two launches:
+ *   t[p, j] = b1[j] + sum_c w1[j][c] * max(f[p, c], 0)   (j < 4)   and   r[p] = sum_c wr[c] * f[p, c],   fp32, c ascending, fma;
+ *   side[p] = br[0] + sigmoid(sum_{ky,kx,j} w2[ky][kx][j] * t[p + (ky - 1, kx - 1), j]) * r[p],  zero outside the image, fp32.
+ * The attention is one scalar per pixel, so wr . (f * a) = a * (wr . f): the 32-channel product is never written.  w1 fp32 [4][32],
+ * b1 fp32 [4], w2 fp32 [3][3][4], wr fp32 [32], br fp32 [1] on the device; t fp32 [images, h, w, 4] (16-byte aligned) and r fp32
+ * [images, h, w] are scratch, side fp32 [images, h, w]; t, r and side must not overlap.  f 16-byte aligned. */
+int ca_csam_reduce(const void* f, const float* w1, const float* b1, const float* w2, const float* wr, const float* br, float* t, float* r, float* side,
+                   int32_t images, int32_t h, int32_t w, int32_t c, int32_t dtype, void* stream);
+
+/* The four side maps (side_k fp32 [images, h >> k, w >> k]; h and w multiples of 8) -> per output pixel: each map sampled as
+ * F.interpolate(mode = "bilinear", align_corners = False) to (h, w) samples it (per axis src = max((d + 0.5) * in / out - 0.5, 0),
+ * i0 = trunc(src), i1 = min(i0 + 1, in - 1), l1 = src - i0, l0 = 1 - l1 in fp32; columns first, l0 * a + l1 * b, then rows, every
+ * product and sum rounded; level 0 is the value itself), z = classifier[4] + sum_k classifier[k] * e_k added for k = 0 .. 3 in
+ * fp32, edge = 1 / (1 + expf(-z)) in fp32, with safe = 1 edge = trunc(edge * 3) / 2, then trunc(clip(edge * 255, 0, 255)).
+ * classifier fp32 [5] on the device (the four weights, then the bias).  Writes any of: logit fp32 [images, h, w] = z (16-byte
+ * aligned); edges, uint8 [images, h, w] (4-byte aligned); control, [rep * images, 3, h, w] of control_dtype (CA_F16 or CA_F32,
+ * aligned to four elements) with level / 255, the three channels equal and, with rep = 2, the frames written twice (the contract of
+ * ca_hed_fuse). */
+int ca_softedge_fuse(const float* side0, const float* side1, const float* side2, const float* side3, const float* classifier, int32_t images, int32_t h,
+                     int32_t w, int32_t safe, float* logit, uint8_t* edges, void* control, int32_t rep, int32_t control_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
