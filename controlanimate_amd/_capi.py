@@ -271,6 +271,15 @@ SYMBOLS = {
     "ca_cdcm_dil4": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ca_csam_reduce": (C.c_int, [C.c_void_p] * 9 + [C.c_int32] * 5 + [C.c_void_p]),
     "ca_softedge_fuse": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.c_void_p]),
+    # added to ABI v16 likewise: the lineart_anime annotator's U-Net layers (controlanimate_amd/lineart_anime.py)
+    "ca_lanime_conv_in": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p]),
+    "ca_conv4x4s2": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 7 + [C.c_void_p]),
+    "ca_im2col4x4s2": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.c_void_p]),
+    "ca_convt4x4s2": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 6 + [C.c_void_p]),
+    "ca_instnorm_act_partials_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "ca_instnorm_act": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] * 2 + [C.c_int32] * 4 + [C.c_float, C.c_int32, C.c_void_p]),
+    "ca_lanime_conv_out": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p]),
+    "ca_lanime_finish": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
 }
 
 _lib = None

@@ -16,7 +16,9 @@ line drawing of controlnet_aux's MLSDdetector from a local mlsd_large_512_fp32.p
 `annotators={"mlsd": MlsdAnnotator.from_pretrained(path)}` (it serves control_v11p_sd15_mlsd and sd-controlnet-mlsd alike).  So is
 softedge, the IP-Adapter sample config's sixth ControlNet: `SoftedgeAnnotator` (softedge.py, re-exported here) runs PiDiNet and the tail of
 controlnet_aux's PidiNetDetector from a local table5_pidinet.pth, opt-in through `annotators={"softedge":
-SoftedgeAnnotator.from_pretrained(path)}`.  The others (openpose, lineart_anime, depth) are not rebuilt: plug them in through `MultiControlNetResidualsPipeline(annotators={...})`.
+SoftedgeAnnotator.from_pretrained(path)}`.  So is lineart_anime, which every sample config lists: `LineartAnimeAnnotator`
+(lineart_anime.py, re-exported here) runs the pix2pix U-Net of controlnet_aux's LineartAnimeDetector from a local netG.pth, opt-in
+through `annotators={"lineart_anime": LineartAnimeAnnotator.from_pretrained(path)}`.  The others (openpose, depth) are not rebuilt: plug them in through `MultiControlNetResidualsPipeline(annotators={...})`.
 
 `CannyAnnotator` is the same function for a whole window of frames on the GPU (ABI v16, csrc/ca_canny.hip): opt-in through
 `annotators={"canny": CannyAnnotator(device)}`; `canny` stays the default.  `canny_edges` is its specification: the device result
@@ -33,6 +35,7 @@ except Exception:  # pragma: no cover
 
 from .hed import HedAnnotator  # noqa: E402,F401  (the learned HED detector on the GPU; torch is imported when it is used)
 from .lineart import LineartAnnotator  # noqa: E402,F401  (the learned lineart detector on the GPU, likewise)
+from .lineart_anime import LineartAnimeAnnotator  # noqa: E402,F401  (the learned anime line detector on the GPU, likewise)
 from .mlsd import MlsdAnnotator  # noqa: E402,F401  (the learned straight-line detector on the GPU, likewise)
 from .softedge import SoftedgeAnnotator  # noqa: E402,F401  (the learned soft-edge detector on the GPU, likewise)
 

@@ -17,8 +17,10 @@ and lineart, the IP-Adapter sample config's, from the user's sk_model.pth throug
 LineartAnnotator.from_pretrained(path)}` (controlanimate_amd/lineart.py), and M-LSD, which every sample config with ControlNets lists,
 from the user's mlsd_large_512_fp32.pth through `annotators={"mlsd": MlsdAnnotator.from_pretrained(path)}` (controlanimate_amd/mlsd.py; the
 key serves control_v11p_sd15_mlsd and sd-controlnet-mlsd), and softedge, the IP-Adapter sample config's, from the user's table5_pidinet.pth
-through `annotators={"softedge": SoftedgeAnnotator.from_pretrained(path)}` (controlanimate_amd/softedge.py); the other learned detectors
-(openpose / lineart_anime / depth) are third-party models outside the loop and are NOT rebuilt: pass already-annotated control images, or plug callables in
+through `annotators={"softedge": SoftedgeAnnotator.from_pretrained(path)}` (controlanimate_amd/softedge.py), and lineart_anime, which
+every sample config lists, from the user's netG.pth through `annotators={"lineart_anime": LineartAnimeAnnotator.from_pretrained(path)}`
+(controlanimate_amd/lineart_anime.py); the other learned detectors
+(openpose / depth) are third-party models outside the loop and are NOT rebuilt: pass already-annotated control images, or plug callables in
 through `annotators`.  Of the keys contained in a ControlNet's name the longest wins (the reference tests `lineart_anime` before
 `lineart`): a `lineart` annotator never serves a `lineart_anime` net.
 """

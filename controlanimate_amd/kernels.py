@@ -1068,6 +1068,127 @@ def lineart_finish(logits: torch.Tensor, edges: Optional[torch.Tensor] = None, c
     check(lib().ca_lineart_finish(_p(logits), n, h, w, _p(edges), _p(control), int(rep), dt, _stream()), "ca_lineart_finish")
 
 
+# ---- added to ABI v16: the lineart_anime annotator's U-Net layers (controlanimate_amd/lineart_anime.py: LineartAnimeAnnotator) -------------
+IN_ACT_NONE, IN_ACT_RELU, IN_ACT_LEAKY = 0, 1, 2  # the activations of instance_norm_act's outputs
+
+
+def lanime_conv_in(frames: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, l0: torch.Tensor, c0: torch.Tensor) -> None:
+    """uint8 RGB [images, H, W, 3] -> d0 = Conv2d(3, 64, 4, 2, 1)(frames / 127.5 - 1) + bias, written as l0 [images, H/2, W/2, 64] =
+    LeakyReLU(0.2)(d0) and c0[..., :64] = ReLU(d0), c0 [images, H/2, W/2, 128] (ca_lanime_conv_in).  w_packed: [64, 64] of l0's dtype
+    (lineart_anime.pack_conv_in); bias: float32 [64]."""
+    _req_cuda(frames, w_packed, bias, l0, c0)
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
+    n, h, w, _ = frames.shape
+    assert tuple(w_packed.shape) == (64, 64) and w_packed.is_contiguous() and w_packed.dtype == l0.dtype == c0.dtype
+    assert bias.dtype == torch.float32 and bias.numel() == 64 and bias.is_contiguous()
+    assert tuple(l0.shape) == (n, h // 2, w // 2, 64) and l0.is_contiguous() and tuple(c0.shape) == (n, h // 2, w // 2, 128) and c0.is_contiguous()
+    check(lib().ca_lanime_conv_in(_p(frames), _p(w_packed), _p(bias), _p(l0), _p(c0), n, h, w, dt_code(l0.dtype), _stream()), "ca_lanime_conv_in")
+
+
+# Below this many output rows conv4x4s2 runs as a gather + gemm: the level is bound by its weights.  A design choice, not the measured
+# crossover: it keeps the levels that hold the work (1 .. 4 of a 16-frame window of 512 x 768) free of an im2col tensor, although the
+# gather form measured faster up to 24576 rows (profiles/lineart_anime_bench.json: stages.conv.forms; DESIGN section 18).
+CONV4X4S2_GEMM_ROWS = 4096
+
+
+def conv4x4s2(x: torch.Tensor, w: torch.Tensor, *, bias: Optional[torch.Tensor] = None, relu: bool = False, out: Optional[torch.Tensor] = None,
+              form: Optional[str] = None, cols: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Conv2d(Cin, Cout, 4, stride=2, padding=1): x [images, H, W, Cin] -> [images, H/2, W/2, Cout]; w [Cout, 4, 4, Cin]; optional
+    float32 bias and ReLU in the epilogue.  form "tile": ca_conv4x4s2, the implicit GEMM from an LDS halo tile, without an im2col tensor;
+    form "gemm": ca_im2col4x4s2 into `cols` [rows, 16 Cin] + gemm (split-K), for the levels whose few output rows leave the tile kernel's grid
+    small while 8 MB of weights stream; None: "gemm" below CONV4X4S2_GEMM_ROWS output rows."""
+    _req_cuda(x, w, bias, out, cols)
+    assert x.dim() == 4 and x.is_contiguous() and w.dim() == 4 and w.is_contiguous() and w.dtype == x.dtype
+    n, h, wd, cin = x.shape
+    cout = w.shape[0]
+    assert tuple(w.shape) == (cout, 4, 4, cin) and form in (None, "tile", "gemm")
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.numel() == cout and bias.is_contiguous()
+    if out is None:
+        out = torch.empty((n, h // 2, wd // 2, cout), dtype=x.dtype, device=x.device)
+    assert tuple(out.shape) == (n, h // 2, wd // 2, cout) and out.is_contiguous() and out.dtype == x.dtype
+    rows = n * (h // 2) * (wd // 2)
+    if form is None:
+        form = "gemm" if rows < CONV4X4S2_GEMM_ROWS else "tile"
+    if form == "tile":
+        check(lib().ca_conv4x4s2(_p(x), _p(w), _p(bias), _p(out), n, h, wd, cin, cout, int(relu), dt_code(x.dtype), _stream()), "ca_conv4x4s2")
+        return out
+    if cols is None:
+        cols = torch.empty((rows, 16 * cin), dtype=x.dtype, device=x.device)
+    else:
+        assert cols.dtype == x.dtype and cols.is_contiguous() and cols.numel() >= rows * 16 * cin
+        cols = cols.view(-1)[: rows * 16 * cin].view(rows, 16 * cin)
+    check(lib().ca_im2col4x4s2(_p(x), _p(cols), n, h, wd, cin, dt_code(x.dtype), _stream()), "ca_im2col4x4s2")
+    gemm(cols, w.view(cout, 16 * cin), bias=bias, act=ACT_RELU if relu else ACT_NONE, out=out.view(rows, cout))
+    return out
+
+
+def conv_transpose4x4s2(x: torch.Tensor, w_phase: torch.Tensor, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ConvTranspose2d(Cin, Cout, 4, stride=2, padding=1) without bias: x [images, H, W, Cin] -> [images, 2H, 2W, Cout] as four 2x2
+    phase convolutions in one launch (ca_convt4x4s2).  w_phase [4, Cout, 2, 2, Cin]: lineart_anime.pack_convt4x4_phases."""
+    _req_cuda(x, w_phase, out)
+    assert x.dim() == 4 and x.is_contiguous() and w_phase.dim() == 5 and w_phase.is_contiguous() and w_phase.dtype == x.dtype
+    n, h, w, cin = x.shape
+    cout = w_phase.shape[1]
+    assert tuple(w_phase.shape) == (4, cout, 2, 2, cin)
+    if out is None:
+        out = torch.empty((n, 2 * h, 2 * w, cout), dtype=x.dtype, device=x.device)
+    assert tuple(out.shape) == (n, 2 * h, 2 * w, cout) and out.is_contiguous() and out.dtype == x.dtype
+    check(lib().ca_convt4x4s2(_p(x), _p(w_phase), _p(out), n, h, w, cin, cout, dt_code(x.dtype), _stream()), "ca_convt4x4s2")
+    return out
+
+
+def instance_norm_act(x: torch.Tensor, outs, *, eps: float = 1e-5, partials: Optional[torch.Tensor] = None) -> None:
+    """InstanceNorm2d(affine=False) of NHWC x [images, H, W, C] (C 64 .. 512) into one or two destinations (ca_instnorm_act).
+    outs: [(tensor [images, H, W, stride], act, channel offset)]; act is IN_ACT_NONE / IN_ACT_RELU / IN_ACT_LEAKY (0.2).  Only channels
+    offset .. offset + C of a destination are written."""
+    _req_cuda(x, partials, *[o[0] for o in outs])
+    assert x.dim() == 4 and x.is_contiguous() and 1 <= len(outs) <= 2
+    n, h, w, c = x.shape
+    args = []
+    for t, act, off in outs:
+        assert t.dim() == 4 and tuple(t.shape[:3]) == (n, h, w) and t.is_contiguous() and t.dtype == x.dtype and t.data_ptr() != x.data_ptr()
+        args += [_p(t), int(act), int(off), int(t.shape[3])]
+    if len(outs) == 1:
+        args += [None, 0, 0, 0]
+    floats = int(lib().ca_instnorm_act_partials_floats(n, h, w, c))
+    if floats <= 0:
+        raise _capi.CAHipError(f"ca_instnorm_act: images={n} h={h} w={w} c={c} is out of range (c is 64, 128, 256 or 512)")
+    if partials is None:
+        partials = torch.empty(floats, dtype=torch.float32, device=x.device)
+    assert partials.dtype == torch.float32 and partials.is_contiguous() and partials.numel() >= floats
+    check(lib().ca_instnorm_act(_p(x), _p(partials), *args, n, h, w, c, float(eps), dt_code(x.dtype), _stream()), "ca_instnorm_act")
+
+
+def lanime_conv_out(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """x [images, H, W, 128] -> `out` float32 [images, 2H, 2W]: ConvTranspose2d(128, 1, 4, 2, 1) + bias (ca_lanime_conv_out).
+    wt: float32 [4, 4, 128]; bias: float32 [1]."""
+    _req_cuda(x, wt, bias, out)
+    assert x.dim() == 4 and x.shape[3] == 128 and x.is_contiguous()
+    n, h, w, _ = x.shape
+    assert wt.dtype == torch.float32 and tuple(wt.shape) == (4, 4, 128) and wt.is_contiguous() and bias.dtype == torch.float32 and bias.numel() == 1
+    assert out.dtype == torch.float32 and tuple(out.shape) == (n, 2 * h, 2 * w) and out.is_contiguous()
+    check(lib().ca_lanime_conv_out(_p(x), _p(wt), _p(bias), _p(out), n, h, w, dt_code(x.dtype), _stream()), "ca_lanime_conv_out")
+    return out
+
+
+def lanime_finish(pre: torch.Tensor, edges: Optional[torch.Tensor] = None, control: Optional[torch.Tensor] = None, rep: int = 1) -> None:
+    """float32 pre-tanh values [images, H, W] -> the uint8 map 255 - trunc(clip(tanh * 127.5 + 127.5)) [images, H, W] and / or the
+    control tensor [rep * images, 3, H, W] (float32 / float16, map / 255) in one launch (ca_lanime_finish)."""
+    _req_cuda(pre, edges, control)
+    assert pre.dtype == torch.float32 and pre.dim() == 3 and pre.is_contiguous()
+    n, h, w = pre.shape
+    if edges is not None:
+        assert edges.dtype == torch.uint8 and tuple(edges.shape) == (n, h, w) and edges.is_contiguous()
+    dt = _capi.CA_F32
+    if control is not None:
+        if control.dtype not in _CANNY_DT:
+            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
+        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
+        dt = _CANNY_DT[control.dtype]
+    check(lib().ca_lanime_finish(_p(pre), n, h, w, _p(edges), _p(control), int(rep), dt, _stream()), "ca_lanime_finish")
+
+
 # ---- added to ABI v16: the M-LSD annotator's stages beside conv3x3 / gemm / add_bcast (controlanimate_amd/mlsd.py: MlsdAnnotator) -----------
 MLSD_TOPK = _capi.CA_MLSD_TOPK
 

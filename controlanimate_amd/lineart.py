@@ -31,7 +31,7 @@ UNPINNED.  Every convolution but the last is followed by an InstanceNorm, so act
 
 Scope of sizes: the reference calls the detector with detect_resolution = image_resolution = min(H, W) on frames floored to
 multiples of 64, for which both of the detector's resamplings are the identity.  H % 64 == 0 and W % 64 == 0 is therefore the
-scope; anything else raises NotImplementedError.  The lineart_anime detector is a different network and is not part of this.
+scope; anything else raises NotImplementedError.  The lineart_anime detector is a different network: lineart_anime.py.
 """
 from __future__ import annotations
 

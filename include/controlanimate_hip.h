@@ -941,6 +941,73 @@ int ca_csam_reduce(const void* f, const float* w1, const float* b1, const float*
 int ca_softedge_fuse(const float* side0, const float* side1, const float* side2, const float* side3, const float* classifier, int32_t images, int32_t h,
                      int32_t w, int32_t safe, float* logit, uint8_t* edges, void* control, int32_t rep, int32_t control_dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * The lineart_anime annotator (added to ABI v16: no struct or existing function changes, the number stays).  Every sample config of
+ * the reference lists control_v11p_sd15s2_lineart_anime, whose frames come from controlnet_aux's LineartAnimeDetector
+ * (modules/controlresiduals_pipeline.py:59, 119-123): the pix2pix UnetGenerator(3, 1, num_downs = 8, ngf = 64) with a non-affine
+ * InstanceNorm -- eight 4x4 stride-2 convolutions down to 1/256 of the frame, eight 4x4 stride-2 transposed convolutions back up
+ * over skip concatenations, and a tanh.  None of the entry points above runs these layers; the ones below do
+ * (controlanimate_amd/lineart_anime.py: LineartAnimeAnnotator; the specification is tests/lineart_anime_ref.py).  Tensors are NHWC,
+ * CA_F16 or CA_BF16, with fp32 accumulation.  Every activation is stored in the form its consumers read: L_i = LeakyReLU(0.2)(d_i)
+ * for the next convolution down, and a concatenation buffer C_i [images, h_i, w_i, 2 c_i] = (ReLU(d_i), ReLU(IN(up_{i+1}))) for the
+ * transposed convolution up, so no MFMA operand path applies an activation.  Every launch is a function of its arguments alone,
+ * with no device-to-host read and no atomics: the chain can be captured in a hipGraph and two runs give the same bits.  Anything
+ * outside the stated ranges is CA_ERR_INVALID_ARG before any launch.  No operand may reach 2^31 bytes.
+ * ------------------------------------------------------------------------------------ */
+
+/* d0 = Conv2d(3, 64, 4, stride 2, padding 1)(src / 127.5 - 1) + bias, the zero padding applied to the NORMALISED image: over the taps
+ * inside the frame, (sum w * byte) / 127.5 - sum w, both sums in fp32 (MFMA).  src uint8 RGB [images, h, w, 3], h and w even;
+ * w_packed [64][64] of dtype: column ky * 12 + kx * 3 + c holds weight[o][c][ky][kx], columns 48 .. 63 zero; bias fp32 [64].
+ * Writes l0 [images, h / 2, w / 2, 64] = LeakyReLU(0.2)(d0) and channels 0 .. 63 of c0 [images, h / 2, w / 2, 128] = ReLU(d0);
+ * channels 64 .. 127 of c0 are not touched.  w_packed, l0 and c0 16-byte aligned. */
+int ca_lanime_conv_in(const uint8_t* src, const void* w_packed, const float* bias, void* l0, void* c0, int32_t images, int32_t h, int32_t w,
+                      int32_t dtype, void* stream);
+
+/* y [images, h / 2, w / 2, cout] = Conv2d(cin, cout, 4, stride 2, padding 1)(x), x [images, h, w, cin] with h and w even, zero
+ * outside the image; wt [cout][4][4][cin] of dtype.  cin is 64, 128, 256 or 512; cout 128, 256 or 512.  bias (fp32 [cout], may be
+ * NULL) is added and, with relu = 1, max(., 0) applied before the one rounding.  An implicit GEMM on the MFMA whose B operand is
+ * read from an LDS tile of the input (8 x 16 output pixels x 128 output channels per block): no im2col tensor is written.
+ * x, wt, y 16-byte aligned; y must not overlap x. */
+int ca_conv4x4s2(const void* x, const void* wt, const float* bias, void* y, int32_t images, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t relu,
+                 int32_t dtype, void* stream);
+
+/* The gather in front of ca_gemm for the levels of that convolution with few output rows (they are bound by their 8 MB of weights,
+ * and ca_gemm splits K): cols [images * h / 2 * w / 2][16 * cin], column (ky * 4 + kx) * cin + ci of row (image, oy, ox) =
+ * x[image, 2 oy - 1 + ky, 2 ox - 1 + kx, ci], zero outside the image -- the row order of wt above, so that
+ * y = ca_gemm(cols, wt as [cout][16 * cin]).  cin a multiple of 8 up to 1024, h and w even.  Both 16-byte aligned. */
+int ca_im2col4x4s2(const void* x, void* cols, int32_t images, int32_t h, int32_t w, int32_t cin, int32_t dtype, void* stream);
+
+/* y [images, 2 h, 2 w, cout] = ConvTranspose2d(cin, cout, 4, stride 2, padding 1)(x) without bias, x [images, h, w, cin], as four
+ * 2x2 "phase" convolutions in ONE launch: output pixel (2 y + py, 2 x + px) = sum over dy, dx in {0, 1} of
+ * w_phase[py * 2 + px][.][dy][dx][.] . x[y + py - 1 + dy, x + px - 1 + dx], zero outside the image, where
+ * w_phase [4][cout][2][2][cin] of dtype holds weight[ci][co][3 - py - 2 dy][3 - px - 2 dx] (lineart_anime.pack_convt4x4_phases; the
+ * layout of ca_conv_up2_phase's weight).  cin is 256, 512 or 1024; cout 64, 128, 256 or 512.  No zero-stuffed tensor and no tap
+ * tensor is written.  x, w_phase, y 16-byte aligned; y must not overlap x. */
+int ca_convt4x4s2(const void* x, const void* w_phase, void* y, int32_t images, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t dtype, void* stream);
+
+/* InstanceNorm2d(affine = False) over h x w (from 1 x 1 upward) per (image, channel) of x [images, h, w, c], biased variance, c = 64,
+ * 128, 256 or 512, written to up to two outputs (y1 may be NULL): y_k[(image, pixel) * stride_k + off_k + channel] =
+ * act_k((x - mean) / sqrt(var + eps)), act 0 = none, 1 = ReLU, 2 = LeakyReLU(0.2); off_k and stride_k are multiples of 8 with
+ * off_k + c <= stride_k <= 4096, and the other channels of a destination are not touched -- one pass fills L_i and a half of C_i.
+ * fp32 statistics in a fixed order (of x minus the image's first pixel, per chunk of pixels, through `partials`, which holds the
+ * number of floats the first function returns, 0 for arguments out of range).  A chunk is 262144 / c pixels, halved down to
+ * 16384 / c while the launch has fewer than 256 blocks -- a function of the arguments alone.  A plane of one chunk runs as ONE
+ * launch, larger ones as two.  x, y0, y1 16-byte aligned; the outputs must not overlap x. */
+int64_t ca_instnorm_act_partials_floats(int32_t images, int32_t h, int32_t w, int32_t c);
+int ca_instnorm_act(const void* x, float* partials, void* y0, int32_t act0, int32_t off0, int32_t stride0, void* y1, int32_t act1, int32_t off1, int32_t stride1,
+                    int32_t images, int32_t h, int32_t w, int32_t c, float eps, int32_t dtype, void* stream);
+
+/* out fp32 [images, 2 h, 2 w] = ConvTranspose2d(128, 1, 4, stride 2, padding 1)(x) + bias, x [images, h, w, 128] of dtype (the
+ * concatenation buffer C_0); wt fp32 [4][4][128] (weight[c][0][ky][kx] at [ky][kx][c]) and bias fp32 [1] on the device; fp32
+ * accumulation in a fixed order on the VALU (512 terms per output).  x 16-byte aligned, out 8-byte aligned. */
+int ca_lanime_conv_out(const void* x, const float* wt, const float* bias, float* out, int32_t images, int32_t h, int32_t w, int32_t dtype, void* stream);
+
+/* Per pixel: level = 255 - trunc(clip(tanh(t) * 127.5 + 127.5, 0, 255)), the tanh in float64.  Writes either or both of: map, uint8
+ * [images, h, w] (4-byte aligned); control, [rep * images, 3, h, w] of control_dtype (CA_F16 or CA_F32, aligned to four elements)
+ * with level / 255, the three channels equal and, with rep = 2, the frames written twice (the contract of ca_lineart_finish).
+ * h * w a multiple of 4; pre 16-byte aligned. */
+int ca_lanime_finish(const float* pre, int32_t images, int32_t h, int32_t w, uint8_t* map, void* control, int32_t rep, int32_t control_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
