@@ -16,6 +16,7 @@ CA_F32 = 2  # control tensor of ca_canny_emit / ca_hed_fuse only
 CA_ACT_NONE, CA_ACT_SILU = 0, 1
 CA_ACT_RELU = 4  # the VGG stack of the HED annotator (hed.py)
 CA_ACT_RELU6 = 5  # the MobileNetV2 backbone of the M-LSD annotator (mlsd.py)
+CA_ACT_LEAKY02 = 6  # LeakyReLU(0.2): the U-Net and the SFT branches of the GFPGAN face restorer (gfpgan.py)
 CA_MLSD_TOPK = 200
 ABI_VERSION = 16
 
@@ -160,6 +161,17 @@ class PerceiverAttnArgs(C.Structure):  # ca_perceiver_attn_args (the IP-Adapter 
     ]
 
 
+class ModconvArgs(C.Structure):  # ca_modconv_args (the StyleConv of the GFPGAN face restorer)
+    _fields_ = [
+        ("x", C.c_void_p), ("wt", C.c_void_p), ("s", C.c_void_p), ("demod", C.c_void_p), ("noise", C.c_void_p), ("bias", C.c_void_p),
+        ("sft_scale", C.c_void_p), ("sft_shift", C.c_void_p), ("y", C.c_void_p),
+        ("s_stride", C.c_int64), ("demod_stride", C.c_int64),
+        ("images", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32),
+        ("upsample", C.c_int32), ("x_shared", C.c_int32),
+        ("noise_weight", C.c_float), ("dtype", C.c_int32),
+    ]
+
+
 # symbol -> (restype, argtypes); this table is also what tests/test_capi_symbols.py checks
 # against the declarations in include/controlanimate_hip.h.
 SYMBOLS = {
@@ -280,6 +292,15 @@ SYMBOLS = {
     "ca_instnorm_act": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] * 2 + [C.c_int32] * 4 + [C.c_float, C.c_int32, C.c_void_p]),
     "ca_lanime_conv_out": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p]),
     "ca_lanime_finish": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    # added to ABI v16 likewise: the GFPGAN face restorer's stages beside ca_conv3x3 / ca_gemm (controlanimate_amd/gfpgan.py)
+    "ca_gfp_prep": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 6 + [C.c_void_p]),
+    "ca_resample2x": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 6 + [C.c_void_p]),
+    "ca_gfp_styles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "ca_modconv3x3": (C.c_int, [C.POINTER(ModconvArgs), C.c_void_p]),
+    "ca_gfp_modulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p]),
+    "ca_gfp_style_epilogue": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_float] + [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p]),
+    "ca_gfp_to_rgb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p]),
+    "ca_gfp_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
 }
 
 _lib = None

@@ -19,6 +19,8 @@ controlnet_aux's PidiNetDetector from a local table5_pidinet.pth, opt-in through
 SoftedgeAnnotator.from_pretrained(path)}`.  So is lineart_anime, which every sample config lists: `LineartAnimeAnnotator`
 (lineart_anime.py, re-exported here) runs the pix2pix U-Net of controlnet_aux's LineartAnimeDetector from a local netG.pth, opt-in
 through `annotators={"lineart_anime": LineartAnimeAnnotator.from_pretrained(path)}`.  The others (openpose, depth) are not rebuilt: plug them in through `MultiControlNetResidualsPipeline(annotators={...})`.
+(The face restorer of the emitted frames is not an annotator and lives in gfpgan.py: GFPGANv1Clean for aligned 512 x 512 faces on the HIP
+kernels, around a caller-supplied helper for detection, warp and paste-back; UNPINNED against gfpgan and real weights; no CPU fallback.)
 
 `CannyAnnotator` is the same function for a whole window of frames on the GPU (ABI v16, csrc/ca_canny.hip): opt-in through
 `annotators={"canny": CannyAnnotator(device)}`; `canny` stays the default.  `canny_edges` is its specification: the device result

@@ -176,6 +176,7 @@ __device__ __forceinline__ float act_f(float x, int act) {
   if (act == CA_ACT_GELU) return gelu_erf_f(x);
   if (act == CA_ACT_RELU) return fmaxf(x, 0.0f);
   if (act == CA_ACT_RELU6) return fminf(fmaxf(x, 0.0f), 6.0f);
+  if (act == CA_ACT_LEAKY02) return x > 0.0f ? x : 0.2f * x;
   return x;
 }
 

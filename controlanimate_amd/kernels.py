@@ -299,7 +299,7 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, *, x2: Optional[torch.Tensor] = No
             rows_per_group: int = 0, residual: Optional[torch.Tensor] = None, stride: int = 1,
             upsample: bool = False, alpha: float = 1.0, post_scale: float = 1.0, act: int = ACT_NONE,
             out_f32: bool = False, pad_asym: bool = False, w_wino: Optional[torch.Tensor] = None,
-            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+            out: Optional[torch.Tensor] = None, split_k: bool = True) -> torch.Tensor:
     """x: [images, H, W, Cin1] (+x2 [.., Cin2]); w: [Cout, 3, 3, Cin1+Cin2]; returns NHWC (written into `out` when given: a
     contiguous tensor of the output's shape and dtype that overlaps no operand).
     pad_asym: pad (0 before, 1 after) instead of 1/1 -- diffusers Downsample2D(padding=0).
@@ -341,7 +341,9 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, *, x2: Optional[torch.Tensor] = No
     if w_wino is not None and dispatch.conv_winograd:
         assert w_wino.dtype == x.dtype and w_wino.is_contiguous() and tuple(w_wino.shape) == (16, cout, cin1 + cin2)
         args.w_wino = _p(w_wino)
-    wbytes = int(lib().ca_conv3x3_workspace_bytes(C.byref(args)))
+    # split_k=False hands over no workspace, and the library then never splits K (whether it would depends on the number of images): the
+    # order of an output's sum is the same whatever the batch (modconv3x3's composed form)
+    wbytes = int(lib().ca_conv3x3_workspace_bytes(C.byref(args))) if split_k else 0
     if wbytes > 0:  # split-K slabs for the small-M levels (allocator-cached, stream-ordered)
         ws = torch.empty((wbytes,), device=x.device, dtype=torch.uint8)
         args.workspace, args.workspace_bytes = _p(ws), wbytes
@@ -1435,3 +1437,133 @@ def softedge_fuse(sides, classifier: torch.Tensor, *, safe: bool = False, logit:
         dt = _CANNY_DT[control.dtype]
     check(lib().ca_softedge_fuse(*[_p(s) for s in sides], _p(classifier), n, h, w, int(safe), _p(logit), _p(edges), _p(control), int(rep), dt, _stream()),
           "ca_softedge_fuse")
+
+
+# ---- added to ABI v16: the GFPGAN face restorer's stages beside conv3x3 / gemm (controlanimate_amd/gfpgan.py: FaceRestorer) ------------------
+ACT_LEAKY02 = _capi.CA_ACT_LEAKY02  # LeakyReLU(0.2) in the epilogue of conv3x3 / gemm
+GFP_STYLE_FEAT = 512
+
+
+def gfp_prep(faces: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, reverse_channels: bool = True) -> torch.Tensor:
+    """uint8 [images, H, W, 3] -> `out` [images, H, W, Cout] = LeakyReLU(0.2)(conv1x1((faces / 255 - 0.5) / 0.5)), the channels read in
+    reverse order with reverse_channels (ca_gfp_prep).  wt: float32 [Cout, 3]; bias: float32 [Cout]."""
+    _req_cuda(faces, wt, bias, out)
+    assert faces.dtype == torch.uint8 and faces.dim() == 4 and faces.shape[3] == 3 and faces.is_contiguous(), "uint8 [images, H, W, 3]"
+    n, h, w, _ = faces.shape
+    cout = out.shape[3]
+    assert tuple(out.shape) == (n, h, w, cout) and out.is_contiguous()
+    assert wt.dtype == torch.float32 and tuple(wt.shape) == (cout, 3) and wt.is_contiguous() and bias.dtype == torch.float32 and bias.numel() == cout and bias.is_contiguous()
+    check(lib().ca_gfp_prep(_p(faces), _p(wt), _p(bias), _p(out), n, h, w, cout, int(bool(reverse_channels)), dt_code(out.dtype), _stream()), "ca_gfp_prep")
+    return out
+
+
+def resample2x(x: torch.Tensor, up: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The bilinear resize (align_corners = False) of NHWC x by 2 (up) or by 1/2 (H and W even: the 2x2 mean), fp32 arithmetic in torch's
+    order and one rounding (ca_resample2x)."""
+    _req_cuda(x, out)
+    assert x.dim() == 4 and x.is_contiguous()
+    n, h, w, c = x.shape
+    shape = (n, 2 * h, 2 * w, c) if up else (n, h // 2, w // 2, c)
+    if out is None:
+        out = torch.empty(shape, dtype=x.dtype, device=x.device)
+    assert tuple(out.shape) == shape and out.is_contiguous() and out.dtype == x.dtype
+    check(lib().ca_resample2x(_p(x), _p(out), n, h, w, c, int(bool(up)), dt_code(x.dtype), _stream()), "ca_resample2x")
+    return out
+
+
+def gfp_styles(latents: torch.Tensor, params: torch.Tensor, desc, out: torch.Tensor) -> torch.Tensor:
+    """Every modulated layer's per-image scales in one launch (ca_gfp_styles).  latents: float32 [images, num_latent, 512]; params: flat
+    float32 (per layer the transposed modulation weight [512, cin] + bias [cin]; per StyleConv Wsq^T [cin, cout]); desc: six integers per
+    layer (latent index, cin, cout -- 0 for a ToRGB --, w_off, wsq_off, out_off); out: float32 [images, out_stride], per layer
+    s / max|s| [cin] then demod' [cout] at out_off (a ToRGB: s [cin])."""
+    _req_cuda(latents, params, out)
+    assert latents.dtype == torch.float32 and latents.dim() == 3 and latents.shape[2] == GFP_STYLE_FEAT and latents.is_contiguous()
+    assert params.dtype == torch.float32 and params.dim() == 1 and params.is_contiguous()
+    n, num_latent, _ = latents.shape
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == n and out.is_contiguous()
+    desc = [int(v) for v in desc]
+    assert len(desc) % 6 == 0 and desc
+    arr = (C.c_int32 * len(desc))(*desc)
+    check(lib().ca_gfp_styles(_p(latents), _p(params), params.numel(), arr, len(desc) // 6, _p(out), out.shape[1], n, num_latent, _stream()), "ca_gfp_styles")
+    return out
+
+
+# From this many output pixels per image upward a StyleConv runs on the one-launch kernel, below it as three launches around ca_conv3x3
+# (measured per level, 16 faces: profiles/gfpgan_bench.json: style_convs; DESIGN section 19).
+MODCONV_FUSED_MIN_PIXELS = 512 * 512
+
+
+def modconv3x3(x: torch.Tensor, wt: torch.Tensor, s: torch.Tensor, demod: torch.Tensor, noise: torch.Tensor, bias: torch.Tensor, noise_weight: float, *,
+               upsample: bool = False, sft=None, images: Optional[int] = None, out: Optional[torch.Tensor] = None, form: Optional[str] = None,
+               scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One StyleConv: LeakyReLU(0.2)(conv3x3(wt, s[n] * X) * demod[n] * sqrt(2) + noise_weight * noise + bias), X = x or its bilinear x2, then
+    with sft = (scale, shift) [images, H, W, Cout / 2] the second half of the channels * scale + shift.
+    x [images, h, w, Cin], or [1, h, w, Cin] shared by `images` images; wt [Cout, 3, 3, Cin]; s float32 [images, Cin] and demod float32
+    [images, Cout], rows at any stride (views of gfp_styles' output); noise float32 [images, H, W]; bias float32 [Cout].
+    form "fused": ca_modconv3x3, one launch, X never written; form "composed": ca_gfp_modulate into `scratch` ([images, H, W, Cin], allocated
+    when None) + conv3x3 without split-K + ca_gfp_style_epilogue in place (one rounding more, of the convolution's output); None: "fused"
+    from MODCONV_FUSED_MIN_PIXELS output pixels per image.  Either form gives an image the same bits whatever the batch it is part of."""
+    assert form in (None, "fused", "composed")
+    sc, sh = sft if sft is not None else (None, None)
+    _req_cuda(x, wt, s, demod, noise, bias, sc, sh, out)
+    assert x.dim() == 4 and x.is_contiguous() and wt.dim() == 4 and wt.is_contiguous() and wt.dtype == x.dtype
+    nx, h, w, cin = x.shape
+    n = nx if images is None else int(images)
+    assert nx == n or nx == 1, "x holds one image per output image, or one shared by all"
+    cout = wt.shape[0]
+    assert tuple(wt.shape) == (cout, 3, 3, cin)
+    hh, ww = (2 * h, 2 * w) if upsample else (h, w)
+    assert s.dtype == torch.float32 and tuple(s.shape) == (n, cin) and s.stride(1) == 1
+    assert demod.dtype == torch.float32 and tuple(demod.shape) == (n, cout) and demod.stride(1) == 1
+    assert noise.dtype == torch.float32 and tuple(noise.shape) == (n, hh, ww) and noise.is_contiguous()
+    assert bias.dtype == torch.float32 and bias.numel() == cout and bias.is_contiguous()
+    if sc is not None:
+        for t in (sc, sh):
+            assert t.dtype == x.dtype and tuple(t.shape) == (n, hh, ww, cout // 2) and t.is_contiguous()
+    if out is None:
+        out = torch.empty((n, hh, ww, cout), dtype=x.dtype, device=x.device)
+    assert tuple(out.shape) == (n, hh, ww, cout) and out.is_contiguous() and out.dtype == x.dtype
+    s_stride, demod_stride = (s.stride(0), demod.stride(0)) if n > 1 else (0, 0)
+    if form is None:
+        form = "fused" if hh * ww >= MODCONV_FUSED_MIN_PIXELS else "composed"
+    if form == "composed":
+        if scratch is None:
+            scratch = torch.empty((n, hh, ww, cin), dtype=x.dtype, device=x.device)
+        assert tuple(scratch.shape) == (n, hh, ww, cin) and scratch.is_contiguous() and scratch.dtype == x.dtype
+        check(lib().ca_gfp_modulate(_p(x), _p(s), s_stride, _p(scratch), n, h, w, cin, int(bool(upsample)), int(nx == 1 and n > 1), dt_code(x.dtype), _stream()),
+              "ca_gfp_modulate")
+        conv3x3(scratch, wt, out=out, split_k=False)
+        check(lib().ca_gfp_style_epilogue(_p(out), _p(demod), demod_stride, _p(noise), float(noise_weight), _p(bias), _p(sc), _p(sh), _p(out), n, hh, ww, cout,
+                                          dt_code(x.dtype), _stream()), "ca_gfp_style_epilogue")
+        return out
+    args = _capi.ModconvArgs(x=_p(x), wt=_p(wt), s=_p(s), demod=_p(demod), noise=_p(noise), bias=_p(bias), sft_scale=_p(sc), sft_shift=_p(sh), y=_p(out),
+                             s_stride=s_stride, demod_stride=demod_stride, images=n, h=h, w=w, cin=cin, cout=cout, upsample=int(bool(upsample)),
+                             x_shared=int(nx == 1 and n > 1), noise_weight=float(noise_weight), dtype=dt_code(x.dtype))
+    check(lib().ca_modconv3x3(C.byref(args), _stream()), "ca_modconv3x3")
+    return out
+
+
+def gfp_to_rgb(x: torch.Tensor, wt: torch.Tensor, s: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, prev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ToRGB (ca_gfp_to_rgb): `out` float32 [images, H, W, 3] = conv1x1(wt * s[n], x) + bias + the bilinear x2 of prev (float32
+    [images, H / 2, W / 2, 3]).  x [images, H, W, Cin]; wt float32 [3, Cin]; s float32 [images, Cin] (rows at any stride); bias float32 [3]."""
+    _req_cuda(x, wt, s, bias, out, prev)
+    assert x.dim() == 4 and x.is_contiguous()
+    n, h, w, cin = x.shape
+    assert wt.dtype == torch.float32 and tuple(wt.shape) == (3, cin) and wt.is_contiguous() and bias.dtype == torch.float32 and bias.numel() == 3
+    assert s.dtype == torch.float32 and tuple(s.shape) == (n, cin) and s.stride(1) == 1
+    assert out.dtype == torch.float32 and tuple(out.shape) == (n, h, w, 3) and out.is_contiguous()
+    if prev is not None:
+        assert prev.dtype == torch.float32 and tuple(prev.shape) == (n, h // 2, w // 2, 3) and prev.is_contiguous() and h % 2 == 0 and w % 2 == 0
+    check(lib().ca_gfp_to_rgb(_p(x), _p(wt), _p(s), s.stride(0) if n > 1 else 0, _p(bias), _p(prev), _p(out), n, h, w, cin, dt_code(x.dtype), _stream()),
+          "ca_gfp_to_rgb")
+    return out
+
+
+def gfp_finish(pre: torch.Tensor, out: torch.Tensor, reverse_channels: bool = True) -> torch.Tensor:
+    """float32 [..., 3] -> uint8 of the same shape: rint((clamp(pre, -1, 1) + 1) / 2 * 255), half to even, the channel order reversed with
+    reverse_channels (ca_gfp_finish)."""
+    _req_cuda(pre, out)
+    assert pre.dtype == torch.float32 and pre.shape[-1] == 3 and pre.is_contiguous() and pre.numel() > 0
+    assert out.dtype == torch.uint8 and tuple(out.shape) == tuple(pre.shape) and out.is_contiguous()
+    check(lib().ca_gfp_finish(_p(pre), _p(out), pre.numel() // 3, int(bool(reverse_channels)), _stream()), "ca_gfp_finish")
+    return out

@@ -285,3 +285,23 @@ def load_realesrgan_state_dict(path: str = REALESRGAN_ANIME_6B_PATH) -> Dict[str
     if not isinstance(sd, dict):
         raise ValueError(f"{path}: not a state dict")
     return sd
+
+
+GFPGAN_V13_PATH = os.path.join("gfpgan", "weights", "GFPGANv1.3.pth")  # where GFPGANer keeps the file modules/upscaler.py:56 names by URL
+
+
+def load_gfpgan_state_dict(path: str = GFPGAN_V13_PATH) -> Dict[str, torch.Tensor]:
+    """The GFPGANv1Clean state dict of a local GFPGAN `.pth` file: `torch.load(weights_only=True)`, then `params_ema` if present, else
+    `params` (GFPGANer.__init__'s choice), else the mapping itself.  The reference downloads the file when it is missing; here a missing
+    file is an error naming the path."""
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"GFPGAN weights {path} do not exist (there is no network to download them; the reference reads GFPGANv1.3.pth, "
+                                f"kept at {GFPGAN_V13_PATH})")
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    if isinstance(sd, dict) and "params_ema" in sd:
+        sd = sd["params_ema"]
+    elif isinstance(sd, dict) and "params" in sd:
+        sd = sd["params"]
+    if not isinstance(sd, dict):
+        raise ValueError(f"{path}: not a state dict")
+    return sd

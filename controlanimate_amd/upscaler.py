@@ -15,8 +15,12 @@ Every convolution is ca_conv3x3_narrow (ABI v14): the dense blocks write x1 .. x
 buffer (no torch.cat), LeakyReLU(0.2) and the residual scalings `x5 * 0.2 + x` / `rdb3 * 0.2 + x` are epilogue terms, the nearest
 x2 upsamplings are folded into the gather of conv_up1 / conv_up2.  There is no CPU path.
 
-GFPGAN face restoration (use_face_enhancer) is NOT built: it is a detector + aligner + StyleGAN2 decoder of its own.  Pass a
-`face_enhancer` callable to get the reference's behaviour around it; without one, use_face_enhancer=True raises.
+GFPGAN face restoration (use_face_enhancer) is a detector + aligner + restoration network + paste-back of its own.  The network is
+built for ALIGNED 512 x 512 faces in gfpgan.py (GFPGANv1Clean on the HIP kernels, no CPU fallback, UNPINNED against gfpgan and real
+weights); face detection, the 5-point warp and the parsing-mask paste-back are facexlib's and stay the caller's.  The call that gives
+the reference's behaviour is `Upscaler(scale, face_enhancer=FaceRestorer(weights).as_face_enhancer(face_helper))` with a caller-supplied
+helper that has facexlib.FaceRestoreHelper's methods; any other `face_enhancer` callable works as before.  Nothing here changes:
+without a callable, use_face_enhancer=True still raises.
 """
 from __future__ import annotations
 
@@ -234,7 +238,7 @@ class Upscaler:
         self.upscale_first = False  # the reference ignores its argument (upscaler.py:23)
         if use_face_enhancer and face_enhancer is None:
             raise NotImplementedError("use_face_enhancer=True: GFPGAN face restoration is not built in this project; pass a "
-                                      "face_enhancer callable or use_face_enhancer=False")
+                                      "face_enhancer callable or use_face_enhancer=False")  # (gfpgan.FaceRestorer.as_face_enhancer(helper) is such a callable)
         self.face_enhancer = face_enhancer
         self.model = RRDBNet(num_in_ch=3, num_out_ch=3, num_feat=64, num_block=6, num_grow_ch=32, scale=NETSCALE)
         if state_dict is None:

@@ -46,6 +46,7 @@ extern "C" {
 #define CA_ACT_GELU 3       /* erf GELU: CLIP ViT-H vision MLP (IP-Adapter image encoder) */
 #define CA_ACT_RELU 4       /* max(x, 0): the VGG stack of the HED annotator (added to ABI v16) */
 #define CA_ACT_RELU6 5      /* min(max(x, 0), 6): the MobileNetV2 backbone of the M-LSD annotator (added to ABI v16) */
+#define CA_ACT_LEAKY02 6    /* x > 0 ? x : 0.2 x: the U-Net and the SFT branches of the GFPGAN face restorer (added to ABI v16) */
 
 int ca_abi_version(void);
 const char* ca_last_error(void);
@@ -1007,6 +1008,99 @@ int ca_lanime_conv_out(const void* x, const float* wt, const float* bias, float*
  * with level / 255, the three channels equal and, with rep = 2, the frames written twice (the contract of ca_lineart_finish).
  * h * w a multiple of 4; pre 16-byte aligned. */
 int ca_lanime_finish(const float* pre, int32_t images, int32_t h, int32_t w, uint8_t* map, void* control, int32_t rep, int32_t control_dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * The GFPGAN face restorer for aligned faces (added to ABI v16: no struct or existing function changes, the number stays).  Three
+ * of the reference's sample configs set use_face_enhancer, and every emitted frame then passes through
+ * GFPGANer(arch='clean', channel_multiplier=2).enhance (modules/upscaler.py:53-70): GFPGANv1Clean, a U-Net whose features modulate
+ * (SFT) a StyleGAN2 decoder.  The U-Net's and the SFT branches' 3x3 convolutions are ca_conv3x3 (act = CA_ACT_LEAKY02), its 1x1
+ * skips and final_linear ca_gemm; the entry points below are the rest (controlanimate_amd/gfpgan.py: FaceRestorer; the
+ * specification is tests/gfpgan_ref.py).  Tensors are NHWC, CA_F16 or CA_BF16, with fp32 accumulation.
+ *
+ * The modulated convolution keeps ONE weight for the whole batch:
+ *     modconv(x, style)[n, o] = demod[n, o] * conv(W, s[n, i] * x),   demod[n, o] = rsqrt(sum_i s[n, i]^2 Wsq[o, i] + 1e-8),
+ * Wsq[o, i] = sum over the taps of W[o, i]^2, packed once.  s is divided by its per-image largest magnitude m, and
+ * demod' = rsqrt(sum (s / m)^2 Wsq + 1e-8 / m^2) = m * demod: the product is unchanged and (s / m) * x stays inside fp16's range.
+ *
+ * Every launch is a function of its arguments alone, with no device-to-host read and no atomics: the chain can be captured in a
+ * hipGraph and two runs give the same bits.  Anything outside the stated ranges is CA_ERR_INVALID_ARG before any launch.  No operand
+ * may reach 2^31 bytes.  The bilinear resamplings are torch's align_corners = False ones at scale 2 (weights 0.25 / 0.75, the index
+ * clamped at the edges, h0 * (w0 * a + w1 * b) + h1 * (w0 * c + w1 * d) in fp32 without contraction) and 1/2 (the 2x2 mean).
+ * ------------------------------------------------------------------------------------ */
+
+/* y [images, h, w, cout] = LeakyReLU(0.2)(conv_body_first(v)), v[c] = (src[c'] / 255 - 0.5) / 0.5 with c' = 2 - c when
+ * reverse_channels (GFPGANer.enhance takes BGR and swaps; the reference hands it RGB), else c.  src uint8 [images, h, w, 3];
+ * wt fp32 [cout][3], bias fp32 [cout]; cout a multiple of 8 up to 256.  On the VALU.  y 16-byte aligned. */
+int ca_gfp_prep(const uint8_t* src, const float* wt, const float* bias, void* y, int32_t images, int32_t h, int32_t w, int32_t cout,
+                int32_t reverse_channels, int32_t dtype, void* stream);
+
+/* The bilinear resize of x [images, h, w, c] by 2 (up = 1: y [images, 2 h, 2 w, c]) or by 1/2 (up = 0, h and w even:
+ * y [images, h / 2, w / 2, c]), c a multiple of 8 up to 4096; fp32 arithmetic, one rounding.  x, y 16-byte aligned. */
+int ca_resample2x(const void* x, void* y, int32_t images, int32_t h, int32_t w, int32_t c, int32_t up, int32_t dtype, void* stream);
+
+/* One launch for every modulated layer of the decoder.  Layer l is described by six host integers desc[6 l ..]:
+ * (latent index, cin, cout, w_off, wsq_off, out_off).  With lat = latents[image][latent index] (fp32 [images][num_latent][512]):
+ *     s[i] = sum_k lat[k] * params[w_off + k * cin + i] + params[w_off + 512 * cin + i]     (the modulation Linear, transposed, then its bias)
+ * cout > 0 (a StyleConv):  m = max |s| (at least 1e-20);  out[image * out_stride + out_off + i] = s[i] / m;
+ *     out[.. + cin + o] = 1 / sqrt(sum_i (s[i] / m)^2 * params[wsq_off + i * cout + o] + 1e-8 / m^2)
+ * cout = 0 (a ToRGB, which does not demodulate): out[.. + i] = s[i].
+ * cin and cout are 64, 128, 256 or 512, at most 32 layers; all sums fp32 in index order.  The offsets are checked against
+ * params_floats and out_stride. */
+int ca_gfp_styles(const float* latents, const float* params, int64_t params_floats, const int32_t* desc, int32_t layers, float* out, int64_t out_stride,
+                  int32_t images, int32_t num_latent, void* stream);
+
+/* One StyleConv in one launch:
+ *     v = acc * demod[image][o] * sqrt(2) + noise_weight * noise[image][y][x] + bias[o],   acc = conv3x3(wt, s[image][i] * X)
+ *     v = LeakyReLU(0.2)(v);   o >= cout / 2 and sft_scale:  v = v * sft_scale[image][y][x][o - cout / 2] + sft_shift[..]
+ * X = x, or with upsample = 1 the bilinear x2 of x, computed from the low-resolution halo in LDS (the 2h x 2w input never exists in
+ * memory); zero outside the plane.  An implicit GEMM on 16x16x32 MFMAs from an LDS halo tile (8 x 16 output pixels x 128 or 64
+ * output channels per block), the input-channel scale applied while the tile is staged (one rounding of s * X).  x [images, h, w, cin],
+ * or ONE image shared by all (x_shared = 1: the decoder's constant); wt [cout][3][3][cin] of dtype; s fp32, image n at s + n * s_stride,
+ * demod fp32, image n at demod + n * demod_stride (ca_gfp_styles' output); noise fp32 [images, H, W] with H x W the output plane; bias fp32 [cout];
+ * sft_scale / sft_shift [images, H, W, cout / 2] of dtype, both or neither; y [images, H, W, cout].  cin and cout are 64, 128, 256 or
+ * 512; planes from 1 x 1 (smaller than a tile: handled by bounds).  x, wt, y, sft_* 16-byte aligned; y must not overlap x. */
+typedef struct ca_modconv_args {
+  const void* x;
+  const void* wt;
+  const float* s;
+  const float* demod;
+  const float* noise;
+  const float* bias;
+  const void* sft_scale;
+  const void* sft_shift;
+  void* y;
+  int64_t s_stride, demod_stride;
+  int32_t images, h, w, cin, cout;
+  int32_t upsample, x_shared;
+  float noise_weight;
+  int32_t dtype;
+} ca_modconv_args;
+int ca_modconv3x3(const ca_modconv_args* args, void* stream);
+
+/* The same StyleConv composed of three launches, for the planes where ca_conv3x3's tiles beat the one-launch kernel
+ * (kernels.modconv3x3 picks by the output plane):
+ *     y1 = ca_gfp_modulate:        round(s[image][i] * X), X = x [images, h, w, c] (ONE image with x_shared = 1) or, with upsample = 1, its
+ *                                  bilinear x2: [images, H, W, c] -- the staging of ca_modconv3x3 as a pass of its own
+ *     t  = ca_conv3x3(y1, wt):     no bias, no activation, and NO workspace, so that K is never split: an output's sum then has the same
+ *                                  order whatever the batch, and a batch split across passes gives the same bits
+ *     y  = ca_gfp_style_epilogue:  LeakyReLU(0.2)(t * demod[image][o] * sqrt(2) + noise_weight * noise[image][y][x] + bias[o]), then SFT on the
+ *                                  channels >= c / 2 as in ca_modconv3x3; y may be t.  t carries one rounding more than the accumulator.
+ * c is 64, 128, 256 or 512; x, y, t, sft_* 16-byte aligned; ca_gfp_modulate's y must not be x. */
+int ca_gfp_modulate(const void* x, const float* s, int64_t s_stride, void* y, int32_t images, int32_t h, int32_t w, int32_t c, int32_t upsample,
+                    int32_t x_shared, int32_t dtype, void* stream);
+int ca_gfp_style_epilogue(const void* t, const float* demod, int64_t demod_stride, const float* noise, float noise_weight, const float* bias,
+                          const void* sft_scale, const void* sft_shift, void* y, int32_t images, int32_t h, int32_t w, int32_t c, int32_t dtype, void* stream);
+
+/* ToRGB: out fp32 [images, h, w, 3] = sum_i wt[c][i] * s[image][i] * x[image, y, x, i] + bias[c] + the bilinear x2 of prev
+ * (fp32 [images, h / 2, w / 2, 3], may be NULL; h and w even then).  x [images, h, w, cin] of dtype, cin 64 .. 512; wt fp32 [3][cin];
+ * s fp32, image n at s + n * s_stride (not demodulated, not scaled).  On the VALU: the per-image wt * s lies in LDS, the sum runs in
+ * fp32 in channel order.  x 16-byte aligned. */
+int ca_gfp_to_rgb(const void* x, const float* wt, const float* s, int64_t s_stride, const float* bias, const float* prev, float* out, int32_t images,
+                  int32_t h, int32_t w, int32_t cin, int32_t dtype, void* stream);
+
+/* tensor2img(rgb2bgr, min_max = (-1, 1)): out uint8 [images * pixels][3], channel 2 - c when reverse_channels, =
+ * rint(((clamp(pre, -1, 1) + 1) / 2) * 255) in fp32, half to even (a NaN counts as -1).  pre fp32 [images * pixels][3]. */
+int ca_gfp_finish(const float* pre, uint8_t* out, int64_t pixels, int32_t reverse_channels, void* stream);
 
 #ifdef __cplusplus
 }
