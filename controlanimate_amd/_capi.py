@@ -301,6 +301,15 @@ SYMBOLS = {
     "ca_gfp_style_epilogue": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_float] + [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p]),
     "ca_gfp_to_rgb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p]),
     "ca_gfp_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    # added to ABI v16 likewise: the depth annotator's stages beside ca_gemm / ca_attention / ca_conv3x3 (controlanimate_amd/depth.py)
+    "ca_resize_pil_u8": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "ca_dpt_patches": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p]),
+    "ca_depth_to_space": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ca_dpt_head_supported": (C.c_int, [C.c_int32]),
+    "ca_dpt_head": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 5 + [C.c_void_p]),
+    "ca_dpt_logit": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]),
+    "ca_resize_bicubic_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p]),
+    "ca_depth_finish": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
 }
 
 _lib = None

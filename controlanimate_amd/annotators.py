@@ -18,7 +18,12 @@ softedge, the IP-Adapter sample config's sixth ControlNet: `SoftedgeAnnotator` (
 controlnet_aux's PidiNetDetector from a local table5_pidinet.pth, opt-in through `annotators={"softedge":
 SoftedgeAnnotator.from_pretrained(path)}`.  So is lineart_anime, which every sample config lists: `LineartAnimeAnnotator`
 (lineart_anime.py, re-exported here) runs the pix2pix U-Net of controlnet_aux's LineartAnimeDetector from a local netG.pth, opt-in
-through `annotators={"lineart_anime": LineartAnimeAnnotator.from_pretrained(path)}`.  The others (openpose, depth) are not rebuilt: plug them in through `MultiControlNetResidualsPipeline(annotators={...})`.
+through `annotators={"lineart_anime": LineartAnimeAnnotator.from_pretrained(path)}`.  So is depth, the transformers depth-estimation
+pipeline (Intel/dpt-large): `DepthAnnotator` (depth.py, re-exported here) runs DPTForDepthEstimation, the image processor's Pillow resize
+and the pipeline's post-processing from a local model directory, opt-in through `annotators={"depth":
+DepthAnnotator.from_pretrained(local_dir)}` (the key serves sd-controlnet-depth and control_v11f1p_sd15_depth alike); it is pinned
+against transformers' and Pillow's own modules.  The last one (openpose) is not rebuilt: plug it in through
+`MultiControlNetResidualsPipeline(annotators={...})`.
 (The face restorer of the emitted frames is not an annotator and lives in gfpgan.py: GFPGANv1Clean for aligned 512 x 512 faces on the HIP
 kernels, around a caller-supplied helper for detection, warp and paste-back; UNPINNED against gfpgan and real weights; no CPU fallback.)
 
@@ -40,6 +45,15 @@ from .lineart import LineartAnnotator  # noqa: E402,F401  (the learned lineart d
 from .lineart_anime import LineartAnimeAnnotator  # noqa: E402,F401  (the learned anime line detector on the GPU, likewise)
 from .mlsd import MlsdAnnotator  # noqa: E402,F401  (the learned straight-line detector on the GPU, likewise)
 from .softedge import SoftedgeAnnotator  # noqa: E402,F401  (the learned soft-edge detector on the GPU, likewise)
+
+
+def __getattr__(name):
+    # DepthAnnotator (the DPT depth estimator on the GPU) is re-exported on first use: depth.py builds on clip.py's packed-model classes,
+    # which import torch, and this module stays importable without it
+    if name == "DepthAnnotator":
+        from .depth import DepthAnnotator
+        return DepthAnnotator
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def _sobel(ch: np.ndarray):

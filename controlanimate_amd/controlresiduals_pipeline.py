@@ -19,9 +19,10 @@ from the user's mlsd_large_512_fp32.pth through `annotators={"mlsd": MlsdAnnotat
 key serves control_v11p_sd15_mlsd and sd-controlnet-mlsd), and softedge, the IP-Adapter sample config's, from the user's table5_pidinet.pth
 through `annotators={"softedge": SoftedgeAnnotator.from_pretrained(path)}` (controlanimate_amd/softedge.py), and lineart_anime, which
 every sample config lists, from the user's netG.pth through `annotators={"lineart_anime": LineartAnimeAnnotator.from_pretrained(path)}`
-(controlanimate_amd/lineart_anime.py); the other learned detectors
-(openpose / depth) are third-party models outside the loop and are NOT rebuilt: pass already-annotated control images, or plug callables in
-through `annotators`.  Of the keys contained in a ControlNet's name the longest wins (the reference tests `lineart_anime` before
+(controlanimate_amd/lineart_anime.py), and depth, the transformers depth-estimation pipeline, from a local Intel/dpt-large directory
+through `annotators={"depth": DepthAnnotator.from_pretrained(local_dir)}` (controlanimate_amd/depth.py; the key serves sd-controlnet-depth
+and control_v11f1p_sd15_depth); the last learned detector (openpose) is a third-party model outside the loop and is NOT rebuilt: pass
+already-annotated control images, or plug a callable in through `annotators`.  Of the keys contained in a ControlNet's name the longest wins (the reference tests `lineart_anime` before
 `lineart`): a `lineart` annotator never serves a `lineart_anime` net.
 """
 from __future__ import annotations

@@ -1567,3 +1567,138 @@ def gfp_finish(pre: torch.Tensor, out: torch.Tensor, reverse_channels: bool = Tr
     assert out.dtype == torch.uint8 and tuple(out.shape) == tuple(pre.shape) and out.is_contiguous()
     check(lib().ca_gfp_finish(_p(pre), _p(out), pre.numel() // 3, int(bool(reverse_channels)), _stream()), "ca_gfp_finish")
     return out
+
+
+# ---- added to ABI v16: the depth annotator's stages beside gemm / attention_spatial / conv3x3 (controlanimate_amd/depth.py: DepthAnnotator) -----------
+def _req_i32(*ts):
+    for t in ts:
+        assert t.dtype == torch.int32 and t.is_contiguous(), "int32 tables"
+
+
+def resize_pil_u8(frames: torch.Tensor, dh: int, dw: int, xbounds: torch.Tensor, xcoef: torch.Tensor, ybounds: torch.Tensor, ycoef: torch.Tensor,
+                  tmp: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Pillow's Image.resize of uint8 RGB frames [images, H, W, 3] -> [images, dh, dw, 3] (ca_resize_pil_u8): bounds int32 [out, 2] and
+    coefficients int32 [out, ksize] per axis, as depth.pil_coeffs builds them; tmp uint8 [images, H, dw, 3]."""
+    _req_cuda(frames, xbounds, xcoef, ybounds, ycoef, tmp, out)
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
+    n, sh, sw, _ = frames.shape
+    _req_i32(xbounds, xcoef, ybounds, ycoef)
+    assert tuple(xbounds.shape) == (dw, 2) and xcoef.dim() == 2 and xcoef.shape[0] == dw and tuple(ybounds.shape) == (dh, 2) and ycoef.dim() == 2 and ycoef.shape[0] == dh
+    if tmp is None:
+        tmp = torch.empty((n, sh, dw, 3), dtype=torch.uint8, device=frames.device)
+    if out is None:
+        out = torch.empty((n, dh, dw, 3), dtype=torch.uint8, device=frames.device)
+    assert tmp.dtype == torch.uint8 and tmp.is_contiguous() and tmp.numel() >= n * sh * dw * 3
+    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n, dh, dw, 3)
+    check(lib().ca_resize_pil_u8(_p(frames), _p(tmp), _p(out), n, sh, sw, dh, dw, _p(xbounds), _p(xcoef), xcoef.shape[1], _p(ybounds), _p(ycoef), ycoef.shape[1],
+                                 _stream()), "ca_resize_pil_u8")
+    return out
+
+
+def dpt_patches(frames: torch.Tensor, patch: int, dtype: torch.dtype, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 RGB [images, S, S, 3] -> (x / 255 - 0.5) / 0.5 as patch rows [images * (S / patch)^2, 3 * patch * patch] in the (c, ky, kx)
+    order of the patch-embedding weight (ca_dpt_patches)."""
+    _req_cuda(frames, out)
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
+    n, s, s2, _ = frames.shape
+    assert s == s2 and patch > 0 and s % patch == 0
+    rows = n * (s // patch) ** 2
+    if out is None:
+        out = torch.empty((rows, 3 * patch * patch), dtype=dtype, device=frames.device)
+    assert tuple(out.shape) == (rows, 3 * patch * patch) and out.is_contiguous() and out.dtype == dtype
+    check(lib().ca_dpt_patches(_p(frames), _p(out), n, s, patch, dt_code(dtype), _stream()), "ca_dpt_patches")
+    return out
+
+
+def depth_to_space(x: torch.Tensor, images: int, gh: int, gw: int, k: int, cout: int, *, rows_per_image: Optional[int] = None, row0: int = 0,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The scatter behind ConvTranspose2d(kernel = stride = k) as a GEMM with N = k * k * cout (ca_depth_to_space): x [rows, >= k * k * cout]
+    (columns (ky, kx, co)), row images * rows_per_image + row0 + y * gw + x -> NHWC [images, gh * k, gw * k, cout]."""
+    _req_cuda(x, out)
+    assert x.dim() == 2 and x.stride(1) == 1
+    rpi = gh * gw if rows_per_image is None else rows_per_image
+    assert x.shape[0] >= images * rpi and x.shape[1] >= k * k * cout
+    if out is None:
+        out = torch.empty((images, gh * k, gw * k, cout), dtype=x.dtype, device=x.device)
+    assert tuple(out.shape) == (images, gh * k, gw * k, cout) and out.is_contiguous() and out.dtype == x.dtype
+    check(lib().ca_depth_to_space(_p(x), _p(out), images, gh, gw, k, cout, x.stride(0), rpi, row0, dt_code(x.dtype), _stream()), "ca_depth_to_space")
+    return out
+
+
+def dpt_head_supported(cmid: int) -> bool:
+    """Does ca_dpt_head take this width (no launch, no device access)?"""
+    return bool(lib().ca_dpt_head_supported(int(cmid)))
+
+
+def dpt_head(x: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor, *, out: Optional[torch.Tensor] = None,
+             fused: Optional[bool] = None, up: Optional[torch.Tensor] = None, mid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """head.head.1 .. 5 of DPTDepthEstimationHead on x [images, h, w, Cmid]: align-corners bilinear x2, Conv3x3(Cmid -> 32) + bias + ReLU,
+    Conv1x1(32 -> 1) + bias + ReLU -> float32 [images, 2h, 2w].  w2: [32, 3, 3, Cmid] of x's dtype; b2, w3 float32 [32]; b3 float32 [1].
+    fused (default: context.dispatch.dpt_head_fused, which is off, where the library takes the width): ONE launch that never writes the
+    upsampled plane (ca_dpt_head); otherwise upsample2x_bilinear_ac into `up`, conv3x3(act=RELU, out_f32) into `mid` and ca_dpt_logit -- the
+    faster form as measured (profiles/depth_bench.json), and the default."""
+    _req_cuda(x, w2, b2, w3, b3, out, up, mid)
+    assert x.dim() == 4 and x.is_contiguous() and w2.dtype == x.dtype and w2.is_contiguous()
+    n, h, w, c = x.shape
+    assert tuple(w2.shape) == (32, 3, 3, c)
+    for t, k in ((b2, 32), (w3, 32), (b3, 1)):
+        assert t.dtype == torch.float32 and t.numel() == k and t.is_contiguous()
+    if out is None:
+        out = torch.empty((n, 2 * h, 2 * w), dtype=torch.float32, device=x.device)
+    assert tuple(out.shape) == (n, 2 * h, 2 * w) and out.is_contiguous() and out.dtype == torch.float32
+    if fused is None:
+        fused = dispatch.dpt_head_fused and dpt_head_supported(c)
+    if fused:
+        check(lib().ca_dpt_head(_p(x), _p(w2), _p(b2), _p(w3), _p(b3), _p(out), n, h, w, c, dt_code(x.dtype), _stream()), "ca_dpt_head")
+        return out
+    if up is None:
+        up = torch.empty((n, 2 * h, 2 * w, c), dtype=x.dtype, device=x.device)
+    upsample2x_bilinear_ac(x, up)
+    mid = conv3x3(up, w2, bias=b2, act=ACT_RELU, out_f32=True, out=mid)
+    check(lib().ca_dpt_logit(_p(mid), _p(w3), _p(b3), _p(out), n * 4 * h * w, _stream()), "ca_dpt_logit")
+    return out
+
+
+def resize_bicubic_f32(x: torch.Tensor, dh: int, dw: int, *, out: Optional[torch.Tensor] = None, keys: Optional[torch.Tensor] = None,
+                       minmax: Optional[torch.Tensor] = None):
+    """F.interpolate(mode="bicubic", align_corners=False) of float32 [images, h, w] -> (out [images, dh, dw], keys): keys int32 [images, 2] is
+    the per-image (max, min) of `out` in the order-preserving encoding depth_finish reads; minmax float32 [images, 2] receives them as
+    floats when given (ca_resize_bicubic_f32)."""
+    _req_cuda(x, out, keys, minmax)
+    assert x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()
+    n, h, w = x.shape
+    if out is None:
+        out = torch.empty((n, dh, dw), dtype=torch.float32, device=x.device)
+    if keys is None:
+        keys = torch.empty((n, 2), dtype=torch.int32, device=x.device)
+    assert tuple(out.shape) == (n, dh, dw) and out.is_contiguous() and out.dtype == torch.float32
+    assert keys.dtype == torch.int32 and keys.is_contiguous() and keys.numel() >= 2 * n
+    if minmax is not None:
+        assert minmax.dtype == torch.float32 and minmax.is_contiguous() and minmax.numel() >= 2 * n
+    check(lib().ca_resize_bicubic_f32(_p(x), _p(out), _p(keys), _p(minmax), n, h, w, dh, dw, _stream()), "ca_resize_bicubic_f32")
+    return out, keys
+
+
+DEPTH_NORMALIZE = {"max": 0, "minmax": 1}
+
+
+def depth_finish(depth: torch.Tensor, keys: torch.Tensor, normalize: str = "max", *, map: Optional[torch.Tensor] = None, control: Optional[torch.Tensor] = None,
+                 rep: int = 1) -> None:
+    """float32 depth [images, H, W] and resize_bicubic_f32's keys -> the uint8 map [images, H, W] and / or the control tensor
+    [rep * images, 3, H, W] (float32 / float16, map / 255) in one launch (ca_depth_finish).  "max": trunc(d * 255 / max); "minmax":
+    trunc((d - min) / (max - min) * 255); values <= -1 saturate to 0."""
+    _req_cuda(depth, keys, map, control)
+    assert depth.dtype == torch.float32 and depth.dim() == 3 and depth.is_contiguous()
+    n, h, w = depth.shape
+    assert keys.dtype == torch.int32 and keys.is_contiguous() and keys.numel() >= 2 * n
+    if normalize not in DEPTH_NORMALIZE:
+        raise ValueError(f"normalize={normalize!r} ('max' or 'minmax')")
+    if map is not None:
+        assert map.dtype == torch.uint8 and tuple(map.shape) == (n, h, w) and map.is_contiguous()
+    dt = _capi.CA_F32
+    if control is not None:
+        if control.dtype not in _CANNY_DT:
+            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
+        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
+        dt = _CANNY_DT[control.dtype]
+    check(lib().ca_depth_finish(_p(depth), _p(keys), n, h, w, DEPTH_NORMALIZE[normalize], _p(map), _p(control), int(rep), dt, _stream()), "ca_depth_finish")

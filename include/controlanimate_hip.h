@@ -1102,6 +1102,49 @@ int ca_gfp_to_rgb(const void* x, const float* wt, const float* s, int64_t s_stri
  * rint(((clamp(pre, -1, 1) + 1) / 2) * 255) in fp32, half to even (a NaN counts as -1).  pre fp32 [images * pixels][3]. */
 int ca_gfp_finish(const float* pre, uint8_t* out, int64_t pixels, int32_t reverse_channels, void* stream);
 
+/* ---- added to ABI v16: the depth annotator's stages beside ca_gemm / ca_attention / ca_conv3x3 (controlanimate_amd/depth.py) ---- */
+
+/* Pillow's Image.resize of uint8 RGB frames src [images, sh, sw, 3] -> dst [images, dh, dw, 3], as Resample.c runs it for 8-bit pixels: a
+ * horizontal pass into tmp [images, sh, dw, 3], then a vertical one.  Output index i of a pass reads the bounds[2 i + 1] source samples from
+ * bounds[2 i] on through the int32 coefficients coef[i * ksize ..] (22 fractional bits), adds 2^21, shifts by 22 and clips to 0 .. 255.  The
+ * tables are device memory, built by the host (depth.pil_coeffs); the bounds are clamped to the source.  Two launches. */
+int ca_resize_pil_u8(const uint8_t* src, uint8_t* tmp, uint8_t* dst, int32_t images, int32_t sh, int32_t sw, int32_t dh, int32_t dw, const int32_t* xbounds,
+                     const int32_t* xcoef, int32_t xksize, const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, void* stream);
+
+/* uint8 RGB src [images, size, size, 3] -> out [images * (size / patch)^2][3 * patch * patch] of dtype: (src / 255 - 0.5) / 0.5, column
+ * (c * patch + ky) * patch + kx -- the flattening of a Conv2d(3, C, patch, stride patch) weight.  patch a multiple of 8. */
+int ca_dpt_patches(const uint8_t* src, void* out, int32_t images, int32_t size, int32_t patch, int32_t dtype, void* stream);
+
+/* The scatter behind ConvTranspose2d(kernel = stride = k) run as a GEMM with N = k * k * cout: y [images, gh * k, gw * k, cout] pixel
+ * (sy * k + ky, sx * k + kx) = columns (ky * k + kx) * cout .. of row image * rows_per_image + row0 + sy * gw + sx of x (row stride ldx
+ * elements).  k is 1 (a gather of rows into a contiguous plane), 2 or 4; cout a multiple of 8; both 16-byte aligned. */
+int ca_depth_to_space(const void* x, void* y, int32_t images, int32_t gh, int32_t gw, int32_t k, int32_t cout, int64_t ldx, int32_t rows_per_image,
+                      int32_t row0, int32_t dtype, void* stream);
+
+/* The tail of the DPT depth head in one launch: out fp32 [images, 2h, 2w] =
+ *     max(sum_c w3[c] * max(conv3x3(w2, U)[c] + b2[c], 0) + b3, 0),   U = the align-corners bilinear x2 of x [images, h, w, cmid] of dtype,
+ * rounded to dtype as ca_upsample2x_bilinear_ac rounds it and zero outside the 2h x 2w plane.  U is never written.  w2 [32][3][3][cmid] of
+ * dtype, b2 fp32 [32], w3 fp32 [32], b3 fp32 [1].  cmid is 32, 64 or 128 (ca_dpt_head_supported: no launch); x and w2 16-byte aligned. */
+int ca_dpt_head_supported(int32_t cmid);
+int ca_dpt_head(const void* x, const void* w2, const float* b2, const float* w3, const float* b3, float* out, int32_t images, int32_t h, int32_t w,
+                int32_t cmid, int32_t dtype, void* stream);
+/* The last step of the same head composed of ca_upsample2x_bilinear_ac + ca_conv3x3(CA_ACT_RELU, out_f32): out[p] =
+ * max(sum_c w3[c] * t[p][c] + b3, 0) over t fp32 [pixels][32]. */
+int ca_dpt_logit(const float* t, const float* w3, const float* b3, float* out, int64_t pixels, void* stream);
+
+/* torch's interpolate(mode = "bicubic", align_corners = False) of fp32 planes src [images, sh, sw] -> dst [images, dh, dw] (A = -0.75,
+ * clamped indices, no antialias), and the per-image maximum and minimum of dst: minmax_keys receives 2 * images uint32 (max, min) in an
+ * order-preserving encoding (what ca_depth_finish reads), minmax (may be NULL) the same as fp32.  Two or three launches. */
+int ca_resize_bicubic_f32(const float* src, float* dst, void* minmax_keys, float* minmax, int32_t images, int32_t sh, int32_t sw, int32_t dh, int32_t dw,
+                          void* stream);
+
+/* depth fp32 [images, h, w] and ca_resize_bicubic_f32's minmax_keys -> the uint8 map [images, h, w] (may be NULL) and / or the control
+ * tensor [rep * images, 3, h, w] of control_dtype (CA_F32 / CA_F16; map / 255, three equal channels, the frames written rep = 1 or 2 times).
+ * mode 0: d * 255 / max;  mode 1: (d - min) / (max - min) * 255; fp32, operation for operation, truncated toward zero.  A value <= -1
+ * saturates to 0, a NaN counts as 0; max <= 0 (mode 0) or max <= min (mode 1) gives an all-zero map. */
+int ca_depth_finish(const float* depth, const void* minmax_keys, int32_t images, int32_t h, int32_t w, int32_t mode, uint8_t* map, void* control, int32_t rep,
+                    int32_t control_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
