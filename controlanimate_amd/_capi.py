@@ -18,6 +18,8 @@ CA_ACT_RELU = 4  # the VGG stack of the HED annotator (hed.py)
 CA_ACT_RELU6 = 5  # the MobileNetV2 backbone of the M-LSD annotator (mlsd.py)
 CA_ACT_LEAKY02 = 6  # LeakyReLU(0.2): the U-Net and the SFT branches of the GFPGAN face restorer (gfpgan.py)
 CA_MLSD_TOPK = 200
+CA_POSE_MAX_PEAKS, CA_POSE_MAX_PEOPLE, CA_POSE_AREA_TAPS = 64, 64, 8  # the OpenPose annotator (openpose.py)
+CA_POSE_OVERFLOW_PEAKS, CA_POSE_OVERFLOW_PEOPLE = 1, 2
 ABI_VERSION = 16
 
 
@@ -172,6 +174,15 @@ class ModconvArgs(C.Structure):  # ca_modconv_args (the StyleConv of the GFPGAN 
     ]
 
 
+class Conv7x7Args(C.Structure):  # ca_conv7x7_args (the refinement stages of the OpenPose annotator)
+    _fields_ = [
+        ("x", C.c_void_p * 2), ("w", C.c_void_p * 2), ("bias", C.c_void_p * 2), ("y", C.c_void_p * 2),
+        ("ldx", C.c_int64), ("ldy", C.c_int64),
+        ("groups", C.c_int32), ("images", C.c_int32), ("h", C.c_int32), ("w_px", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32),
+        ("relu", C.c_int32), ("dtype", C.c_int32),
+    ]
+
+
 # symbol -> (restype, argtypes); this table is also what tests/test_capi_symbols.py checks
 # against the declarations in include/controlanimate_hip.h.
 SYMBOLS = {
@@ -310,6 +321,17 @@ SYMBOLS = {
     "ca_dpt_logit": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]),
     "ca_resize_bicubic_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p]),
     "ca_depth_finish": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    # added to ABI v16 likewise: the OpenPose body annotator's stages beside ca_conv3x3 / ca_maxpool2x2 / ca_gemm (controlanimate_amd/openpose.py)
+    "ca_pose_prep": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 8 + [C.c_void_p]),
+    "ca_conv7x7": (C.c_int, [C.POINTER(Conv7x7Args), C.c_void_p]),
+    "ca_im2col7x7": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 4 + [C.c_int64, C.c_int32, C.c_void_p]),
+    "ca_copy_cols": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "ca_pose_maps_workspace_bytes": (C.c_int64, [C.c_int32] * 3),
+    "ca_pose_maps": (C.c_int, [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p]),
+    "ca_pose_peaks": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p]),
+    "ca_pose_connect": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p]),
+    "ca_pose_assemble": (C.c_int, [C.c_void_p] * 9 + [C.c_int32] * 3 + [C.c_void_p]),
+    "ca_pose_draw": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 5 + [C.c_void_p]),
 }
 
 _lib = None

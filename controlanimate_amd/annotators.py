@@ -22,8 +22,11 @@ through `annotators={"lineart_anime": LineartAnimeAnnotator.from_pretrained(path
 pipeline (Intel/dpt-large): `DepthAnnotator` (depth.py, re-exported here) runs DPTForDepthEstimation, the image processor's Pillow resize
 and the pipeline's post-processing from a local model directory, opt-in through `annotators={"depth":
 DepthAnnotator.from_pretrained(local_dir)}` (the key serves sd-controlnet-depth and control_v11f1p_sd15_depth alike); it is pinned
-against transformers' and Pillow's own modules.  The last one (openpose) is not rebuilt: plug it in through
-`MultiControlNetResidualsPipeline(annotators={...})`.
+against transformers' and Pillow's own modules.  So is openpose, the first ControlNet of three sample configs: `OpenposeAnnotator`
+(openpose.py, re-exported here) runs bodypose_model, the skeleton decode and the drawing of controlnet_aux's OpenposeDetector on the
+device from a local body_pose_model.pth, opt-in through `annotators={"openpose": OpenposeAnnotator.from_pretrained(path)}` (the key serves
+control_v11p_sd15_openpose and sd-controlnet-openpose alike).  It draws the BODY skeleton only: the hands and faces of the reference's
+hand_and_face=True are not part of it.
 (The face restorer of the emitted frames is not an annotator and lives in gfpgan.py: GFPGANv1Clean for aligned 512 x 512 faces on the HIP
 kernels, around a caller-supplied helper for detection, warp and paste-back; UNPINNED against gfpgan and real weights; no CPU fallback.)
 
@@ -45,6 +48,7 @@ from .lineart import LineartAnnotator  # noqa: E402,F401  (the learned lineart d
 from .lineart_anime import LineartAnimeAnnotator  # noqa: E402,F401  (the learned anime line detector on the GPU, likewise)
 from .mlsd import MlsdAnnotator  # noqa: E402,F401  (the learned straight-line detector on the GPU, likewise)
 from .softedge import SoftedgeAnnotator  # noqa: E402,F401  (the learned soft-edge detector on the GPU, likewise)
+from .openpose import OpenposeAnnotator  # noqa: E402,F401  (the learned body-pose detector on the GPU, likewise)
 
 
 def __getattr__(name):

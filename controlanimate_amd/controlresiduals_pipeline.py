@@ -21,8 +21,10 @@ through `annotators={"softedge": SoftedgeAnnotator.from_pretrained(path)}` (cont
 every sample config lists, from the user's netG.pth through `annotators={"lineart_anime": LineartAnimeAnnotator.from_pretrained(path)}`
 (controlanimate_amd/lineart_anime.py), and depth, the transformers depth-estimation pipeline, from a local Intel/dpt-large directory
 through `annotators={"depth": DepthAnnotator.from_pretrained(local_dir)}` (controlanimate_amd/depth.py; the key serves sd-controlnet-depth
-and control_v11f1p_sd15_depth); the last learned detector (openpose) is a third-party model outside the loop and is NOT rebuilt: pass
-already-annotated control images, or plug a callable in through `annotators`.  Of the keys contained in a ControlNet's name the longest wins (the reference tests `lineart_anime` before
+and control_v11f1p_sd15_depth), and openpose, the first ControlNet of three sample configs, from the user's body_pose_model.pth through
+`annotators={"openpose": OpenposeAnnotator.from_pretrained(path)}` (controlanimate_amd/openpose.py; the key serves
+control_v11p_sd15_openpose and sd-controlnet-openpose; the body skeleton only, not the hands and faces of the reference's
+hand_and_face=True).  For any other net pass already-annotated control images, or plug a callable in through `annotators`.  Of the keys contained in a ControlNet's name the longest wins (the reference tests `lineart_anime` before
 `lineart`): a `lineart` annotator never serves a `lineart_anime` net.
 """
 from __future__ import annotations

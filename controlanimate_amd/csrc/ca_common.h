@@ -220,4 +220,70 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
   return base + idx;
 }
 
+// cv2.line(img, pt1, pt2, color, 1, 8) on an h x w image: OpenCV's clipLine, then LineIterator(connectivity 8, left to right); put(x, y) is
+// called for every pixel of the line, each inside the image (k_mlsd_draw, k_pose_raster; tests/mlsd_ref.py: clip_line, line_pixels).
+template <typename Put>
+__device__ __forceinline__ void cv_line8(int h, int w, long long x1, long long y1, long long x2, long long y2, Put put) {
+  const long long right = w - 1, bottom = h - 1;
+  int c1 = (x1 < 0) + (x1 > right) * 2 + (y1 < 0) * 4 + (y1 > bottom) * 8;
+  int c2 = (x2 < 0) + (x2 > right) * 2 + (y2 < 0) * 4 + (y2 > bottom) * 8;
+  if ((c1 & c2) == 0 && (c1 | c2) != 0) {
+    long long a;
+    if (c1 & 12) {
+      a = c1 < 8 ? 0 : bottom;
+      x1 += (long long)((double)(a - y1) * (double)(x2 - x1) / (double)(y2 - y1));
+      y1 = a;
+      c1 = (x1 < 0) + (x1 > right) * 2;
+    }
+    if (c2 & 12) {
+      a = c2 < 8 ? 0 : bottom;
+      x2 += (long long)((double)(a - y2) * (double)(x2 - x1) / (double)(y2 - y1));
+      y2 = a;
+      c2 = (x2 < 0) + (x2 > right) * 2;
+    }
+    if ((c1 & c2) == 0 && (c1 | c2) != 0) {
+      if (c1) {
+        a = c1 == 1 ? 0 : right;
+        y1 += (long long)((double)(a - x1) * (double)(y2 - y1) / (double)(x2 - x1));
+        x1 = a;
+        c1 = 0;
+      }
+      if (c2) {
+        a = c2 == 1 ? 0 : right;
+        y2 += (long long)((double)(a - x2) * (double)(y2 - y1) / (double)(x2 - x1));
+        x2 = a;
+        c2 = 0;
+      }
+    }
+  }
+  if ((c1 | c2) != 0) return;
+  long long dx = x2 - x1, dy = y2 - y1;
+  if (dx < 0) {
+    dx = -dx, dy = -dy;
+    x1 = x2, y1 = y2;
+  }
+  const int ystep = dy < 0 ? -1 : 1;
+  dy = dy < 0 ? -dy : dy;
+  const bool vert = dy > dx;
+  if (vert) {
+    const long long tmp = dx;
+    dx = dy, dy = tmp;
+  }
+  long long err = dx - 2 * dy;
+  const long long plus = 2 * dx, minus = -2 * dy;
+  long long px = x1, py = y1;
+  for (long long i = 0; i <= dx; ++i) {  // (clipped: fewer than max(h, w) steps)
+    if (px >= 0 && px <= right && py >= 0 && py <= bottom) put(px, py);
+    const bool neg = err < 0;
+    err += minus + (neg ? plus : 0);
+    if (vert) {
+      px += neg ? 1 : 0;
+      py += ystep;
+    } else {
+      py += neg ? ystep : 0;
+      px += 1;
+    }
+  }
+}
+
 static inline int ceil_div_i(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

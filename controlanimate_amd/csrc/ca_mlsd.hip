@@ -391,68 +391,8 @@ __global__ __launch_bounds__(256) void k_mlsd_draw(const int32_t* __restrict__ s
   n = n < 0 ? 0 : (n > kTopK ? kTopK : n);
   if (s >= n) return;
   const int32_t* sg = segments + (int64_t)idx * 4;
-  long long x1 = sg[0], y1 = sg[1], x2 = sg[2], y2 = sg[3];
-  const long long right = w - 1, bottom = h - 1;
-  int c1 = (x1 < 0) + (x1 > right) * 2 + (y1 < 0) * 4 + (y1 > bottom) * 8;
-  int c2 = (x2 < 0) + (x2 > right) * 2 + (y2 < 0) * 4 + (y2 > bottom) * 8;
-  if ((c1 & c2) == 0 && (c1 | c2) != 0) {
-    long long a;
-    if (c1 & 12) {
-      a = c1 < 8 ? 0 : bottom;
-      x1 += (long long)((double)(a - y1) * (double)(x2 - x1) / (double)(y2 - y1));
-      y1 = a;
-      c1 = (x1 < 0) + (x1 > right) * 2;
-    }
-    if (c2 & 12) {
-      a = c2 < 8 ? 0 : bottom;
-      x2 += (long long)((double)(a - y2) * (double)(x2 - x1) / (double)(y2 - y1));
-      y2 = a;
-      c2 = (x2 < 0) + (x2 > right) * 2;
-    }
-    if ((c1 & c2) == 0 && (c1 | c2) != 0) {
-      if (c1) {
-        a = c1 == 1 ? 0 : right;
-        y1 += (long long)((double)(a - x1) * (double)(y2 - y1) / (double)(x2 - x1));
-        x1 = a;
-        c1 = 0;
-      }
-      if (c2) {
-        a = c2 == 1 ? 0 : right;
-        y2 += (long long)((double)(a - x2) * (double)(y2 - y1) / (double)(x2 - x1));
-        x2 = a;
-        c2 = 0;
-      }
-    }
-  }
-  if ((c1 | c2) != 0) return;
-  long long dx = x2 - x1, dy = y2 - y1;
-  if (dx < 0) {
-    dx = -dx, dy = -dy;
-    x1 = x2, y1 = y2;
-  }
-  const int ystep = dy < 0 ? -1 : 1;
-  dy = dy < 0 ? -dy : dy;
-  const bool vert = dy > dx;
-  if (vert) {
-    const long long tmp = dx;
-    dx = dy, dy = tmp;
-  }
-  long long err = dx - 2 * dy;
-  const long long plus = 2 * dx, minus = -2 * dy;
-  long long px = x1, py = y1;
   uint8_t* m = map + (int64_t)img * h * w;
-  for (long long i = 0; i <= dx; ++i) {
-    if (px >= 0 && px <= right && py >= 0 && py <= bottom) m[py * w + px] = 255;
-    const bool neg = err < 0;
-    err += minus + (neg ? plus : 0);
-    if (vert) {
-      px += neg ? 1 : 0;
-      py += ystep;
-    } else {
-      py += neg ? ystep : 0;
-      px += 1;
-    }
-  }
+  cv_line8(h, w, sg[0], sg[1], sg[2], sg[3], [m, w](long long px, long long py) { m[py * w + px] = 255; });
 }
 
 template <typename T>

@@ -1702,3 +1702,181 @@ def depth_finish(depth: torch.Tensor, keys: torch.Tensor, normalize: str = "max"
         assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
         dt = _CANNY_DT[control.dtype]
     check(lib().ca_depth_finish(_p(depth), _p(keys), n, h, w, DEPTH_NORMALIZE[normalize], _p(map), _p(control), int(rep), dt, _stream()), "ca_depth_finish")
+
+
+# ---- added to ABI v16: the OpenPose body annotator's stages beside conv3x3 / maxpool2x2 / gemm (controlanimate_amd/openpose.py: OpenposeAnnotator) ----
+
+POSE_MAX_PEAKS, POSE_MAX_PEOPLE, POSE_AREA_TAPS = _capi.CA_POSE_MAX_PEAKS, _capi.CA_POSE_MAX_PEOPLE, _capi.CA_POSE_AREA_TAPS
+POSE_OVERFLOW_PEAKS, POSE_OVERFLOW_PEOPLE = _capi.CA_POSE_OVERFLOW_PEAKS, _capi.CA_POSE_OVERFLOW_PEOPLE
+POSE_PARTS, POSE_LIMBS, POSE_PAF = 18, 19, 38
+
+
+def pose_prep(frames: torch.Tensor, tables, hs: int, ws: int, out: torch.Tensor) -> torch.Tensor:
+    """uint8 RGB [images, H, W, 3] -> `out` [images, hp, wp, 8] fp16 / bf16: the INTER_AREA resize to hs x ws through the per-axis tables
+    (xofs, xcnt, xw, yofs, ycnt, yw: openpose.area_tables), BGR, x / 256 - 0.5, zeros in the padding and in channels 3 .. 7 (ca_pose_prep)."""
+    _req_cuda(frames, out, *tables)
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
+    n, h, w, _ = frames.shape
+    hp, wp = out.shape[1], out.shape[2]
+    assert tuple(out.shape) == (n, hp, wp, 8) and out.is_contiguous()
+    xofs, xcnt, xw, yofs, ycnt, yw = tables
+    _req_i32(xofs, xcnt, yofs, ycnt)
+    assert xofs.numel() == ws and xcnt.numel() == ws and tuple(xw.shape) == (ws, POSE_AREA_TAPS) and xw.dtype == torch.float32 and xw.is_contiguous()
+    assert yofs.numel() == hs and ycnt.numel() == hs and tuple(yw.shape) == (hs, POSE_AREA_TAPS) and yw.dtype == torch.float32 and yw.is_contiguous()
+    check(lib().ca_pose_prep(_p(frames), _p(out), _p(xofs), _p(xcnt), _p(xw), _p(yofs), _p(ycnt), _p(yw), n, h, w, hs, ws, hp, wp, dt_code(out.dtype), _stream()),
+          "ca_pose_prep")
+    return out
+
+
+def _pixels_view(t: torch.Tensor):
+    """(images, h, w, channels, pixel stride) of an NHWC tensor whose pixels are evenly spaced (a column range of a wider tensor)."""
+    assert t.dim() == 4 and t.stride(3) == 1
+    n, h, w, c = t.shape
+    ld = t.stride(2)
+    assert t.stride(1) == w * ld and (n == 1 or t.stride(0) == h * w * ld), "pixels must be evenly spaced"
+    return n, h, w, c, ld
+
+
+def conv7x7(xs, ws_, *, biases=None, relu: bool = False, outs=None, direct: Optional[bool] = None, cols: Optional[torch.Tensor] = None):
+    """Conv2d(Cin, Cout, 7, padding=3) of one or two independent problems of one shape: xs [images, H, W, Cin] NHWC tensors (each may be
+    a column range of a wider tensor), ws_ [Cout, 7, 7, Cin], fp32 biases, optional ReLU -> outs (allocated when None; each may be a
+    column range of a wider tensor).  direct (default: context.dispatch.pose_conv7_direct): ca_conv7x7, one launch for all problems, the
+    implicit GEMM from an LDS halo tile; otherwise ca_im2col7x7 into `cols` + gemm (split-K) per problem."""
+    xs, ws_ = list(xs), list(ws_)
+    g = len(xs)
+    assert g in (1, 2) and len(ws_) == g
+    biases = [None] * g if biases is None else list(biases)
+    _req_cuda(*xs, *ws_, *biases, cols)
+    n, h, w, cin, ldx = _pixels_view(xs[0])
+    cout = ws_[0].shape[0]
+    for x, wt, b in zip(xs, ws_, biases):
+        assert _pixels_view(x) == (n, h, w, cin, ldx) and x.dtype == xs[0].dtype
+        assert tuple(wt.shape) == (cout, 7, 7, cin) and wt.is_contiguous() and wt.dtype == x.dtype
+        assert b is None or (b.dtype == torch.float32 and b.numel() == cout and b.is_contiguous())
+    if outs is None:
+        outs = [torch.empty((n, h, w, cout), dtype=xs[0].dtype, device=xs[0].device) for _ in range(g)]
+    outs = list(outs)
+    ldy = _pixels_view(outs[0])[4]
+    for o in outs:
+        assert _pixels_view(o) == (n, h, w, cout, ldy) and o.dtype == xs[0].dtype
+    if direct is None:
+        direct = bool(dispatch.pose_conv7_direct)
+    if direct:
+        a = _capi.Conv7x7Args(ldx=ldx, ldy=ldy, groups=g, images=n, h=h, w_px=w, cin=cin, cout=cout, relu=int(relu), dtype=dt_code(xs[0].dtype))
+        for i in range(g):
+            a.x[i], a.w[i], a.bias[i], a.y[i] = _p(xs[i]), _p(ws_[i]), _p(biases[i]), _p(outs[i])
+        check(lib().ca_conv7x7(C.byref(a), _stream()), "ca_conv7x7")
+        return outs
+    rows = n * h * w
+    if cols is None:
+        cols = torch.empty((rows, 49 * cin), dtype=xs[0].dtype, device=xs[0].device)
+    else:
+        assert cols.dtype == xs[0].dtype and cols.is_contiguous() and cols.numel() >= rows * 49 * cin
+        cols = cols.view(-1)[: rows * 49 * cin].view(rows, 49 * cin)
+    for x, wt, b, o in zip(xs, ws_, biases, outs):
+        check(lib().ca_im2col7x7(_p(x), _p(cols), n, h, w, cin, ldx, dt_code(x.dtype), _stream()), "ca_im2col7x7")
+        gemm(cols, wt.view(cout, 49 * cin), bias=b, act=ACT_RELU if relu else ACT_NONE, out=torch.as_strided(o, (rows, cout), (ldy, 1)))
+    return outs
+
+
+def copy_cols(src: torch.Tensor, dst: torch.Tensor, col0: int) -> torch.Tensor:
+    """src [rows, c] into columns col0 .. col0 + c - 1 of the contiguous dst [rows, ld] (ca_copy_cols)."""
+    _req_cuda(src, dst)
+    assert src.dim() == 2 and dst.dim() == 2 and src.is_contiguous() and dst.is_contiguous() and src.dtype == dst.dtype and src.shape[0] == dst.shape[0]
+    check(lib().ca_copy_cols(_p(src), _p(dst), src.shape[0], src.shape[1], dst.shape[1], col0, dt_code(src.dtype), _stream()), "ca_copy_cols")
+    return dst
+
+
+def pose_maps_workspace_bytes(images: int, hl: int, w: int) -> int:
+    n = int(lib().ca_pose_maps_workspace_bytes(images, hl, w))
+    if n <= 0:
+        raise _capi.CAHipError(f"ca_pose_maps_workspace_bytes: images={images} hl={hl} w={w} is out of range")
+    return n
+
+
+def pose_maps(low: torch.Tensor, mx: torch.Tensor, my: torch.Tensor, raw: torch.Tensor, smooth: torch.Tensor, paf: torch.Tensor,
+              ws: Optional[torch.Tensor] = None) -> None:
+    """low fp32 [images, hl, wl, 64] (PAF in columns 0 .. 37, heat in 40 .. 58), mx fp32 [2, W, wl], my fp32 [2, H, hl] (the composite
+    resampling matrix of an axis, then the same with the Gaussian on top) -> raw [images, 18, H, W], smooth [images, 18, H, W] and paf
+    [images, 38, H, W], fp32 (ca_pose_maps)."""
+    _req_cuda(low, mx, my, raw, smooth, paf, ws)
+    n, hl, wl, c = low.shape
+    h, w = my.shape[1], mx.shape[1]
+    assert c == 64 and low.dtype == torch.float32 and low.is_contiguous()
+    assert tuple(mx.shape) == (2, w, wl) and tuple(my.shape) == (2, h, hl) and mx.dtype == my.dtype == torch.float32 and mx.is_contiguous() and my.is_contiguous()
+    for t, ch in ((raw, POSE_PARTS), (smooth, POSE_PARTS), (paf, POSE_PAF)):
+        assert tuple(t.shape) == (n, ch, h, w) and t.dtype == torch.float32 and t.is_contiguous()
+    if ws is None:
+        ws = torch.empty(pose_maps_workspace_bytes(n, hl, w), dtype=torch.uint8, device=low.device)
+    check(lib().ca_pose_maps(_p(low), _p(mx), _p(my), _p(ws), _ws_bytes(ws), _p(raw), _p(smooth), _p(paf), n, hl, wl, h, w, _stream()), "ca_pose_maps")
+
+
+def pose_decode_buffers(n: int, device) -> dict:
+    """The tensors the three decode launches pass on, for n frames."""
+    i32 = dict(dtype=torch.int32, device=device)
+    return {"peaks": torch.empty((n, POSE_PARTS, POSE_MAX_PEAKS, 2), **i32), "scores": torch.empty((n, POSE_PARTS, POSE_MAX_PEAKS), dtype=torch.float32, device=device),
+            "counts": torch.empty((n, POSE_PARTS), **i32), "overflow": torch.empty((n,), **i32),
+            "conn_ij": torch.empty((n, POSE_LIMBS, POSE_MAX_PEAKS, 2), **i32), "conn_score": torch.empty((n, POSE_LIMBS, POSE_MAX_PEAKS), dtype=torch.float64, device=device),
+            "conn_n": torch.empty((n, POSE_LIMBS), **i32), "keypoints": torch.empty((n, POSE_MAX_PEOPLE, POSE_PARTS, 2), **i32),
+            "coords": torch.empty((n, POSE_MAX_PEOPLE, POSE_PARTS, 2), **i32), "people": torch.empty((n,), **i32)}
+
+
+def pose_decode(raw: torch.Tensor, smooth: torch.Tensor, paf: torch.Tensor, buf: Optional[dict] = None, stage=None) -> dict:
+    """raw / smooth [images, 18, H, W] and paf [images, 38, H, W], fp32 -> the buffers of pose_decode_buffers filled: peaks (ca_pose_peaks),
+    connections (ca_pose_connect), keypoints / coords / people / overflow (ca_pose_assemble).  Three launches, no host read.
+    stage(name) -> a (start, end) pair of events whose start is recorded, or None: called before each launch (the annotator's timings)."""
+    _req_cuda(raw, smooth, paf)
+    n, _, h, w = raw.shape
+    for t, ch in ((raw, POSE_PARTS), (smooth, POSE_PARTS), (paf, POSE_PAF)):
+        assert tuple(t.shape) == (n, ch, h, w) and t.dtype == torch.float32 and t.is_contiguous()
+    b = pose_decode_buffers(n, raw.device) if buf is None else buf
+    stage = stage or (lambda name: None)
+    ev = stage("peaks")
+    check(lib().ca_pose_peaks(_p(raw), _p(smooth), _p(b["peaks"]), _p(b["scores"]), _p(b["counts"]), _p(b["overflow"]), n, h, w, _stream()), "ca_pose_peaks")
+    if ev:
+        ev[1].record()
+    ev = stage("connect")
+    check(lib().ca_pose_connect(_p(paf), _p(b["peaks"]), _p(b["counts"]), _p(b["conn_ij"]), _p(b["conn_score"]), _p(b["conn_n"]), n, h, w, _stream()), "ca_pose_connect")
+    if ev:
+        ev[1].record()
+    ev = stage("assemble")
+    pose_assemble(b, h, w)
+    if ev:
+        ev[1].record()
+    return b
+
+
+def pose_assemble(b: dict, h: int, w: int) -> dict:
+    """The peaks and connections of the buffers `b` (pose_decode_buffers) -> their keypoints, coords and people; overflow gets
+    POSE_OVERFLOW_PEOPLE where a 65th subset row was needed (ca_pose_assemble; overflow must hold ca_pose_peaks' bits or zeros)."""
+    n = b["people"].shape[0]
+    check(lib().ca_pose_assemble(_p(b["peaks"]), _p(b["scores"]), _p(b["conn_ij"]), _p(b["conn_score"]), _p(b["conn_n"]), _p(b["keypoints"]), _p(b["coords"]),
+                                 _p(b["people"]), _p(b["overflow"]), n, h, w, _stream()), "ca_pose_assemble")
+    return b
+
+
+def pose_draw(coords: torch.Tensor, people: torch.Tensor, sin_table: torch.Tensor, h: int, w: int, *, index: Optional[torch.Tensor] = None,
+              skeleton: Optional[torch.Tensor] = None, control: Optional[torch.Tensor] = None, rep: int = 1) -> Optional[torch.Tensor]:
+    """draw_bodypose of the people of every frame (coords int32 [images, 64, 18, 2] and people int32 [images] of pose_decode): the uint8
+    map `skeleton` [images, h, w, 3] and / or the control tensor [rep * images, 3, h, w] (float32 / float16) = map / 255 (ca_pose_draw).
+    index: the uint32 [images, h, w] plane the primitives' draw indices are resolved from."""
+    _req_cuda(coords, people, sin_table, index, skeleton, control)
+    n = coords.shape[0]
+    assert coords.dtype == torch.int32 and tuple(coords.shape) == (n, POSE_MAX_PEOPLE, POSE_PARTS, 2) and coords.is_contiguous()
+    assert people.dtype == torch.int32 and tuple(people.shape) == (n,) and people.is_contiguous()
+    assert sin_table.dtype == torch.float32 and sin_table.numel() == 451 and sin_table.is_contiguous()
+    if index is None:
+        index = torch.empty((n, h, w), dtype=torch.int32, device=coords.device)
+    assert index.dtype == torch.int32 and tuple(index.shape) == (n, h, w) and index.is_contiguous()
+    if skeleton is None and control is None:
+        skeleton = torch.empty((n, h, w, 3), dtype=torch.uint8, device=coords.device)
+    if skeleton is not None:
+        assert skeleton.dtype == torch.uint8 and tuple(skeleton.shape) == (n, h, w, 3) and skeleton.is_contiguous()
+    dt = _capi.CA_F32
+    if control is not None:
+        if control.dtype not in _CANNY_DT:
+            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
+        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
+        dt = _CANNY_DT[control.dtype]
+    check(lib().ca_pose_draw(_p(coords), _p(people), _p(sin_table), _p(index), _p(skeleton), _p(control), n, h, w, int(rep), dt, _stream()), "ca_pose_draw")
+    return skeleton

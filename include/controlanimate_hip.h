@@ -1145,6 +1145,77 @@ int ca_resize_bicubic_f32(const float* src, float* dst, void* minmax_keys, float
 int ca_depth_finish(const float* depth, const void* minmax_keys, int32_t images, int32_t h, int32_t w, int32_t mode, uint8_t* map, void* control, int32_t rep,
                     int32_t control_dtype, void* stream);
 
+/* ---- added to ABI v16 (no struct or existing function changes, the number stays): the OpenPose body annotator's stages beside
+ * ca_conv3x3 / ca_maxpool2x2 / ca_gemm (controlanimate_amd/openpose.py; csrc/ca_openpose.hip) ---- */
+#define CA_POSE_MAX_PEAKS 64        /* peaks kept per part and frame: the first ones in row-major order */
+#define CA_POSE_MAX_PEOPLE 64       /* rows of the subset table */
+#define CA_POSE_AREA_TAPS 8         /* taps per axis of ca_pose_prep's tables */
+#define CA_POSE_OVERFLOW_PEAKS 1    /* bits of overflow[frame] */
+#define CA_POSE_OVERFLOW_PEOPLE 2
+
+/* uint8 RGB frames [images, h, w, 3] -> out [images, hp, wp, 8] of dtype: the INTER_AREA resize to hs x ws as a separable weighted sum
+ * (per destination index of an axis: first source index ofs, number of taps cnt <= CA_POSE_AREA_TAPS, fp32 weights w [.., CA_POSE_AREA_TAPS];
+ * horizontal sums first, left to right, then their vertical sum, top to bottom, fp32, no fused multiply-add; rounded to a byte half to
+ * even), channels in BGR order, byte / 256 - 0.5; the pixels right of ws and below hs (the constant-128 padding) and channels 3 .. 7
+ * are zero. */
+int ca_pose_prep(const uint8_t* frames, void* out, const int32_t* xofs, const int32_t* xcnt, const float* xw, const int32_t* yofs, const int32_t* ycnt,
+                 const float* yw, int32_t images, int32_t h, int32_t w, int32_t hs, int32_t ws, int32_t hp, int32_t wp, int32_t dtype, void* stream);
+
+/* Conv2d(cin, cout, 7, stride 1, padding 3) of NHWC x [images, h, w_px, cin] (a pixel every ldx elements) into y (a pixel every ldy
+ * elements) for `groups` = 1 or 2 independent problems of one shape in ONE launch; w [cout, 7, 7, cin] of dtype, fp32 bias (may be NULL),
+ * optional ReLU; fp32 accumulation over (32-channel chunk, tap, channel), rounded once.  An implicit GEMM on MFMA 16x16x32 from an LDS
+ * halo tile; no im2col tensor, no split of the reduction: an image's result does not depend on the batch.  cin % 32 == 0, cout % 64 == 0. */
+typedef struct {
+  const void* x[2];
+  const void* w[2];
+  const float* bias[2];
+  void* y[2];
+  int64_t ldx, ldy;
+  int32_t groups, images, h, w_px, cin, cout, relu, dtype;
+} ca_conv7x7_args;
+int ca_conv7x7(const ca_conv7x7_args* args, void* stream);
+
+/* The gather in front of ca_gemm for the same convolution: cols [images * h * w, 49 * cin], column (ky * 7 + kx) * cin + ci of row
+ * (img, oy, ox) = x[img, oy - 3 + ky, ox - 3 + kx, ci], zero outside the image. */
+int ca_im2col7x7(const void* x, void* cols, int32_t images, int32_t h, int32_t w, int32_t cin, int64_t ldx, int32_t dtype, void* stream);
+
+/* src [rows, c] -> columns col0 .. col0 + c - 1 of dst [rows, ld] (16-bit elements; c, col0 and ld multiples of 8). */
+int ca_copy_cols(const void* src, void* dst, int64_t rows, int32_t c, int64_t ld, int32_t col0, int32_t dtype, void* stream);
+
+/* low fp32 [images, hl, wl, 64] (PAF in columns 0 .. 37, heat in 40 .. 58) -> planar fp32 raw [images, 18, h, w], smooth [images, 18, h, w]
+ * and paf [images, 38, h, w].  mx [2, w, wl] and my [2, h, hl]: per axis the matrix A of (x8 LANCZOS4, crop, LANCZOS4 to the frame) and the
+ * matrix G A with the sigma-3 Gaussian (reflect) on top, composed on the host in float64; raw and paf take A, smooth G A.  A columns pass
+ * into the workspace and a rows pass (a thread owns one column of four output rows), fp32, the source index ascending.  images <= 885. */
+int64_t ca_pose_maps_workspace_bytes(int32_t images, int32_t hl, int32_t w);
+int ca_pose_maps(const float* low, const float* mx, const float* my, void* workspace, int64_t workspace_bytes, float* raw, float* smooth, float* paf,
+                 int32_t images, int32_t hl, int32_t wl, int32_t h, int32_t w, void* stream);
+
+/* Per (frame, part): smooth >= its four neighbours (zero outside the frame) and (double) smooth > 0.1; the first CA_POSE_MAX_PEAKS in
+ * row-major order -> peaks int32 [images, 18, 64, 2] (x, y), scores fp32 [images, 18, 64] read from raw, counts int32 [images, 18];
+ * overflow int32 [images] is zeroed and gets CA_POSE_OVERFLOW_PEAKS where a part had more. */
+int ca_pose_peaks(const float* raw, const float* smooth, int32_t* peaks, float* scores, int32_t* counts, int32_t* overflow, int32_t images, int32_t h, int32_t w,
+                  void* stream);
+
+/* Per (frame, limb): the float64 score of every candidate pair (10 samples at int(round(linspace)), mean(paf . unit) + min(0.5 h / norm
+ * - 1, 0), kept when more than 8 samples exceed 0.05 and the score is positive), the stable descending order and the greedy matching ->
+ * conn_ij int32 [images, 19, 64, 2] (index into the two parts' peaks), conn_score float64 [images, 19, 64], conn_n int32 [images, 19]. */
+int ca_pose_connect(const float* paf, const int32_t* peaks, const int32_t* counts, int32_t* conn_ij, double* conn_score, int32_t* conn_n, int32_t images, int32_t h,
+                    int32_t w, void* stream);
+
+/* Per frame: the subset table (found == 1 / found == 2 merge or extend / new row for the first 17 limbs), rows with fewer than 4 parts or
+ * score / parts < 0.4 deleted -> keypoints int32 [images, 64, 18, 2] = int(x / float(w) * w), int(y / float(h) * h) (-1 where a part is
+ * missing or the row is unused), coords (the same table with the peaks' own pixels, what ca_pose_draw reads), people int32 [images];
+ * overflow gets CA_POSE_OVERFLOW_PEOPLE where a 65th row was needed. */
+int ca_pose_assemble(const int32_t* peaks, const float* scores, const int32_t* conn_ij, const double* conn_score, const int32_t* conn_n, int32_t* keypoints,
+                     int32_t* coords, int32_t* people, int32_t* overflow, int32_t images, int32_t h, int32_t w, void* stream);
+
+/* draw_bodypose of every person in order: per person 17 limbs (ellipse2Poly + fillConvexPoly, colour int(c * 0.6)) and then 18 filled
+ * radius-4 circles; primitive person * 35 + k writes its index with atomicMax into index uint32 [images, h, w] (zeroed here), a second
+ * pass writes the colours: map uint8 [images, h, w, 3] (may be NULL) and / or control [rep * images, 3, h, w] of control_dtype (CA_F32 /
+ * CA_F16) = map / 255.  sin_table: fp32 [451], OpenCV's table of sin(degrees). */
+int ca_pose_draw(const int32_t* coords, const int32_t* people, const float* sin_table, uint32_t* index, uint8_t* map, void* control, int32_t images, int32_t h,
+                 int32_t w, int32_t rep, int32_t control_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
