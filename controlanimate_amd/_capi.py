@@ -20,6 +20,9 @@ CA_ACT_LEAKY02 = 6  # LeakyReLU(0.2): the U-Net and the SFT branches of the GFPG
 CA_MLSD_TOPK = 200
 CA_POSE_MAX_PEAKS, CA_POSE_MAX_PEOPLE, CA_POSE_AREA_TAPS = 64, 64, 8  # the OpenPose annotator (openpose.py)
 CA_POSE_OVERFLOW_PEAKS, CA_POSE_OVERFLOW_PEOPLE = 1, 2
+CA_POSE_OVERFLOW_FACES, CA_POSE_OVERFLOW_FACE_RESIZE = 4, 8  # the face stage (openpose_face.py)
+CA_FACE_SIZE, CA_FACE_HEAT, CA_FACE_PARTS, CA_FACE_MIN_SIDE, CA_FACE_SLOT_INTS = 384, 48, 71, 11, 8
+CA_FACE_MODE_NONE, CA_FACE_MODE_LANCZOS4, CA_FACE_MODE_AREA = 0, 1, 2
 ABI_VERSION = 16
 
 
@@ -332,6 +335,11 @@ SYMBOLS = {
     "ca_pose_connect": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p]),
     "ca_pose_assemble": (C.c_int, [C.c_void_p] * 9 + [C.c_int32] * 3 + [C.c_void_p]),
     "ca_pose_draw": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 5 + [C.c_void_p]),
+    # added to ABI v16 likewise: the face stage of the OpenPose annotator around its network (controlanimate_amd/openpose_face.py)
+    "ca_face_boxes": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_void_p]),
+    "ca_face_crop": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 8 + [C.c_void_p]),
+    "ca_face_peaks": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p]),
+    "ca_pose_draw_faces": (C.c_int, [C.c_void_p] * 9 + [C.c_int32] * 5 + [C.c_void_p]),
 }
 
 _lib = None

@@ -21,6 +21,8 @@
 //   assemble  k_pose_assemble   per frame, one wave: the subset table (a lane per row), the deletion rule, the keypoint tables
 //   draw      k_pose_raster     per (frame, person, primitive): ellipse2Poly + fillConvexPoly / circle, atomicMax of the draw index
 //             k_pose_resolve    the index plane -> colours: the uint8 map and / or the control tensor
+//             k_face_raster     ca_pose_draw_faces only: per (frame, person) the 71 radius-3 discs of the face points (ca_openpose_face.hip finds
+//                               them) into the same index plane, after that person's body primitives and before the next person's
 //
 // Every loop of the decode is bounded by a compile-time constant.  No launch depends on device data on the host side: the chain can be
 // captured in a hipGraph.  atomicMax / atomicOr only where the result does not depend on the order.
@@ -31,6 +33,7 @@ namespace {
 constexpr int64_t kMaxPixels = ((int64_t)1 << 31) - 1;
 constexpr int64_t kMaxBytes = 0x7FFFFF00;
 constexpr int kParts = 18, kLimbs = 19, kDrawLimbs = 17, kPrims = kDrawLimbs + kParts;
+constexpr int kFaceParts = CA_FACE_PARTS, kPrimsFace = kPrims + kFaceParts;  // ca_pose_draw_faces: a person's 71 discs follow the body's primitives
 constexpr int kMaxPeaks = CA_POSE_MAX_PEAKS, kMaxPeople = CA_POSE_MAX_PEOPLE;
 constexpr int kPafCh = 38, kMapCh = 2 * kParts + kPafCh;  // raw heat, smoothed heat, PAF
 constexpr int kMidNum = 10;
@@ -45,6 +48,7 @@ __constant__ unsigned char c_color[kParts][3] = {{255, 0, 0},   {255, 85, 0},  {
                                                  {0, 255, 0},   {0, 255, 85},  {0, 255, 170}, {0, 255, 255}, {0, 170, 255}, {0, 85, 255},
                                                  {0, 0, 255},   {85, 0, 255},  {170, 0, 255}, {255, 0, 255}, {255, 0, 170}, {255, 0, 85}};
 __constant__ int c_circle_half[5] = {4, 3, 3, 2, 0};  // cv2.circle(radius 4, filled): half width of the row |dy|
+__constant__ int c_disc_half[4] = {3, 2, 2, 0};       // ... of radius 3 (draw_facepose)
 
 inline bool dtype_ok(int32_t dtype) { return dtype == CA_BF16 || dtype == CA_F16; }
 inline bool sizes_ok(int32_t images, int32_t h, int32_t w) { return images >= 1 && h >= 1 && w >= 1 && (int64_t)images * h * w <= kMaxPixels; }
@@ -538,7 +542,7 @@ __device__ __forceinline__ void put(unsigned* plane, int H, int W, long long x, 
 constexpr int kPolyMax = 361;
 
 __global__ __launch_bounds__(256) void k_pose_raster(const int32_t* __restrict__ coords, const int32_t* __restrict__ people, const float* __restrict__ sin_table,
-                                                     unsigned* __restrict__ index, int H, int W) {
+                                                     unsigned* __restrict__ index, int H, int W, int prims) {
   __shared__ int ptx[kPolyMax], pty[kPolyMax];
   __shared__ int vx[kPolyMax], vy[kPolyMax];
   __shared__ int npts_s, row0_s, rows_s;
@@ -549,7 +553,7 @@ __global__ __launch_bounds__(256) void k_pose_raster(const int32_t* __restrict__
   if (person >= np) return;
   const int32_t* co = coords + ((int64_t)img * kMaxPeople + person) * kParts * 2;
   unsigned* plane = index + (int64_t)img * H * W;
-  const unsigned value = (unsigned)(person * kPrims + prim) + 1u;
+  const unsigned value = (unsigned)(person * prims + prim) + 1u;  // prims: the primitives of a person (kPrims, or kPrimsFace with faces)
   if (prim >= kDrawLimbs) {  // cv2.circle(canvas, (x, y), 4, color, -1)
     const int q = prim - kDrawLimbs;
     if (co[q * 2] < 0) return;
@@ -669,6 +673,27 @@ __global__ __launch_bounds__(256) void k_pose_raster(const int32_t* __restrict__
   }
 }
 
+// draw_facepose: a filled radius-3 disc at (xmap[px], ymap[py]) of every face point whose two coordinates come out positive.  A block per
+// (person, frame); a thread per pixel of the 7 x 7 square around a point.
+__global__ __launch_bounds__(256) void k_face_raster(const int32_t* __restrict__ points, const int32_t* __restrict__ people, const int32_t* __restrict__ xmap,
+                                                     const int32_t* __restrict__ ymap, unsigned* __restrict__ index, int H, int W) {
+  const int person = blockIdx.x, img = blockIdx.y;
+  int np = people[img];
+  np = np < 0 ? 0 : (np > kMaxPeople ? kMaxPeople : np);
+  if (person >= np) return;
+  const int32_t* pt = points + ((int64_t)img * kMaxPeople + person) * kFaceParts * 2;
+  unsigned* plane = index + (int64_t)img * H * W;
+  for (int i = threadIdx.x; i < kFaceParts * 49; i += 256) {
+    const int q = i / 49, t = i - q * 49, dy = t / 7 - 3, dx = t % 7 - 3;
+    const int px = pt[q * 2], py = pt[q * 2 + 1];
+    if (px < 0 || py < 0 || px >= W || py >= H) continue;
+    const int cx = xmap[px], cy = ymap[py];
+    if (!(cx > 0 && cy > 0)) continue;  // x > eps and y > eps of integers
+    const int half = c_disc_half[dy < 0 ? -dy : dy];
+    if (dx >= -half && dx <= half) put(plane, H, W, cx + dx, cy + dy, (unsigned)(person * kPrimsFace + kPrims + q) + 1u);
+  }
+}
+
 template <typename T>
 __device__ __forceinline__ T ctrl_of(int level);
 template <>
@@ -678,7 +703,7 @@ __device__ __forceinline__ u16 ctrl_of<u16>(int level) { return Elem<CA_F16>::fr
 
 template <typename T>
 __global__ __launch_bounds__(256) void k_pose_resolve(const unsigned* __restrict__ index, uint8_t* __restrict__ map, T* __restrict__ ctrl, int images, int64_t hw,
-                                                      int rep) {
+                                                      int rep, int prims) {
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (g >= images * hw) return;
   const int img = (int)(g / hw);
@@ -686,9 +711,10 @@ __global__ __launch_bounds__(256) void k_pose_resolve(const unsigned* __restrict
   const unsigned v = index[g];
   int rgb[3] = {0, 0, 0};
   if (v) {
-    const int prim = (int)((v - 1u) % kPrims);
+    const int prim = (int)((v - 1u) % (unsigned)prims);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) rgb[c] = prim < kDrawLimbs ? (int)((double)c_color[prim][c] * 0.6) : (int)c_color[prim - kDrawLimbs][c];
+    for (int c = 0; c < 3; ++c)
+      rgb[c] = prim < kDrawLimbs ? (int)((double)c_color[prim][c] * 0.6) : (prim < kPrims ? (int)c_color[prim - kDrawLimbs][c] : 255);  // a face disc is white
   }
   if (map) {
 #pragma unroll
@@ -867,10 +893,38 @@ extern "C" int ca_pose_draw(const int32_t* coords, const int32_t* people, const 
   const int64_t hw = (int64_t)h * w, total = (int64_t)images * hw;
   hipError_t e = hipMemsetAsync(index, 0, (size_t)total * 4, st);
   if (e != hipSuccess) CA_FAIL(CA_ERR_LAUNCH, "ca_pose_draw: %s", hipGetErrorString(e));
-  hipLaunchKernelGGL(k_pose_raster, dim3(kPrims, kMaxPeople, (unsigned)images), dim3(256), 0, st, coords, people, sin_table, (unsigned*)index, (int)h, (int)w);
+  hipLaunchKernelGGL(k_pose_raster, dim3(kPrims, kMaxPeople, (unsigned)images), dim3(256), 0, st, coords, people, sin_table, (unsigned*)index, (int)h, (int)w, kPrims);
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (control_dtype == CA_F32) hipLaunchKernelGGL(k_pose_resolve<float>, grid, block, 0, st, (const unsigned*)index, map, (float*)control, (int)images, hw, (int)rep);
-  else hipLaunchKernelGGL(k_pose_resolve<u16>, grid, block, 0, st, (const unsigned*)index, map, (u16*)control, (int)images, hw, (int)rep);
+  if (control_dtype == CA_F32) hipLaunchKernelGGL(k_pose_resolve<float>, grid, block, 0, st, (const unsigned*)index, map, (float*)control, (int)images, hw, (int)rep, kPrims);
+  else hipLaunchKernelGGL(k_pose_resolve<u16>, grid, block, 0, st, (const unsigned*)index, map, (u16*)control, (int)images, hw, (int)rep, kPrims);
   CA_CHECK_LAUNCH("ca_pose_draw");
+  return CA_OK;
+}
+
+extern "C" int ca_pose_draw_faces(const int32_t* coords, const int32_t* people, const float* sin_table, const int32_t* points, const int32_t* xmap, const int32_t* ymap,
+                                  uint32_t* index, uint8_t* map, void* control, int32_t images, int32_t h, int32_t w, int32_t rep, int32_t control_dtype,
+                                  void* stream) {
+  CA_REQUIRE(coords && people && sin_table && index, "ca_pose_draw_faces: coords, people, sin_table and index are required");
+  CA_REQUIRE(!points || (xmap && ymap), "ca_pose_draw_faces: points need xmap and ymap");
+  CA_REQUIRE(map || control, "ca_pose_draw_faces: map or control is required");
+  CA_REQUIRE(sizes_ok(images, h, w) && images <= 65535 && h <= kMaxSide && w <= kMaxSide,
+             "ca_pose_draw_faces: images=%d h=%d w=%d (each >= 1, images <= 65535, h and w <= %d, images * h * w < 2^31)", images, h, w, kMaxSide);
+  CA_REQUIRE(rep == 1 || rep == 2, "ca_pose_draw_faces: rep=%d (1 or 2)", rep);
+  CA_REQUIRE(control_dtype == CA_F16 || control_dtype == CA_F32, "ca_pose_draw_faces: control_dtype=%d (CA_F16 or CA_F32)", control_dtype);
+  CA_REQUIRE((((uintptr_t)coords | (uintptr_t)people | (uintptr_t)sin_table | (uintptr_t)index | (uintptr_t)points | (uintptr_t)xmap | (uintptr_t)ymap) & 3) == 0 &&
+                 ((uintptr_t)control & (control_dtype == CA_F32 ? 3 : 1)) == 0,
+             "ca_pose_draw_faces: coords, people, sin_table, points, xmap, ymap and index must be 4-byte aligned, control aligned to its element");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t hw = (int64_t)h * w, total = (int64_t)images * hw;
+  hipError_t e = hipMemsetAsync(index, 0, (size_t)total * 4, st);
+  if (e != hipSuccess) CA_FAIL(CA_ERR_LAUNCH, "ca_pose_draw_faces: %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(k_pose_raster, dim3(kPrims, kMaxPeople, (unsigned)images), dim3(256), 0, st, coords, people, sin_table, (unsigned*)index, (int)h, (int)w, kPrimsFace);
+  if (points) hipLaunchKernelGGL(k_face_raster, dim3(kMaxPeople, (unsigned)images), dim3(256), 0, st, points, people, xmap, ymap, (unsigned*)index, (int)h, (int)w);
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  if (control_dtype == CA_F32)
+    hipLaunchKernelGGL(k_pose_resolve<float>, grid, block, 0, st, (const unsigned*)index, map, (float*)control, (int)images, hw, (int)rep, kPrimsFace);
+  else
+    hipLaunchKernelGGL(k_pose_resolve<u16>, grid, block, 0, st, (const unsigned*)index, map, (u16*)control, (int)images, hw, (int)rep, kPrimsFace);
+  CA_CHECK_LAUNCH("ca_pose_draw_faces");
   return CA_OK;
 }

@@ -1880,3 +1880,100 @@ def pose_draw(coords: torch.Tensor, people: torch.Tensor, sin_table: torch.Tenso
         dt = _CANNY_DT[control.dtype]
     check(lib().ca_pose_draw(_p(coords), _p(people), _p(sin_table), _p(index), _p(skeleton), _p(control), n, h, w, int(rep), dt, _stream()), "ca_pose_draw")
     return skeleton
+
+
+# ---- added to ABI v16: the face stage of the OpenPose annotator around its network (controlanimate_amd/openpose_face.py: FaceStage) ----
+
+POSE_OVERFLOW_FACES, POSE_OVERFLOW_FACE_RESIZE = _capi.CA_POSE_OVERFLOW_FACES, _capi.CA_POSE_OVERFLOW_FACE_RESIZE
+FACE_SIZE, FACE_HEAT, FACE_PARTS, FACE_MIN_SIDE, FACE_SLOT_INTS = _capi.CA_FACE_SIZE, _capi.CA_FACE_HEAT, _capi.CA_FACE_PARTS, _capi.CA_FACE_MIN_SIDE, _capi.CA_FACE_SLOT_INTS
+FACE_MODE_NONE, FACE_MODE_LANCZOS4, FACE_MODE_AREA = _capi.CA_FACE_MODE_NONE, _capi.CA_FACE_MODE_LANCZOS4, _capi.CA_FACE_MODE_AREA
+
+
+def face_buffers(n: int, max_faces: int, device) -> dict:
+    """The tensors the face stage's launches pass on, for n frames."""
+    i32 = dict(dtype=torch.int32, device=device)
+    return {"boxes": torch.empty((n, POSE_MAX_PEOPLE, 4), **i32), "slots": torch.empty((n, max_faces, FACE_SLOT_INTS), **i32), "overflow": torch.empty((n,), **i32),
+            "points": torch.empty((n, POSE_MAX_PEOPLE, FACE_PARTS, 2), **i32)}
+
+
+def face_boxes(keypoints: torch.Tensor, people: torch.Tensor, h: int, w: int, buf: dict, overflow_in: Optional[torch.Tensor] = None) -> dict:
+    """util.faceDetect per person of keypoints int32 [images, 64, 18, 2] / people int32 [images] -> buf["boxes"] (x, y, w, slot),
+    buf["slots"] [images, max_faces, 8] (person, x, y, w, hc, wc, mode, 0) and buf["overflow"] = overflow_in | the face bits (ca_face_boxes)."""
+    _req_cuda(keypoints, people, overflow_in, buf["boxes"], buf["slots"], buf["overflow"])
+    n = keypoints.shape[0]
+    assert keypoints.dtype == torch.int32 and tuple(keypoints.shape) == (n, POSE_MAX_PEOPLE, POSE_PARTS, 2) and keypoints.is_contiguous()
+    assert people.dtype == torch.int32 and tuple(people.shape) == (n,) and people.is_contiguous()
+    assert overflow_in is None or (overflow_in.dtype == torch.int32 and tuple(overflow_in.shape) == (n,) and overflow_in.is_contiguous())
+    max_faces = buf["slots"].shape[1]
+    assert tuple(buf["boxes"].shape) == (n, POSE_MAX_PEOPLE, 4) and tuple(buf["slots"].shape) == (n, max_faces, FACE_SLOT_INTS) and tuple(buf["overflow"].shape) == (n,)
+    _req_i32(buf["boxes"], buf["slots"], buf["overflow"])
+    check(lib().ca_face_boxes(_p(keypoints), _p(people), _p(overflow_in), _p(buf["boxes"]), _p(buf["slots"]), _p(buf["overflow"]), n, h, w, max_faces, _stream()),
+          "ca_face_boxes")
+    return buf
+
+
+def face_crop(frames: torch.Tensor, slots: torch.Tensor, tables: dict, out: torch.Tensor, first: int = 0) -> torch.Tensor:
+    """uint8 RGB [images, H, W, 3] and slots [images, max_faces, 8] -> `out` [crops, 384, 384, 8] fp16 / bf16: the crops of slots first ..
+    first + crops - 1 resized as cv2.resize does (INTER_LANCZOS4 / INTER_AREA by the slot's mode), BGR, x / 256 - 0.5 (ca_face_crop).
+    tables: openpose_face.resize_tables(side_max) on the device (lz_ofs, lz_coef, ar_ofs, ar_cnt, ar_w, side_max)."""
+    _req_cuda(frames, slots, out, tables["lz_ofs"], tables["lz_coef"], tables["ar_ofs"], tables["ar_cnt"], tables["ar_w"])
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
+    n, h, w, _ = frames.shape
+    max_faces = slots.shape[1]
+    assert slots.dtype == torch.int32 and tuple(slots.shape) == (n, max_faces, FACE_SLOT_INTS) and slots.is_contiguous()
+    crops = out.shape[0]
+    assert tuple(out.shape) == (crops, FACE_SIZE, FACE_SIZE, 8) and out.is_contiguous()
+    side_max = int(tables["side_max"])
+    nl, na = side_max - FACE_MIN_SIDE + 1, side_max - FACE_SIZE + 1
+    assert tuple(tables["lz_ofs"].shape) == (nl, FACE_SIZE) and tuple(tables["lz_coef"].shape) == (nl, FACE_SIZE, 8) and tables["lz_coef"].dtype == torch.int16
+    assert tuple(tables["ar_ofs"].shape) == (na, FACE_SIZE) and tuple(tables["ar_cnt"].shape) == (na, FACE_SIZE)
+    assert tuple(tables["ar_w"].shape) == (na, FACE_SIZE, 8) and tables["ar_w"].dtype == torch.float32
+    _req_i32(tables["lz_ofs"], tables["ar_ofs"], tables["ar_cnt"])
+    for t in ("lz_ofs", "lz_coef", "ar_ofs", "ar_cnt", "ar_w"):
+        assert tables[t].is_contiguous()
+    check(lib().ca_face_crop(_p(frames), _p(slots), _p(out), _p(tables["lz_ofs"]), _p(tables["lz_coef"]), _p(tables["ar_ofs"]), _p(tables["ar_cnt"]), _p(tables["ar_w"]),
+                             n, h, w, max_faces, int(first), crops, side_max, dt_code(out.dtype), _stream()), "ca_face_crop")
+    return out
+
+
+def face_peaks(heat: torch.Tensor, slots: torch.Tensor, points: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """heat fp32 [images * max_faces, 48, 48, 72] and slots [images, max_faces, 8] -> points int32 [images, 64, 71, 2]: per crop and part the
+    first position of the largest align-corners bilinear value above 0.05 over the crop's pixels, in frame pixels (ca_face_peaks)."""
+    _req_cuda(heat, slots, points)
+    n, max_faces = slots.shape[0], slots.shape[1]
+    assert slots.dtype == torch.int32 and tuple(slots.shape) == (n, max_faces, FACE_SLOT_INTS) and slots.is_contiguous()
+    assert heat.dtype == torch.float32 and tuple(heat.shape) == (n * max_faces, FACE_HEAT, FACE_HEAT, FACE_PARTS + 1) and heat.is_contiguous()
+    assert points.dtype == torch.int32 and tuple(points.shape) == (n, POSE_MAX_PEOPLE, FACE_PARTS, 2) and points.is_contiguous()
+    check(lib().ca_face_peaks(_p(heat), _p(slots), _p(points), n, max_faces, h, w, _stream()), "ca_face_peaks")
+    return points
+
+
+def pose_draw_faces(coords: torch.Tensor, people: torch.Tensor, sin_table: torch.Tensor, points: Optional[torch.Tensor], xmap: Optional[torch.Tensor],
+                    ymap: Optional[torch.Tensor], h: int, w: int, *, index: Optional[torch.Tensor] = None, skeleton: Optional[torch.Tensor] = None,
+                    control: Optional[torch.Tensor] = None, rep: int = 1) -> Optional[torch.Tensor]:
+    """pose_draw with the 71 radius-3 white discs of every person's face points int32 [images, 64, 71, 2] after that person's body and
+    before the next person's (ca_pose_draw_faces).  xmap int32 [w], ymap int32 [h]: openpose_face.pixel_map.  points None: the bodies only."""
+    _req_cuda(coords, people, sin_table, points, xmap, ymap, index, skeleton, control)
+    n = coords.shape[0]
+    assert coords.dtype == torch.int32 and tuple(coords.shape) == (n, POSE_MAX_PEOPLE, POSE_PARTS, 2) and coords.is_contiguous()
+    assert people.dtype == torch.int32 and tuple(people.shape) == (n,) and people.is_contiguous()
+    assert sin_table.dtype == torch.float32 and sin_table.numel() == 451 and sin_table.is_contiguous()
+    if points is not None:
+        assert points.dtype == torch.int32 and tuple(points.shape) == (n, POSE_MAX_PEOPLE, FACE_PARTS, 2) and points.is_contiguous()
+        assert xmap.dtype == torch.int32 and tuple(xmap.shape) == (w,) and ymap.dtype == torch.int32 and tuple(ymap.shape) == (h,)
+    if index is None:
+        index = torch.empty((n, h, w), dtype=torch.int32, device=coords.device)
+    assert index.dtype == torch.int32 and tuple(index.shape) == (n, h, w) and index.is_contiguous()
+    if skeleton is None and control is None:
+        skeleton = torch.empty((n, h, w, 3), dtype=torch.uint8, device=coords.device)
+    if skeleton is not None:
+        assert skeleton.dtype == torch.uint8 and tuple(skeleton.shape) == (n, h, w, 3) and skeleton.is_contiguous()
+    dt = _capi.CA_F32
+    if control is not None:
+        if control.dtype not in _CANNY_DT:
+            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
+        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
+        dt = _CANNY_DT[control.dtype]
+    check(lib().ca_pose_draw_faces(_p(coords), _p(people), _p(sin_table), _p(points), _p(xmap), _p(ymap), _p(index), _p(skeleton), _p(control), n, h, w, int(rep), dt,
+                                   _stream()), "ca_pose_draw_faces")
+    return skeleton

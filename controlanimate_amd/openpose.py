@@ -2,10 +2,11 @@
 list lllyasviel/control_v11p_sd15_openpose as their first ControlNet; their control frames come from controlnet_aux's OpenposeDetector,
 modules/controlresiduals_pipeline.py:57, 107-113) on the GPU, for a whole window of frames at once.
 
-This annotator draws the reference's BODY skeleton and not its hands and faces: the reference calls the detector with
-hand_and_face=True, which additionally runs a hand network and a face network on crops around the detected body.  That is a separate
-feature; `include_hand` / `include_face` must be false here (anything else raises NotImplementedError), and `poses()` is the hook a later
-hand / face stage would start from.
+The reference calls the detector with hand_and_face=True, which additionally runs a hand network and a face network on crops around
+the detected body.  Without further weights this annotator draws the BODY skeleton only.  Given a face network
+(`OpenposeAnnotator(body, face=<state dict or facenet.pth>)`) it also draws the 71 face points of the first `max_faces` people of a
+frame: the face stage is openpose_face.py (its head describes it; `faces()` returns its points and boxes).  Hands are still missing:
+`include_hand` must be false (anything else raises NotImplementedError), and so must `include_face` when no face network is given.
 
 The detector's body part, as the reference calls it (detect_resolution = image_resolution = 512):
 
@@ -72,6 +73,7 @@ except Exception:  # pragma: no cover
 WEIGHTS_NAME = "body_pose_model.pth"
 MAX_PEAKS, MAX_PEOPLE, AREA_TAPS = 64, 64, 8
 OVERFLOW_PEAKS, OVERFLOW_PEOPLE = 1, 2
+OVERFLOW_FACES, OVERFLOW_FACE_RESIZE = 4, 8   # the face stage (openpose_face.py)
 BOXSIZE, STRIDE = 368, 8
 STAGES = {"prep": 1, "conv": 18, "pool": 3, "copy": 1, "pointwise": 24, "conv7": 25, "maps": 1, "peaks": 1, "connect": 1, "assemble": 1, "draw": 1}
 
@@ -216,11 +218,51 @@ def sin_table() -> np.ndarray:
     return np.round(np.sin(np.deg2rad(np.arange(451, dtype=np.float64))), 7).astype(np.float32)
 
 
+class BufferPlan:
+    """The activation buffers of one pass through a network, out of a workspace's pool (ws["pool"]: [[flat buffer, taken]]; ws["plan"]: the
+    slot of the i-th take of a pass, fixed by the first pass; ws["planned"]).  The layers take and give buffers in a fixed order; the first
+    pass allocates them and every later pass gets the same ones in the same order, so nothing is allocated after it and a captured graph
+    stays valid.  The caller sets ws["planned"] when a pass has finished (a first pass that did not finish starts over)."""
+
+    def __init__(self, ws: dict, dtype, device):
+        self.pool, self.plan, self.replay, self.cursor = ws["pool"], ws["plan"], ws["planned"], 0
+        self.dtype, self.device = dtype, device
+        if not self.replay:
+            self.plan.clear()
+        for slot in self.pool:
+            slot[1] = False
+
+    def take(self, *shape):
+        import torch
+        numel = int(np.prod(shape))
+        pool = self.pool
+        if self.replay:
+            slot = pool[self.plan[self.cursor]]
+            self.cursor += 1
+            assert not slot[1] and slot[0].numel() >= numel
+        else:
+            free = [i for i, sl in enumerate(pool) if not sl[1] and sl[0].numel() >= numel]
+            if not free:
+                pool.append([torch.empty(numel, dtype=self.dtype, device=self.device), False])
+                free = [len(pool) - 1]
+            self.plan.append(min(free, key=lambda i: pool[i][0].numel()))
+            slot = pool[self.plan[-1]]
+        slot[1] = True
+        return slot[0][:numel].view(*shape)
+
+    def give(self, t) -> None:
+        for slot in self.pool:
+            if slot[0].data_ptr() == t.data_ptr():
+                slot[1] = False
+                return
+        raise AssertionError("not a pool buffer")
+
+
 class OpenposeAnnotator:
     """`OpenposeAnnotator(weights)(image)` has the contract of `annotators.canny(image)` (PIL in, PIL RGB out; an array in, an array out),
     so it plugs into `MultiControlNetResidualsPipeline(annotators={"openpose": OpenposeAnnotator.from_pretrained(path)})`, whose
     `prep_control_images` then calls `annotate_batch` once per list of frames.  Nothing makes it a default: the weights are the user's
-    file.  It draws the body skeleton only (see the module's head).  Non-uint8 input raises TypeError, frames of different sizes
+    file.  It draws the body skeleton, and the faces when a face network is given (see the module's head).  Non-uint8 input raises TypeError, frames of different sizes
     ValueError, sizes out of scope NotImplementedError -- all before the device is touched; without the library or a GPU a call raises
     CAHipUnavailable (there is no CPU fallback)."""
 
@@ -229,14 +271,18 @@ class OpenposeAnnotator:
     STAGES = STAGES
 
     def __init__(self, state_dict_or_path, device=None, dtype=None, detect_resolution: int = 512, image_resolution: int = 512,
-                 include_hand: bool = False, include_face: bool = False):
+                 include_hand: bool = False, include_face=None, face=None, max_faces: int = 2):
         import torch
         dtype = torch.float16 if dtype is None else dtype
         if dtype not in (torch.float16, torch.bfloat16):
             raise TypeError(f"dtype must be torch.float16 or torch.bfloat16, got {dtype}")
-        if include_hand or include_face:
-            raise NotImplementedError("OpenposeAnnotator draws the body skeleton only: the hand and face networks of the reference's "
-                                      "hand_and_face=True are not part of it (include_hand and include_face must be False)")
+        if include_hand:
+            raise NotImplementedError("OpenposeAnnotator draws the body skeleton and, given a face network, the faces: the hand network of the "
+                                      "reference's hand_and_face=True is not part of it (include_hand must be False)")
+        include_face = face is not None if include_face is None else bool(include_face)   # with `face` given, faces are drawn by default
+        if include_face and face is None:
+            raise NotImplementedError("include_face=True, but no face network was given: pass face=<state dict, facenet.pth or the directory "
+                                      "that holds it> (nothing is ever downloaded)")
         if detect_resolution != image_resolution or detect_resolution < 192 or detect_resolution % 64:
             raise NotImplementedError(f"OpenposeAnnotator takes detect_resolution == image_resolution, a multiple of 64 and >= 192; got "
                                       f"{detect_resolution} and {image_resolution}")
@@ -274,6 +320,11 @@ class OpenposeAnnotator:
         self._dev = None
         self._ws = {}
         self._tables = {}
+        self._face = None
+        if include_face:
+            from .openpose_face import FACE_STAGES, FaceStage
+            self._face = FaceStage(self, face, max_faces)   # (its key and shape checks come before the device is touched, like the body's)
+            self.STAGES = {**STAGES, **FACE_STAGES}
         self.timings = None  # a dict: receives (start, end) torch events per stage under the keys of STAGES -- tools/bench_openpose.py
 
     @staticmethod
@@ -296,7 +347,8 @@ class OpenposeAnnotator:
 
     @classmethod
     def from_pretrained(cls, path, **kwargs):
-        """path: a local body_pose_model.pth or a directory that holds it (no network access, ever)."""
+        """path: a local body_pose_model.pth or a directory that holds it (no network access, ever).  face=<a local facenet.pth or a
+        directory that holds it> adds the face stage."""
         return cls(cls._load(path), **kwargs)
 
     # ---- device state ----------------------------------------------------------------------------------------------------------
@@ -428,39 +480,13 @@ class OpenposeAnnotator:
     # ---- the chain -------------------------------------------------------------------------------------------------------------
     def _network(self, src, ws, i0: int) -> None:
         """The network for the frames `src` (a chunk): PAF and heat into ws["low"][i0 : i0 + len(src)]."""
-        import torch
         from . import kernels as K
         from .context import dispatch
         wts = self._weights(src.device)
         n = src.shape[0]
         g = ws["geometry"]
-        pool, plan = ws["pool"], ws["plan"]  # [[flat buffer, taken]]; the slot of the i-th take of a pass, fixed by the first pass
-        replay, cursor = ws["planned"], [0]
-        if not replay:
-            plan.clear()   # (a first pass that did not finish starts over)
-
-        def take(*shape):
-            numel = int(np.prod(shape))
-            if replay:   # the same buffers in the same order on every pass: nothing is allocated after the first one (a captured graph stays valid)
-                slot = pool[plan[cursor[0]]]
-                cursor[0] += 1
-                assert not slot[1] and slot[0].numel() >= numel
-            else:
-                free = [i for i, sl in enumerate(pool) if not sl[1] and sl[0].numel() >= numel]
-                if not free:
-                    pool.append([torch.empty(numel, dtype=self.dtype, device=src.device), False])
-                    free = [len(pool) - 1]
-                plan.append(min(free, key=lambda i: pool[i][0].numel()))
-                slot = pool[plan[-1]]
-            slot[1] = True
-            return slot[0][:numel].view(*shape)
-
-        def give(t):
-            for slot in pool:
-                if slot[0].data_ptr() == t.data_ptr():
-                    slot[1] = False
-                    return
-            raise AssertionError("not a pool buffer")
+        plan = BufferPlan(ws, self.dtype, src.device)
+        take, give = plan.take, plan.give
 
         def timed(name, fn, *args, **kw):
             ev = self._stage(name)
@@ -477,8 +503,6 @@ class OpenposeAnnotator:
         def pw(x2d, wb, act, out2d, out_f32=False):
             timed("pointwise", K.gemm, x2d, wb[0], bias=wb[1], act=act, out=out2d, out_f32=out_f32)
 
-        for slot in pool:
-            slot[1] = False
         x = timed("prep", K.pose_prep, src, ws["area"], g["hs"], g["ws"], take(n, g["hp"], g["wp"], 8))
         for layer, wb in zip(FRONT, wts["front"]):
             if layer == "pool":
@@ -535,7 +559,8 @@ class OpenposeAnnotator:
         give(cat)
         ws["planned"] = True
 
-    def _run(self, src, skeleton, control, rep, decode=True):
+    def _run(self, src, skeleton, control, rep, decode=True, face=None):
+        """face: run the face stage (None: when there is one and something is drawn)."""
         from . import kernels as K
         n, h, w, _ = src.shape
         ws = self.workspace(n, h, w)
@@ -554,12 +579,28 @@ class OpenposeAnnotator:
             ev[1].record()
         if decode:
             K.pose_decode(ws["raw"], ws["smooth"], ws["paf"], ws["decode"], stage=self._stage)
-        if skeleton is not None or control is not None:
+        drawn = skeleton is not None or control is not None
+        fws = None
+        if self._face is not None and decode and (drawn if face is None else face):
+            fws = self._faces_from(src, ws["decode"]["keypoints"], ws["decode"]["people"], ws["decode"]["overflow"])
+        if drawn:
             ev = self._stage("draw")
-            K.pose_draw(ws["decode"]["coords"], ws["decode"]["people"], ws["sin"], h, w, index=ws["index"], skeleton=skeleton, control=control, rep=rep)
+            d = ws["decode"]
+            if fws is None:
+                K.pose_draw(d["coords"], d["people"], ws["sin"], h, w, index=ws["index"], skeleton=skeleton, control=control, rep=rep)
+            else:
+                K.pose_draw_faces(d["coords"], d["people"], ws["sin"], fws["buf"]["points"], fws["xmap"], fws["ymap"], h, w, index=ws["index"],
+                                  skeleton=skeleton, control=control, rep=rep)
             if ev:
                 ev[1].record()
         return ws
+
+    def _faces_from(self, src, keypoints, people, overflow=None):
+        """The face stage from given keypoints int32 [n, MAX_PEOPLE, 18, 2] and people int32 [n] on the device (the internal entry: tests
+        plant them, a hand stage would start the same way) -> the stage's workspace (openpose_face.FaceStage.run)."""
+        if self._face is None:
+            raise NotImplementedError("no face network was given (OpenposeAnnotator(..., face=<state dict or facenet.pth>))")
+        return self._face.run(src, keypoints, people, overflow, direct=self._direct())
 
     @staticmethod
     def _direct() -> bool:
@@ -585,9 +626,21 @@ class OpenposeAnnotator:
         d = self._run(src, None, None, 1)["decode"]
         return d["keypoints"].clone(), d["people"].clone(), d["overflow"].clone()
 
+    def faces(self, frames):
+        """-> (points int32 [n, MAX_PEOPLE, 71, 2] = (x, y) frame pixels of the face keypoints of the person of that row of poses(), -1 for
+        none; boxes int32 [n, MAX_PEOPLE, 4] = (x, y, side, slot) of util.faceDetect, side 0 for no box, slot -1 for a face that was not
+        taken; overflow int32 [n]: poses()'s bits and OVERFLOW_FACES | OVERFLOW_FACE_RESIZE), on the device, as new tensors."""
+        if self._face is None:
+            raise NotImplementedError("no face network was given (OpenposeAnnotator(..., face=<state dict or facenet.pth>))")
+        src = self._frames(frames)
+        self._run(src, None, None, 1, face=True)
+        b = self._face.workspace(*src.shape[:3], src.device)["buf"]
+        return b["points"].clone(), b["boxes"].clone(), b["overflow"].clone()
+
     def skeleton(self, frames, out=None):
         """frames: a list of PIL images / uint8 arrays of one size, or a uint8 tensor [n, H, W, C] (no host copy when it is on the
-        device) -> uint8 device tensor [n, H, W, 3] (RGB: the detector's drawing on black), written into `out` when given."""
+        device) -> uint8 device tensor [n, H, W, 3] (RGB: the detector's drawing on black, with the face dots when there is a face
+        network), written into `out` when given."""
         import torch
         src = self._frames(frames)
         n, h, w, _ = src.shape

@@ -1216,6 +1216,54 @@ int ca_pose_assemble(const int32_t* peaks, const float* scores, const int32_t* c
 int ca_pose_draw(const int32_t* coords, const int32_t* people, const float* sin_table, uint32_t* index, uint8_t* map, void* control, int32_t images, int32_t h,
                  int32_t w, int32_t rep, int32_t control_dtype, void* stream);
 
+/* ---- added to ABI v16 likewise: the face stage of the OpenPose annotator, around the face network that ca_conv3x3 / ca_maxpool2x2 /
+ * ca_gemm / ca_conv7x7 / ca_copy_cols run (controlanimate_amd/openpose_face.py; csrc/ca_openpose_face.hip, ca_pose_draw_faces in
+ * csrc/ca_openpose.hip; the specification is tests/face_ref.py) ---- */
+#define CA_FACE_SIZE 384              /* every crop is resized to 384 x 384 */
+#define CA_FACE_HEAT 48               /* the network's output is 48 x 48 */
+#define CA_FACE_PARTS 71              /* heat maps that are read for peaks (the network writes 72 columns, the last one zero) */
+#define CA_FACE_MIN_SIDE 11           /* the smallest side of a crop the box rule can produce */
+#define CA_FACE_SLOT_INTS 8           /* a slot: person (-1: empty), x, y, w, hc, wc, mode, 0 */
+#define CA_FACE_MODE_NONE 0           /* empty slot, or a crop shape whose resize is not restated: constant input, no points */
+#define CA_FACE_MODE_LANCZOS4 1
+#define CA_FACE_MODE_AREA 2
+#define CA_POSE_OVERFLOW_FACES 4        /* more people with a face box than max_faces: the first max_faces in person order are taken */
+#define CA_POSE_OVERFLOW_FACE_RESIZE 8  /* a face was skipped: INTER_AREA while an axis grows, or both scales integers with one >= 2 */
+
+/* util.faceDetect per person, from keypoints int32 [images, 64, 18, 2] (pixels, -1: missing) and people int32 [images]: the box from
+ * the nose (0), eyes (14, 15: 3.0 x) and ears (16, 17: 1.5 x), in exact integer arithmetic on half pixels -> boxes int32 [images, 64, 4]
+ * = (x, y, w, slot) (w = 0 and slot = -1 where there is no box; slot = -1 too where the box got no slot), slots int32 [images, max_faces,
+ * CA_FACE_SLOT_INTS] in person order, overflow[img] = (overflow_in ? overflow_in[img] : 0) | the two face bits.  The crop of a box is
+ * rows y .. y + hc - 1, columns x .. x + wc - 1 with hc = min(w, h - y), wc = min(w, w_px - x); the mode is CA_FACE_MODE_AREA when hc +
+ * wc > 768, else CA_FACE_MODE_LANCZOS4 (smart_resize's k < 1), CA_FACE_MODE_NONE for the shapes of CA_POSE_OVERFLOW_FACE_RESIZE. */
+int ca_face_boxes(const int32_t* keypoints, const int32_t* people, const int32_t* overflow_in, int32_t* boxes, int32_t* slots, int32_t* overflow, int32_t images,
+                  int32_t h, int32_t w, int32_t max_faces, void* stream);
+
+/* The crops of slots first .. first + crops - 1 (of images * max_faces) of uint8 RGB frames [images, h, w, 3] -> out [crops, 384, 384, 8] of
+ * dtype: cv2.resize of the BGR crop to 384 x 384, byte / 256 - 0.5, channels 3 .. 7 zero; zeros for a slot of CA_FACE_MODE_NONE.  Tables
+ * per crop side s of an axis (made on the host): INTER_LANCZOS4 for s = CA_FACE_MIN_SIDE .. side_max, lz_ofs int32 [.., 384] and lz_coef
+ * int16 [.., 384, 8] (11-bit fixed point; indices clamped to the crop; (sum + 2^21) >> 22); INTER_AREA for s = 384 .. side_max, ar_ofs /
+ * ar_cnt int32 [.., 384] and ar_w fp32 [.., 384, 8] (horizontal sums first, then their vertical sum, fp32, no fused multiply-add,
+ * rounded half to even).  A block owns two output rows: the horizontal pass of the source rows under them into LDS, then the vertical
+ * pass; the host checks that no table a slot can use spans more than the 13 source rows a block keeps (a LANCZOS4 slot with hc + wc > 768
+ * is treated as empty).  max(h, w) <= side_max <= 2048. */
+int ca_face_crop(const uint8_t* frames, const int32_t* slots, void* out, const int32_t* lz_ofs, const int16_t* lz_coef, const int32_t* ar_ofs, const int32_t* ar_cnt,
+                 const float* ar_w, int32_t images, int32_t h, int32_t w, int32_t max_faces, int32_t first, int32_t crops, int32_t side_max, int32_t dtype,
+                 void* stream);
+
+/* heat fp32 [images * max_faces, 48, 48, 72] and the slots -> points int32 [images, 64, 71, 2] (frame pixels, -1: none; every row
+ * without a slot is -1), the point written to the row of the slot's person.  Per (crop, part) one block evaluates F.interpolate(bilinear,
+ * align_corners = True) to (hc, wc) at every crop pixel in fp32 (the plane is never written) and keeps the largest value above 0.05 at
+ * its first row-major position; a local coordinate 0 makes that axis -1, otherwise the box origin is added.  A slot of CA_FACE_MODE_NONE, or one
+ * whose crop would leave the h x w frame, gives no points. */
+int ca_face_peaks(const float* heat, const int32_t* slots, int32_t* points, int32_t images, int32_t max_faces, int32_t h, int32_t w, void* stream);
+
+/* ca_pose_draw with faces: per person the 35 body primitives, then 71 filled radius-3 white discs (draw_facepose) at (xmap[px], ymap[py])
+ * of points int32 [images, 64, 71, 2] where both are > 0; primitive person * 106 + k.  xmap int32 [w], ymap int32 [h]:
+ * int(float32(float32(p) / side) * side), made on the host.  points == NULL draws the bodies only: ca_pose_draw's bytes. */
+int ca_pose_draw_faces(const int32_t* coords, const int32_t* people, const float* sin_table, const int32_t* points, const int32_t* xmap, const int32_t* ymap,
+                       uint32_t* index, uint8_t* map, void* control, int32_t images, int32_t h, int32_t w, int32_t rep, int32_t control_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
