@@ -23,6 +23,9 @@ CA_POSE_OVERFLOW_PEAKS, CA_POSE_OVERFLOW_PEOPLE = 1, 2
 CA_POSE_OVERFLOW_FACES, CA_POSE_OVERFLOW_FACE_RESIZE = 4, 8  # the face stage (openpose_face.py)
 CA_FACE_SIZE, CA_FACE_HEAT, CA_FACE_PARTS, CA_FACE_MIN_SIDE, CA_FACE_SLOT_INTS = 384, 48, 71, 11, 8
 CA_FACE_MODE_NONE, CA_FACE_MODE_LANCZOS4, CA_FACE_MODE_AREA = 0, 1, 2
+CA_POSE_OVERFLOW_HANDS, CA_POSE_OVERFLOW_HAND_RESIZE = 16, 32  # the hand stage (openpose_hand.py)
+CA_HAND_PARTS, CA_HAND_HEAT_COLS, CA_HAND_MAP, CA_HAND_SCALES, CA_HAND_SLOT_INTS = 21, 24, 128, 4, 8
+CA_HAND_MODE_NONE, CA_HAND_MODE_RESIZE, CA_HAND_MIN_BOX, CA_HAND_AREA_TAPS = 0, 1, 20, 16
 ABI_VERSION = 16
 
 
@@ -340,6 +343,12 @@ SYMBOLS = {
     "ca_face_crop": (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 8 + [C.c_void_p]),
     "ca_face_peaks": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p]),
     "ca_pose_draw_faces": (C.c_int, [C.c_void_p] * 9 + [C.c_int32] * 5 + [C.c_void_p]),
+    # added to ABI v16 likewise: the hand stage of the OpenPose annotator around its network (controlanimate_amd/openpose_hand.py)
+    "ca_hand_boxes": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_void_p]),
+    "ca_hand_crop": (C.c_int, [C.c_void_p] * 10 + [C.c_int32] * 10 + [C.c_void_p]),
+    "ca_hand_maps": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] + [C.c_void_p]),
+    "ca_hand_peaks": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_void_p]),
+    "ca_pose_draw_hands": (C.c_int, [C.c_void_p] * 10 + [C.c_int32] * 5 + [C.c_void_p]),
 }
 
 _lib = None

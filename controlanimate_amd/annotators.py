@@ -26,8 +26,8 @@ against transformers' and Pillow's own modules.  So is openpose, the first Contr
 (openpose.py, re-exported here) runs bodypose_model, the skeleton decode and the drawing of controlnet_aux's OpenposeDetector on the
 device from a local body_pose_model.pth, opt-in through `annotators={"openpose": OpenposeAnnotator.from_pretrained(path)}` (the key serves
 control_v11p_sd15_openpose and sd-controlnet-openpose alike).  Given a face network (`face=<facenet.pth>`) it also draws the face
-keypoints of the reference's hand_and_face=True (openpose_face.py); without one it draws the BODY skeleton only.  The hands are still
-missing.
+keypoints of the reference's hand_and_face=True (openpose_face.py); without one it draws the BODY skeleton only.  Given a hand network
+(`hand=<hand_pose_model.pth>`) it draws the hands too (openpose_hand.py); with both, the drawing is the reference's hand_and_face=True.
 (The face restorer of the emitted frames is not an annotator and lives in gfpgan.py: GFPGANv1Clean for aligned 512 x 512 faces on the HIP
 kernels, around a caller-supplied helper for detection, warp and paste-back; UNPINNED against gfpgan and real weights; no CPU fallback.)
 

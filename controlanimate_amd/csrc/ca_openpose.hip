@@ -676,7 +676,7 @@ __global__ __launch_bounds__(256) void k_pose_raster(const int32_t* __restrict__
 // draw_facepose: a filled radius-3 disc at (xmap[px], ymap[py]) of every face point whose two coordinates come out positive.  A block per
 // (person, frame); a thread per pixel of the 7 x 7 square around a point.
 __global__ __launch_bounds__(256) void k_face_raster(const int32_t* __restrict__ points, const int32_t* __restrict__ people, const int32_t* __restrict__ xmap,
-                                                     const int32_t* __restrict__ ymap, unsigned* __restrict__ index, int H, int W) {
+                                                     const int32_t* __restrict__ ymap, unsigned* __restrict__ index, int H, int W, int prims, int base) {
   const int person = blockIdx.x, img = blockIdx.y;
   int np = people[img];
   np = np < 0 ? 0 : (np > kMaxPeople ? kMaxPeople : np);
@@ -690,7 +690,207 @@ __global__ __launch_bounds__(256) void k_face_raster(const int32_t* __restrict__
     const int cx = xmap[px], cy = ymap[py];
     if (!(cx > 0 && cy > 0)) continue;  // x > eps and y > eps of integers
     const int half = c_disc_half[dy < 0 ? -dy : dy];
-    if (dx >= -half && dx <= half) put(plane, H, W, cx + dx, cy + dy, (unsigned)(person * kPrimsFace + kPrims + q) + 1u);
+    if (dx >= -half && dx <= half) put(plane, H, W, cx + dx, cy + dy, (unsigned)(person * prims + base + q) + 1u);
+  }
+}
+
+// draw_handpose: per hand 20 edges cv2.line(thickness = 2) and then 21 filled circles of radius 4.  A thick line is OpenCV's ThickLine:
+// the endpoints at 16 fractional bits, dp = (cvRound(dy r), cvRound(dx r)) with r = 65536 / sqrt(dx^2 + dy^2), the four corners p0 +- dp,
+// p1 -+ dp through FillConvexPoly at shift 16 (the outline with Line2, then the rows between the two edge chains), and a filled circle of
+// radius 1 at each end; a zero-length edge draws only the circles.  An edge is short and thin, so one thread walks it.
+__device__ bool cv_clip_line(long long wd, long long ht, long long& x1, long long& y1, long long& x2, long long& y2) {
+  const long long right = wd - 1, bottom = ht - 1;
+  if (wd <= 0 || ht <= 0) return false;
+  int c1 = (x1 < 0) + (x1 > right) * 2 + (y1 < 0) * 4 + (y1 > bottom) * 8;
+  int c2 = (x2 < 0) + (x2 > right) * 2 + (y2 < 0) * 4 + (y2 > bottom) * 8;
+  if ((c1 & c2) == 0 && (c1 | c2) != 0) {
+    long long a;
+    if (c1 & 12) {
+      a = c1 < 8 ? 0 : bottom;
+      x1 += (long long)((double)(a - y1) * (double)(x2 - x1) / (double)(y2 - y1));
+      y1 = a;
+      c1 = (x1 < 0) + (x1 > right) * 2;
+    }
+    if (c2 & 12) {
+      a = c2 < 8 ? 0 : bottom;
+      x2 += (long long)((double)(a - y2) * (double)(x2 - x1) / (double)(y2 - y1));
+      y2 = a;
+      c2 = (x2 < 0) + (x2 > right) * 2;
+    }
+    if ((c1 & c2) == 0 && (c1 | c2) != 0) {
+      if (c1) {
+        a = c1 == 1 ? 0 : right;
+        y1 += (long long)((double)(a - x1) * (double)(y2 - y1) / (double)(x2 - x1));
+        x1 = a;
+        c1 = 0;
+      }
+      if (c2) {
+        a = c2 == 1 ? 0 : right;
+        y2 += (long long)((double)(a - x2) * (double)(y2 - y1) / (double)(x2 - x1));
+        x2 = a;
+        c2 = 0;
+      }
+    }
+  }
+  return (c1 | c2) == 0;
+}
+
+// OpenCV's Line2: a line between two points at 16 fractional bits, one pixel per step of the longer axis.
+__device__ void cv_line2(unsigned* plane, int H, int W, unsigned v, long long x1, long long y1, long long x2, long long y2) {
+  if (!cv_clip_line((long long)W << 16, (long long)H << 16, x1, y1, x2, y2)) return;
+  long long dx = x2 - x1, dy = y2 - y1;
+  const long long ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
+  long long x_step, y_step;
+  int ecount;
+  if (ax > ay) {
+    if (dx < 0) {
+      long long t = x1;
+      x1 = x2, x2 = t, t = y1, y1 = y2, y2 = t, dy = -dy;
+    }
+    x_step = 65536, y_step = (dy * 65536) / (ax | 1);
+    ecount = (int)((x2 - x1) >> 16);
+  } else {
+    if (dy < 0) {
+      long long t = x1;
+      x1 = x2, x2 = t, t = y1, y1 = y2, y2 = t, dx = -dx;
+    }
+    x_step = (dx * 65536) / (ay | 1), y_step = 65536;
+    ecount = (int)((y2 - y1) >> 16);
+  }
+  x1 += 32768, y1 += 32768;
+  put(plane, H, W, (x2 + 32768) >> 16, (y2 + 32768) >> 16, v);
+  if (ax > ay) {
+    x1 >>= 16;
+    for (int k = 0; k <= kMaxSide; ++k) {
+      if (k > ecount) break;
+      put(plane, H, W, x1, y1 >> 16, v);
+      x1 += 1, y1 += y_step;
+    }
+  } else {
+    y1 >>= 16;
+    for (int k = 0; k <= kMaxSide; ++k) {
+      if (k > ecount) break;
+      put(plane, H, W, x1 >> 16, y1, v);
+      x1 += x_step, y1 += 1;
+    }
+  }
+  (void)x_step;
+}
+
+// FillConvexPoly(pts, 4, line_type 8, shift 16): the routine k_pose_raster runs at shift 0 for the limbs, for four corners at 16 fractional bits.
+__device__ void cv_fill_quad16(unsigned* plane, int H, int W, unsigned v, const long long* vx, const long long* vy) {
+  constexpr int n = 4;
+  constexpr long long delta = 32768;
+  long long xmin = vx[0], xmax = vx[0], ymin = vy[0], ymax = vy[0];
+  int imin = 0;
+  for (int i = 0; i < n; ++i) {
+    if (vy[i] < ymin) ymin = vy[i], imin = i;
+    ymax = vy[i] > ymax ? vy[i] : ymax;
+    xmax = vx[i] > xmax ? vx[i] : xmax;
+    xmin = vx[i] < xmin ? vx[i] : xmin;
+    const int i0 = i == 0 ? n - 1 : i - 1;
+    cv_line2(plane, H, W, v, vx[i0], vy[i0], vx[i], vy[i]);
+  }
+  xmin = (xmin + delta) >> 16, xmax = (xmax + delta) >> 16, ymin = (ymin + delta) >> 16, ymax = (ymax + delta) >> 16;
+  if ((int)xmax < 0 || (int)ymax < 0 || (int)xmin >= W || (int)ymin >= H) return;
+  ymax = ymax < H - 1 ? ymax : H - 1;
+  int e_idx[2] = {imin, imin}, e_di[2] = {1, n - 1}, e_ye[2] = {(int)ymin, (int)ymin};
+  long long e_x[2] = {-65536, -65536}, e_dx[2] = {0, 0};
+  int edges = n, y = (int)ymin;
+  for (int step = 0; step < 3 * kMaxSide; ++step) {
+    for (int e = 0; e < 2; ++e) {
+      if (y >= e_ye[e]) {
+        int idx0 = e_idx[e];
+        const int di = e_di[e];
+        int idx = idx0 + di;
+        if (idx >= n) idx -= n;
+        for (int guard = 0; guard <= n; ++guard) {
+          const int had = edges;
+          edges -= 1;
+          if (!(had > 0)) break;
+          const int ty = (int)((vy[idx] + delta) >> 16);
+          if (ty > y) {
+            const long long xs = vx[idx0], xe = vx[idx];
+            e_ye[e] = ty;
+            e_dx[e] = ((xe - xs) * 2 + (ty - y)) / (2 * (ty - y));
+            e_x[e] = xs;
+            e_idx[e] = idx;
+            break;
+          }
+          idx0 = idx;
+          idx += di;
+          if (idx >= n) idx -= n;
+        }
+      }
+    }
+    if (edges < 0) break;
+    if (y >= 0) {
+      const int left = e_x[0] > e_x[1] ? 1 : 0, right = 1 - left;
+      int xx1 = (int)((e_x[left] + 32768) >> 16), xx2 = (int)((e_x[right] + 32768) >> 16);
+      if (xx2 >= 0 && xx1 < W) {
+        xx1 = xx1 < 0 ? 0 : xx1;
+        xx2 = xx2 >= W ? W - 1 : xx2;
+        for (int x = 0; x < kMaxSide; ++x) {
+          if (xx1 + x > xx2) break;
+          put(plane, H, W, xx1 + x, y, v);
+        }
+      }
+    }
+    e_x[0] += e_dx[0], e_x[1] += e_dx[1];
+    if (++y > (int)ymax) break;
+  }
+}
+
+__constant__ unsigned char c_hand_color[20][3] = {{255, 0, 0},   {255, 77, 0},  {255, 153, 0}, {255, 229, 0}, {204, 255, 0}, {128, 255, 0}, {51, 255, 0},
+                                                  {0, 255, 25},  {0, 255, 102}, {0, 255, 179}, {0, 255, 255}, {0, 178, 255}, {0, 102, 255}, {0, 25, 255},
+                                                  {51, 0, 255},  {128, 0, 255}, {204, 0, 255}, {255, 0, 230}, {255, 0, 153}, {255, 0, 77}};  // openpose_hand.hand_colors()
+__constant__ int c_hand_edge[20][2] = {{0, 1},  {1, 2},   {2, 3},   {3, 4},   {0, 5},   {5, 6},   {6, 7},   {7, 8},   {0, 9},   {9, 10},
+                                       {10, 11}, {11, 12}, {0, 13}, {13, 14}, {14, 15}, {15, 16}, {0, 17}, {17, 18}, {18, 19}, {19, 20}};
+constexpr int kHandParts = CA_HAND_PARTS, kHandEdges = 20, kHandPrims = kHandEdges + kHandParts;  // 41 per hand
+constexpr int kPrimsAll = kPrims + 2 * kHandPrims + kFaceParts;                                     // body, left hand, right hand, face
+
+// A block per (primitive of a hand, hand of a person, frame): hand_points int32 [images, 64, 2, 21, 2].
+__global__ __launch_bounds__(64) void k_hand_raster(const int32_t* __restrict__ points, const int32_t* __restrict__ people, const int32_t* __restrict__ xmap,
+                                                    const int32_t* __restrict__ ymap, unsigned* __restrict__ index, int H, int W) {
+  const int prim = blockIdx.x, person = blockIdx.y >> 1, hand = blockIdx.y & 1, img = blockIdx.z, tid = threadIdx.x;
+  int np = people[img];
+  np = np < 0 ? 0 : (np > kMaxPeople ? kMaxPeople : np);
+  if (person >= np) return;
+  const int32_t* pt = points + (((int64_t)img * kMaxPeople + person) * 2 + hand) * kHandParts * 2;
+  unsigned* plane = index + (int64_t)img * H * W;
+  const unsigned value = (unsigned)(person * kPrimsAll + kPrims + hand * kHandPrims + prim) + 1u;
+  if (prim >= kHandEdges) {  // cv2.circle(canvas, (x, y), 4, (0, 0, 255), -1)
+    const int q = prim - kHandEdges;
+    const int px = pt[q * 2], py = pt[q * 2 + 1];
+    if (px < 0 || py < 0 || px >= W || py >= H) return;
+    const int cx = xmap[px], cy = ymap[py];
+    if (!(cx > 0 && cy > 0)) return;
+    for (int i = tid; i < 81; i += 64) {
+      const int dy = i / 9 - 4, dx = i % 9 - 4;
+      const int half = c_circle_half[dy < 0 ? -dy : dy];
+      if (dx >= -half && dx <= half) put(plane, H, W, cx + dx, cy + dy, value);
+    }
+    return;
+  }
+  if (tid != 0) return;
+  const int a = c_hand_edge[prim][0], b = c_hand_edge[prim][1];
+  const int ax = pt[a * 2], ay = pt[a * 2 + 1], bx = pt[b * 2], by = pt[b * 2 + 1];
+  if (ax < 0 || ay < 0 || bx < 0 || by < 0 || ax >= W || bx >= W || ay >= H || by >= H) return;
+  const int x1 = xmap[ax], y1 = ymap[ay], x2 = xmap[bx], y2 = ymap[by];
+  if (!(x1 > 0 && y1 > 0 && x2 > 0 && y2 > 0)) return;
+  const long long p0x = (long long)x1 << 16, p0y = (long long)y1 << 16, p1x = (long long)x2 << 16, p1y = (long long)y2 << 16;
+  const double dx = (double)(p0x - p1x) * (1.0 / 65536.0), dy = (double)(p1y - p0y) * (1.0 / 65536.0);
+  double r = dx * dx + dy * dy;
+  if (fabs(r) > 2.220446049250313e-16) {
+    r = 65536.0 / sqrt(r);
+    const long long dpx = (long long)rint(dy * r), dpy = (long long)rint(dx * r);
+    const long long vx[4] = {p0x + dpx, p0x - dpx, p1x - dpx, p1x + dpx}, vy[4] = {p0y + dpy, p0y - dpy, p1y - dpy, p1y + dpy};
+    cv_fill_quad16(plane, H, W, value, vx, vy);
+  }
+  const int ex[2] = {x1, x2}, ey[2] = {y1, y2};
+  for (int e = 0; e < 2; ++e) {  // Circle(center, 1, filled): the centre's row three wide, one pixel above and below
+    put(plane, H, W, ex[e] - 1, ey[e], value), put(plane, H, W, ex[e], ey[e], value), put(plane, H, W, ex[e] + 1, ey[e], value);
+    put(plane, H, W, ex[e], ey[e] - 1, value), put(plane, H, W, ex[e], ey[e] + 1, value);
   }
 }
 
@@ -703,7 +903,7 @@ __device__ __forceinline__ u16 ctrl_of<u16>(int level) { return Elem<CA_F16>::fr
 
 template <typename T>
 __global__ __launch_bounds__(256) void k_pose_resolve(const unsigned* __restrict__ index, uint8_t* __restrict__ map, T* __restrict__ ctrl, int images, int64_t hw,
-                                                      int rep, int prims) {
+                                                      int rep, int prims, int hands) {
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (g >= images * hw) return;
   const int img = (int)(g / hw);
@@ -715,6 +915,11 @@ __global__ __launch_bounds__(256) void k_pose_resolve(const unsigned* __restrict
 #pragma unroll
     for (int c = 0; c < 3; ++c)
       rgb[c] = prim < kDrawLimbs ? (int)((double)c_color[prim][c] * 0.6) : (prim < kPrims ? (int)c_color[prim - kDrawLimbs][c] : 255);  // a face disc is white
+    if (hands && prim >= kPrims && prim < kPrims + 2 * kHandPrims) {  // a hand's edge in its hsv colour, its circles (0, 0, 255)
+      const int j = (prim - kPrims) % kHandPrims;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) rgb[c] = j < kHandEdges ? (int)c_hand_color[j][c] : (c == 2 ? 255 : 0);
+    }
   }
   if (map) {
 #pragma unroll
@@ -895,8 +1100,8 @@ extern "C" int ca_pose_draw(const int32_t* coords, const int32_t* people, const 
   if (e != hipSuccess) CA_FAIL(CA_ERR_LAUNCH, "ca_pose_draw: %s", hipGetErrorString(e));
   hipLaunchKernelGGL(k_pose_raster, dim3(kPrims, kMaxPeople, (unsigned)images), dim3(256), 0, st, coords, people, sin_table, (unsigned*)index, (int)h, (int)w, kPrims);
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (control_dtype == CA_F32) hipLaunchKernelGGL(k_pose_resolve<float>, grid, block, 0, st, (const unsigned*)index, map, (float*)control, (int)images, hw, (int)rep, kPrims);
-  else hipLaunchKernelGGL(k_pose_resolve<u16>, grid, block, 0, st, (const unsigned*)index, map, (u16*)control, (int)images, hw, (int)rep, kPrims);
+  if (control_dtype == CA_F32) hipLaunchKernelGGL(k_pose_resolve<float>, grid, block, 0, st, (const unsigned*)index, map, (float*)control, (int)images, hw, (int)rep, kPrims, 0);
+  else hipLaunchKernelGGL(k_pose_resolve<u16>, grid, block, 0, st, (const unsigned*)index, map, (u16*)control, (int)images, hw, (int)rep, kPrims, 0);
   CA_CHECK_LAUNCH("ca_pose_draw");
   return CA_OK;
 }
@@ -919,12 +1124,42 @@ extern "C" int ca_pose_draw_faces(const int32_t* coords, const int32_t* people, 
   hipError_t e = hipMemsetAsync(index, 0, (size_t)total * 4, st);
   if (e != hipSuccess) CA_FAIL(CA_ERR_LAUNCH, "ca_pose_draw_faces: %s", hipGetErrorString(e));
   hipLaunchKernelGGL(k_pose_raster, dim3(kPrims, kMaxPeople, (unsigned)images), dim3(256), 0, st, coords, people, sin_table, (unsigned*)index, (int)h, (int)w, kPrimsFace);
-  if (points) hipLaunchKernelGGL(k_face_raster, dim3(kMaxPeople, (unsigned)images), dim3(256), 0, st, points, people, xmap, ymap, (unsigned*)index, (int)h, (int)w);
+  if (points) hipLaunchKernelGGL(k_face_raster, dim3(kMaxPeople, (unsigned)images), dim3(256), 0, st, points, people, xmap, ymap, (unsigned*)index, (int)h, (int)w, kPrimsFace, kPrims);
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
   if (control_dtype == CA_F32)
-    hipLaunchKernelGGL(k_pose_resolve<float>, grid, block, 0, st, (const unsigned*)index, map, (float*)control, (int)images, hw, (int)rep, kPrimsFace);
+    hipLaunchKernelGGL(k_pose_resolve<float>, grid, block, 0, st, (const unsigned*)index, map, (float*)control, (int)images, hw, (int)rep, kPrimsFace, 0);
   else
-    hipLaunchKernelGGL(k_pose_resolve<u16>, grid, block, 0, st, (const unsigned*)index, map, (u16*)control, (int)images, hw, (int)rep, kPrimsFace);
+    hipLaunchKernelGGL(k_pose_resolve<u16>, grid, block, 0, st, (const unsigned*)index, map, (u16*)control, (int)images, hw, (int)rep, kPrimsFace, 0);
   CA_CHECK_LAUNCH("ca_pose_draw_faces");
+  return CA_OK;
+}
+
+extern "C" int ca_pose_draw_hands(const int32_t* coords, const int32_t* people, const float* sin_table, const int32_t* hand_points, const int32_t* face_points,
+                                  const int32_t* xmap, const int32_t* ymap, uint32_t* index, uint8_t* map, void* control, int32_t images, int32_t h, int32_t w,
+                                  int32_t rep, int32_t control_dtype, void* stream) {
+  CA_REQUIRE(coords && people && sin_table && index && hand_points && xmap && ymap, "ca_pose_draw_hands: coords, people, sin_table, hand_points, xmap, ymap and index are required");
+  CA_REQUIRE(map || control, "ca_pose_draw_hands: map or control is required");
+  CA_REQUIRE(sizes_ok(images, h, w) && images <= 65535 && h <= kMaxSide && w <= kMaxSide,
+             "ca_pose_draw_hands: images=%d h=%d w=%d (each >= 1, images <= 65535, h and w <= %d, images * h * w < 2^31)", images, h, w, kMaxSide);
+  CA_REQUIRE(rep == 1 || rep == 2, "ca_pose_draw_hands: rep=%d (1 or 2)", rep);
+  CA_REQUIRE(control_dtype == CA_F16 || control_dtype == CA_F32, "ca_pose_draw_hands: control_dtype=%d (CA_F16 or CA_F32)", control_dtype);
+  CA_REQUIRE((((uintptr_t)coords | (uintptr_t)people | (uintptr_t)sin_table | (uintptr_t)index | (uintptr_t)hand_points | (uintptr_t)face_points | (uintptr_t)xmap |
+               (uintptr_t)ymap) & 3) == 0 && ((uintptr_t)control & (control_dtype == CA_F32 ? 3 : 1)) == 0,
+             "ca_pose_draw_hands: coords, people, sin_table, the points, xmap, ymap and index must be 4-byte aligned, control aligned to its element");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t hw = (int64_t)h * w, total = (int64_t)images * hw;
+  hipError_t e = hipMemsetAsync(index, 0, (size_t)total * 4, st);
+  if (e != hipSuccess) CA_FAIL(CA_ERR_LAUNCH, "ca_pose_draw_hands: %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(k_pose_raster, dim3(kPrims, kMaxPeople, (unsigned)images), dim3(256), 0, st, coords, people, sin_table, (unsigned*)index, (int)h, (int)w, kPrimsAll);
+  hipLaunchKernelGGL(k_hand_raster, dim3(kHandPrims, 2 * kMaxPeople, (unsigned)images), dim3(64), 0, st, hand_points, people, xmap, ymap, (unsigned*)index, (int)h, (int)w);
+  if (face_points)
+    hipLaunchKernelGGL(k_face_raster, dim3(kMaxPeople, (unsigned)images), dim3(256), 0, st, face_points, people, xmap, ymap, (unsigned*)index, (int)h, (int)w, kPrimsAll,
+                       kPrims + 2 * kHandPrims);
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  if (control_dtype == CA_F32)
+    hipLaunchKernelGGL(k_pose_resolve<float>, grid, block, 0, st, (const unsigned*)index, map, (float*)control, (int)images, hw, (int)rep, kPrimsAll, 1);
+  else
+    hipLaunchKernelGGL(k_pose_resolve<u16>, grid, block, 0, st, (const unsigned*)index, map, (u16*)control, (int)images, hw, (int)rep, kPrimsAll, 1);
+  CA_CHECK_LAUNCH("ca_pose_draw_hands");
   return CA_OK;
 }

@@ -1977,3 +1977,129 @@ def pose_draw_faces(coords: torch.Tensor, people: torch.Tensor, sin_table: torch
     check(lib().ca_pose_draw_faces(_p(coords), _p(people), _p(sin_table), _p(points), _p(xmap), _p(ymap), _p(index), _p(skeleton), _p(control), n, h, w, int(rep), dt,
                                    _stream()), "ca_pose_draw_faces")
     return skeleton
+
+
+# ---- added to ABI v16: the hand stage of the OpenPose annotator around its network (controlanimate_amd/openpose_hand.py) ------------------
+
+POSE_OVERFLOW_HANDS, POSE_OVERFLOW_HAND_RESIZE = _capi.CA_POSE_OVERFLOW_HANDS, _capi.CA_POSE_OVERFLOW_HAND_RESIZE
+HAND_PARTS, HAND_HEAT_COLS, HAND_MAP, HAND_SCALES, HAND_SLOT_INTS = _capi.CA_HAND_PARTS, _capi.CA_HAND_HEAT_COLS, _capi.CA_HAND_MAP, _capi.CA_HAND_SCALES, _capi.CA_HAND_SLOT_INTS
+HAND_MODE_NONE, HAND_MODE_RESIZE = _capi.CA_HAND_MODE_NONE, _capi.CA_HAND_MODE_RESIZE
+HAND_MAP_SIDES = (23, 46, 69, 92)
+
+
+def hand_buffers(n: int, max_hands: int, device) -> dict:
+    """The tensors the hand stage's launches pass on, for n frames."""
+    i32 = dict(dtype=torch.int32, device=device)
+    slots = n * max_hands
+    return {"boxes": torch.empty((n, POSE_MAX_PEOPLE, 2, 4), **i32), "slots": torch.empty((n, max_hands, HAND_SLOT_INTS), **i32), "overflow": torch.empty((n,), **i32),
+            "points": torch.empty((n, POSE_MAX_PEOPLE, 2, HAND_PARTS, 2), **i32), "peaks": torch.empty((slots, HAND_PARTS, 2), **i32),
+            "mass": torch.empty((slots, HAND_PARTS), dtype=torch.float64, device=device),
+            "raw": torch.empty((slots, HAND_PARTS, HAND_MAP, HAND_MAP), dtype=torch.float32, device=device),
+            "smooth": torch.empty((slots, HAND_PARTS, HAND_MAP, HAND_MAP), dtype=torch.float32, device=device)}
+
+
+def hand_boxes(keypoints: torch.Tensor, people: torch.Tensor, h: int, w: int, buf: dict, overflow_in: Optional[torch.Tensor] = None) -> dict:
+    """util.handDetect per person of keypoints int32 [images, 64, 18, 2] / people int32 [images] -> buf["boxes"] [images, 64, 2, 4] (x, y, w,
+    slot; left then right), buf["slots"] [images, max_hands, 8] (person, x, y, w, hand, mode, 0, 0) and buf["overflow"] = overflow_in | the
+    hand bits (ca_hand_boxes)."""
+    _req_cuda(keypoints, people, overflow_in, buf["boxes"], buf["slots"], buf["overflow"])
+    n = keypoints.shape[0]
+    assert keypoints.dtype == torch.int32 and tuple(keypoints.shape) == (n, POSE_MAX_PEOPLE, POSE_PARTS, 2) and keypoints.is_contiguous()
+    assert people.dtype == torch.int32 and tuple(people.shape) == (n,) and people.is_contiguous()
+    assert overflow_in is None or (overflow_in.dtype == torch.int32 and tuple(overflow_in.shape) == (n,) and overflow_in.is_contiguous())
+    max_hands = buf["slots"].shape[1]
+    assert tuple(buf["boxes"].shape) == (n, POSE_MAX_PEOPLE, 2, 4) and tuple(buf["slots"].shape) == (n, max_hands, HAND_SLOT_INTS) and tuple(buf["overflow"].shape) == (n,)
+    _req_i32(buf["boxes"], buf["slots"], buf["overflow"])
+    check(lib().ca_hand_boxes(_p(keypoints), _p(people), _p(overflow_in), _p(buf["boxes"]), _p(buf["slots"]), _p(buf["overflow"]), n, h, w, max_hands, _stream()),
+          "ca_hand_boxes")
+    return buf
+
+
+def hand_crop(frames: torch.Tensor, slots: torch.Tensor, tables: dict, blurred: torch.Tensor, out: torch.Tensor, first: int = 0, blur: bool = True) -> torch.Tensor:
+    """uint8 RGB [images, H, W, 3] and slots [images, max_hands, 8] -> `out` [crops, side, side, 8] fp16 / bf16: the Gaussian-blurred crops of
+    slots first .. first + crops - 1 resized to side x side as cv2.resize does, BGR, x / 256 - 0.5 (ca_hand_crop).  blurred uint8 [images *
+    max_hands, min(H, W), min(H, W), 3] is written when `blur`, else read.  tables: openpose_hand.resize_tables(side, min(H, W)) on the
+    device (taps, lz_ofs, lz_coef, ar_ofs, ar_cnt, ar_w; the AREA ones None when no box can be wider than side)."""
+    _req_cuda(frames, slots, blurred, out, *[t for t in tables.values() if isinstance(t, torch.Tensor)])
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
+    n, h, w, _ = frames.shape
+    max_hands, side_max = slots.shape[1], min(h, w)
+    assert slots.dtype == torch.int32 and tuple(slots.shape) == (n, max_hands, HAND_SLOT_INTS) and slots.is_contiguous()
+    crops, side = out.shape[0], out.shape[1]
+    assert tuple(out.shape) == (crops, side, side, 8) and out.is_contiguous()
+    assert blurred.dtype == torch.uint8 and tuple(blurred.shape) == (n * max_hands, side_max, side_max, 3) and blurred.is_contiguous()
+    nl, na = min(side, side_max) - _capi.CA_HAND_MIN_BOX + 1, max(side_max - side, 0)
+    assert tables["taps"].dtype == torch.float64 and tuple(tables["taps"].shape) == (7,)
+    assert tuple(tables["lz_ofs"].shape) == (nl, side) and tuple(tables["lz_coef"].shape) == (nl, side, 8) and tables["lz_coef"].dtype == torch.int16
+    _req_i32(tables["lz_ofs"])
+    assert tables["lz_coef"].is_contiguous()
+    if na:
+        assert tuple(tables["ar_ofs"].shape) == (na, side) and tuple(tables["ar_cnt"].shape) == (na, side)
+        assert tuple(tables["ar_w"].shape) == (na, side, _capi.CA_HAND_AREA_TAPS) and tables["ar_w"].dtype == torch.float32 and tables["ar_w"].is_contiguous()
+        _req_i32(tables["ar_ofs"], tables["ar_cnt"])
+    check(lib().ca_hand_crop(_p(frames), _p(slots), _p(tables["taps"]), _p(blurred), _p(out), _p(tables["lz_ofs"]), _p(tables["lz_coef"]), _p(tables.get("ar_ofs")),
+                             _p(tables.get("ar_cnt")), _p(tables.get("ar_w")), n, h, w, max_hands, int(first), crops, side, side_max, int(bool(blur)), dt_code(out.dtype),
+                             _stream()), "ca_hand_crop")
+    return out
+
+
+def hand_maps(heats, mats: torch.Tensor, raw: torch.Tensor, smooth: torch.Tensor) -> None:
+    """heats: the network's fp32 maps of the four scales, [slots, m, m, 24] with m = 23, 46, 69, 92; mats fp32 [2, 230, 128]
+    (openpose_hand.map_matrices) -> raw, smooth fp32 [slots, 21, 128, 128]: the four-scale average and its sigma-3 Gaussian (ca_hand_maps)."""
+    _req_cuda(*heats, mats, raw, smooth)
+    slots = raw.shape[0]
+    assert len(heats) == HAND_SCALES
+    for m, t in zip(HAND_MAP_SIDES, heats):
+        assert t.dtype == torch.float32 and tuple(t.shape) == (slots, m, m, HAND_HEAT_COLS) and t.is_contiguous(), f"heat of side {m}: fp32 [{slots}, {m}, {m}, {HAND_HEAT_COLS}]"
+    assert mats.dtype == torch.float32 and tuple(mats.shape) == (2, sum(HAND_MAP_SIDES), HAND_MAP) and mats.is_contiguous()
+    for t in (raw, smooth):
+        assert t.dtype == torch.float32 and tuple(t.shape) == (slots, HAND_PARTS, HAND_MAP, HAND_MAP) and t.is_contiguous()
+    check(lib().ca_hand_maps(*[_p(t) for t in heats], _p(mats), _p(raw), _p(smooth), slots, _stream()), "ca_hand_maps")
+
+
+def hand_peaks(raw: torch.Tensor, smooth: torch.Tensor, buf: dict, h: int, w: int) -> dict:
+    """raw, smooth fp32 [images * max_hands, 21, 128, 128] and buf["slots"] -> buf["peaks"] (x, y on the 128 grid), buf["mass"] (the winning
+    component's double sum) and buf["points"] int32 [images, 64, 2, 21, 2] in frame pixels (ca_hand_peaks)."""
+    _req_cuda(raw, smooth, buf["slots"], buf["points"], buf["peaks"], buf["mass"])
+    n, max_hands = buf["slots"].shape[0], buf["slots"].shape[1]
+    slots = n * max_hands
+    for t in (raw, smooth):
+        assert t.dtype == torch.float32 and tuple(t.shape) == (slots, HAND_PARTS, HAND_MAP, HAND_MAP) and t.is_contiguous()
+    _req_i32(buf["slots"], buf["points"], buf["peaks"])
+    assert tuple(buf["slots"].shape) == (n, max_hands, HAND_SLOT_INTS) and tuple(buf["points"].shape) == (n, POSE_MAX_PEOPLE, 2, HAND_PARTS, 2)
+    assert tuple(buf["peaks"].shape) == (slots, HAND_PARTS, 2) and buf["mass"].dtype == torch.float64 and tuple(buf["mass"].shape) == (slots, HAND_PARTS)
+    assert buf["mass"].is_contiguous()
+    check(lib().ca_hand_peaks(_p(raw), _p(smooth), _p(buf["slots"]), _p(buf["points"]), _p(buf["peaks"]), _p(buf["mass"]), n, max_hands, h, w, _stream()), "ca_hand_peaks")
+    return buf
+
+
+def pose_draw_hands(coords: torch.Tensor, people: torch.Tensor, sin_table: torch.Tensor, hand_points: torch.Tensor, face_points: Optional[torch.Tensor],
+                    xmap: torch.Tensor, ymap: torch.Tensor, h: int, w: int, *, index: Optional[torch.Tensor] = None, skeleton: Optional[torch.Tensor] = None,
+                    control: Optional[torch.Tensor] = None, rep: int = 1) -> Optional[torch.Tensor]:
+    """pose_draw_faces with hands: per person the body, the left hand, the right hand (20 thickness-2 edges and 21 radius-4 circles each, from
+    hand_points int32 [images, 64, 2, 21, 2]), then the face discs (face_points int32 [images, 64, 71, 2] or None) (ca_pose_draw_hands)."""
+    _req_cuda(coords, people, sin_table, hand_points, face_points, xmap, ymap, index, skeleton, control)
+    n = coords.shape[0]
+    assert coords.dtype == torch.int32 and tuple(coords.shape) == (n, POSE_MAX_PEOPLE, POSE_PARTS, 2) and coords.is_contiguous()
+    assert people.dtype == torch.int32 and tuple(people.shape) == (n,) and people.is_contiguous()
+    assert sin_table.dtype == torch.float32 and sin_table.numel() == 451 and sin_table.is_contiguous()
+    assert hand_points.dtype == torch.int32 and tuple(hand_points.shape) == (n, POSE_MAX_PEOPLE, 2, HAND_PARTS, 2) and hand_points.is_contiguous()
+    if face_points is not None:
+        assert face_points.dtype == torch.int32 and tuple(face_points.shape) == (n, POSE_MAX_PEOPLE, FACE_PARTS, 2) and face_points.is_contiguous()
+    assert xmap.dtype == torch.int32 and tuple(xmap.shape) == (w,) and ymap.dtype == torch.int32 and tuple(ymap.shape) == (h,)
+    if index is None:
+        index = torch.empty((n, h, w), dtype=torch.int32, device=coords.device)
+    assert index.dtype == torch.int32 and tuple(index.shape) == (n, h, w) and index.is_contiguous()
+    if skeleton is None and control is None:
+        skeleton = torch.empty((n, h, w, 3), dtype=torch.uint8, device=coords.device)
+    if skeleton is not None:
+        assert skeleton.dtype == torch.uint8 and tuple(skeleton.shape) == (n, h, w, 3) and skeleton.is_contiguous()
+    dt = _capi.CA_F32
+    if control is not None:
+        if control.dtype not in _CANNY_DT:
+            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
+        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
+        dt = _CANNY_DT[control.dtype]
+    check(lib().ca_pose_draw_hands(_p(coords), _p(people), _p(sin_table), _p(hand_points), _p(face_points), _p(xmap), _p(ymap), _p(index), _p(skeleton), _p(control),
+                                   n, h, w, int(rep), dt, _stream()), "ca_pose_draw_hands")
+    return skeleton

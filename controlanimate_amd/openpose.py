@@ -5,8 +5,11 @@ modules/controlresiduals_pipeline.py:57, 107-113) on the GPU, for a whole window
 The reference calls the detector with hand_and_face=True, which additionally runs a hand network and a face network on crops around
 the detected body.  Without further weights this annotator draws the BODY skeleton only.  Given a face network
 (`OpenposeAnnotator(body, face=<state dict or facenet.pth>)`) it also draws the 71 face points of the first `max_faces` people of a
-frame: the face stage is openpose_face.py (its head describes it; `faces()` returns its points and boxes).  Hands are still missing:
-`include_hand` must be false (anything else raises NotImplementedError), and so must `include_face` when no face network is given.
+frame: the face stage is openpose_face.py (its head describes it; `faces()` returns its points and boxes).  Given a hand network
+(`hand=<state dict or hand_pose_model.pth>`) it also draws the hands of the first `max_hands` wrist boxes of a frame (20 edges and 21
+circles each): the hand stage is openpose_hand.py (`hands()` returns its points and boxes).  With both networks the drawing is the
+reference's hand_and_face=True: per person the body, the left hand, the right hand, the face.  `include_hand=True` without a hand
+network raises NotImplementedError, and so does `include_face=True` without a face network.
 
 The detector's body part, as the reference calls it (detect_resolution = image_resolution = 512):
 
@@ -74,6 +77,7 @@ WEIGHTS_NAME = "body_pose_model.pth"
 MAX_PEAKS, MAX_PEOPLE, AREA_TAPS = 64, 64, 8
 OVERFLOW_PEAKS, OVERFLOW_PEOPLE = 1, 2
 OVERFLOW_FACES, OVERFLOW_FACE_RESIZE = 4, 8   # the face stage (openpose_face.py)
+OVERFLOW_HANDS, OVERFLOW_HAND_RESIZE = 16, 32   # the hand stage (openpose_hand.py)
 BOXSIZE, STRIDE = 368, 8
 STAGES = {"prep": 1, "conv": 18, "pool": 3, "copy": 1, "pointwise": 24, "conv7": 25, "maps": 1, "peaks": 1, "connect": 1, "assemble": 1, "draw": 1}
 
@@ -271,14 +275,15 @@ class OpenposeAnnotator:
     STAGES = STAGES
 
     def __init__(self, state_dict_or_path, device=None, dtype=None, detect_resolution: int = 512, image_resolution: int = 512,
-                 include_hand: bool = False, include_face=None, face=None, max_faces: int = 2):
+                 include_hand=None, include_face=None, face=None, max_faces: int = 2, hand=None, max_hands: int = 2):
         import torch
         dtype = torch.float16 if dtype is None else dtype
         if dtype not in (torch.float16, torch.bfloat16):
             raise TypeError(f"dtype must be torch.float16 or torch.bfloat16, got {dtype}")
-        if include_hand:
-            raise NotImplementedError("OpenposeAnnotator draws the body skeleton and, given a face network, the faces: the hand network of the "
-                                      "reference's hand_and_face=True is not part of it (include_hand must be False)")
+        include_hand = hand is not None if include_hand is None else bool(include_hand)   # with `hand` given, hands are drawn by default
+        if include_hand and hand is None:
+            raise NotImplementedError("include_hand=True, but no hand network was given: pass hand=<state dict, hand_pose_model.pth or the "
+                                      "directory that holds it> (nothing is ever downloaded)")
         include_face = face is not None if include_face is None else bool(include_face)   # with `face` given, faces are drawn by default
         if include_face and face is None:
             raise NotImplementedError("include_face=True, but no face network was given: pass face=<state dict, facenet.pth or the directory "
@@ -325,6 +330,11 @@ class OpenposeAnnotator:
             from .openpose_face import FACE_STAGES, FaceStage
             self._face = FaceStage(self, face, max_faces)   # (its key and shape checks come before the device is touched, like the body's)
             self.STAGES = {**STAGES, **FACE_STAGES}
+        self._hand = None
+        if include_hand:
+            from .openpose_hand import HAND_STAGES, HandStage
+            self._hand = HandStage(self, hand, max_hands)   # (key and shape checks before the device is touched)
+            self.STAGES = {**self.STAGES, **HAND_STAGES}
         self.timings = None  # a dict: receives (start, end) torch events per stage under the keys of STAGES -- tools/bench_openpose.py
 
     @staticmethod
@@ -348,7 +358,7 @@ class OpenposeAnnotator:
     @classmethod
     def from_pretrained(cls, path, **kwargs):
         """path: a local body_pose_model.pth or a directory that holds it (no network access, ever).  face=<a local facenet.pth or a
-        directory that holds it> adds the face stage."""
+        directory that holds it> adds the face stage, hand=<a local hand_pose_model.pth or its directory> the hand stage (hands())."""
         return cls(cls._load(path), **kwargs)
 
     # ---- device state ----------------------------------------------------------------------------------------------------------
@@ -559,8 +569,8 @@ class OpenposeAnnotator:
         give(cat)
         ws["planned"] = True
 
-    def _run(self, src, skeleton, control, rep, decode=True, face=None):
-        """face: run the face stage (None: when there is one and something is drawn)."""
+    def _run(self, src, skeleton, control, rep, decode=True, face=None, hand=None):
+        """face, hand: run that stage (None: when there is one and something is drawn)."""
         from . import kernels as K
         n, h, w, _ = src.shape
         ws = self.workspace(n, h, w)
@@ -580,13 +590,19 @@ class OpenposeAnnotator:
         if decode:
             K.pose_decode(ws["raw"], ws["smooth"], ws["paf"], ws["decode"], stage=self._stage)
         drawn = skeleton is not None or control is not None
-        fws = None
+        fws = hws = None
         if self._face is not None and decode and (drawn if face is None else face):
             fws = self._faces_from(src, ws["decode"]["keypoints"], ws["decode"]["people"], ws["decode"]["overflow"])
+        if self._hand is not None and decode and (drawn if hand is None else hand):   # (its overflow word carries the face stage's bits on)
+            over = fws["buf"]["overflow"] if fws is not None else ws["decode"]["overflow"]
+            hws = self._hand.run(src, ws["decode"]["keypoints"], ws["decode"]["people"], over, direct=self._direct())
         if drawn:
             ev = self._stage("draw")
             d = ws["decode"]
-            if fws is None:
+            if hws is not None:
+                K.pose_draw_hands(d["coords"], d["people"], ws["sin"], hws["buf"]["points"], None if fws is None else fws["buf"]["points"], hws["xmap"], hws["ymap"],
+                                  h, w, index=ws["index"], skeleton=skeleton, control=control, rep=rep)
+            elif fws is None:
                 K.pose_draw(d["coords"], d["people"], ws["sin"], h, w, index=ws["index"], skeleton=skeleton, control=control, rep=rep)
             else:
                 K.pose_draw_faces(d["coords"], d["people"], ws["sin"], fws["buf"]["points"], fws["xmap"], fws["ymap"], h, w, index=ws["index"],
@@ -633,8 +649,20 @@ class OpenposeAnnotator:
         if self._face is None:
             raise NotImplementedError("no face network was given (OpenposeAnnotator(..., face=<state dict or facenet.pth>))")
         src = self._frames(frames)
-        self._run(src, None, None, 1, face=True)
+        self._run(src, None, None, 1, face=True, hand=False)
         b = self._face.workspace(*src.shape[:3], src.device)["buf"]
+        return b["points"].clone(), b["boxes"].clone(), b["overflow"].clone()
+
+    def hands(self, frames):
+        """-> (points int32 [n, MAX_PEOPLE, 2, 21, 2] = (x, y) frame pixels of the hand keypoints of the person of that row of poses(), left
+        then right, -1 for a missing coordinate; boxes int32 [n, MAX_PEOPLE, 2, 4] = (x, y, side, slot) of util.handDetect, side 0 for no box,
+        slot -1 for a hand that was not taken; overflow int32 [n]: poses()'s bits and OVERFLOW_HANDS | OVERFLOW_HAND_RESIZE), on the device,
+        as new tensors."""
+        if self._hand is None:
+            raise NotImplementedError("no hand network was given (OpenposeAnnotator(..., hand=<state dict or hand_pose_model.pth>))")
+        src = self._frames(frames)
+        self._run(src, None, None, 1, face=False, hand=True)
+        b = self._hand.workspace(*src.shape[:3], src.device)["buf"]
         return b["points"].clone(), b["boxes"].clone(), b["overflow"].clone()
 
     def skeleton(self, frames, out=None):

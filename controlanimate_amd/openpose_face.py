@@ -1,8 +1,7 @@
 """The face half of the OpenPose detector's hand_and_face=True (modules/controlresiduals_pipeline.py:113 of the reference), driven by
 openpose.OpenposeAnnotator when it is given a face network: the 71 face points of every detected person (one per
 map of FaceNet, as the specification reads them: FACE_PEAK_MAPS = 71), drawn as white dots into the
-body's drawing.  Hands are still missing (their four-scale pyramid, smoothing and component labelling are a separate piece of work; the
-crop machinery here is meant to serve them).
+body's drawing.  The hand half is openpose_hand.py (its crops go through the table builders here, made for its four sides).
 
 The detector's face part, as the reference calls it:
 
@@ -173,9 +172,10 @@ def lanczos4_side_tables(sides, dst: int = FACE_SIZE):
     return (s.astype(np.int64) - 3).astype(np.int32), coef
 
 
-def area_side_tables(sides, dst: int = FACE_SIZE):
+def area_side_tables(sides, dst: int = FACE_SIZE, taps: int = TAPS):
     """openpose.area_tables(side, dst, dst / side) for every side >= dst of `sides` at once: (ofs int32 [len, dst], cnt int32 [len, dst],
-    w float32 [len, dst, 8]) with scale = side / dst, as cv2.resize computes it from the two sizes."""
+    w float32 [len, dst, taps]) with scale = side / dst, as cv2.resize computes it from the two sizes (taps: 8 here; the hand stage, whose
+    smallest input is 184 pixels, takes up to 16)."""
     sides = np.asarray(sides, np.int64)
     assert (sides >= dst).all()
     src = sides.astype(np.float64)[:, None]
@@ -190,14 +190,14 @@ def area_side_tables(sides, dst: int = FACE_SIZE):
     last = (f2 - s2 > 1e-3)
     full = s2 - s1
     cnt = first.astype(np.int64) + full + last
-    if cnt.max() > TAPS or cnt.min() < 1:
-        raise NotImplementedError(f"INTER_AREA to {dst}: {cnt.min()} .. {cnt.max()} taps (1 .. {TAPS} are taken)")
+    if cnt.max() > taps or cnt.min() < 1:
+        raise NotImplementedError(f"INTER_AREA to {dst}: {cnt.min()} .. {cnt.max()} taps (1 .. {taps} are taken)")
     wfirst = ((s1 - f1) / cell).astype(np.float32)
     wfull = (1.0 / cell).astype(np.float32)
     wlast = (np.minimum(np.minimum(f2 - s2, 1.0), cell) / cell).astype(np.float32)
-    j = np.arange(TAPS)[None, None, :] - first[..., None]   # index among the full taps; -1: the first partial tap
+    j = np.arange(taps)[None, None, :] - first[..., None]   # index among the full taps; -1: the first partial tap
     w = np.where(j < 0, wfirst[..., None], np.where(j < full[..., None], wfull[..., None], np.where((j == full[..., None]) & last[..., None], wlast[..., None], 0)))
-    w = np.where(np.arange(TAPS)[None, None, :] < cnt[..., None], w, 0).astype(np.float32)
+    w = np.where(np.arange(taps)[None, None, :] < cnt[..., None], w, 0).astype(np.float32)
     return (s1 - first).astype(np.int32), cnt.astype(np.int32), np.ascontiguousarray(w)
 
 

@@ -1264,6 +1264,66 @@ int ca_face_peaks(const float* heat, const int32_t* slots, int32_t* points, int3
 int ca_pose_draw_faces(const int32_t* coords, const int32_t* people, const float* sin_table, const int32_t* points, const int32_t* xmap, const int32_t* ymap,
                        uint32_t* index, uint8_t* map, void* control, int32_t images, int32_t h, int32_t w, int32_t rep, int32_t control_dtype, void* stream);
 
+/* ---- added to ABI v16 likewise: the hand stage of the OpenPose annotator around the hand network (FaceNet's layers with 22 output maps;
+ * controlanimate_amd/openpose_hand.py; csrc/ca_openpose_hand.hip; the specification is tests/hand_ref.py) ---- */
+#define CA_HAND_PARTS 21              /* heat maps that are decoded (the network writes 22, padded to CA_HAND_HEAT_COLS columns) */
+#define CA_HAND_HEAT_COLS 24
+#define CA_HAND_MAP 128               /* the four-scale average is 128 x 128 */
+#define CA_HAND_SCALES 4              /* network inputs of 184, 368, 552 and 736 pixels, maps of 23, 46, 69 and 92 */
+#define CA_HAND_SLOT_INTS 8           /* a slot: person (-1: empty), x, y, w, hand (0 left, 1 right), mode, 0, 0 */
+#define CA_HAND_MODE_NONE 0           /* empty slot, or a crop side whose resize is not restated: no points */
+#define CA_HAND_MODE_RESIZE 1
+#define CA_POSE_OVERFLOW_HANDS 16        /* more hand boxes than max_hands: the first max_hands are taken, people in order, left before right */
+#define CA_POSE_OVERFLOW_HAND_RESIZE 32  /* a hand was skipped: INTER_AREA at an exact integer ratio other than 2 (w = 184 k, k >= 3) */
+
+/* util.handDetect per person, from keypoints int32 [images, 64, 18, 2] (pixels, -1: missing) and people int32 [images], in double and in
+ * the published operation order: left from parts (5, 6, 7), right from (2, 3, 4) = shoulder, elbow, wrist; x = wrist + 0.33 (wrist -
+ * elbow), width = 1.5 max(|wrist - elbow|, 0.9 |elbow - shoulder|), the corner moved by width / 2 and clamped at 0, the width cut at the
+ * frame, kept from 20 on.  boxes int32 [images, 64, 2, 4] = (x, y, w, slot) (w = 0 and slot = -1 where there is no box; slot = -1 too where
+ * the box got no slot), slots int32 [images, max_hands, CA_HAND_SLOT_INTS] in person order, left before right, overflow[img] =
+ * (overflow_in ? overflow_in[img] : 0) | the two hand bits.  The crop of a box is always the full w x w square. */
+int ca_hand_boxes(const int32_t* keypoints, const int32_t* people, const int32_t* overflow_in, int32_t* boxes, int32_t* slots, int32_t* overflow, int32_t images,
+                  int32_t h, int32_t w, int32_t max_hands, void* stream);
+
+/* The input of the hand network at one side (184, 368, 552 or 736) for slots first .. first + crops - 1 of uint8 RGB frames [images, h,
+ * w, 3] -> out [crops, side, side, 8] of dtype (BGR, byte / 256 - 0.5, channels 3 .. 7 zero; zeros for an empty or skipped slot).  blur = 1
+ * first writes cv2.GaussianBlur(crop, (0, 0), 0.8) of those slots into blurred uint8 [images * max_hands, side_max, side_max, 3] (taps:
+ * the 7 double taps; rows then columns in double, BORDER_REFLECT_101 inside the crop, one rounding); blur = 0 reads what an earlier call
+ * wrote there.  The resize of the blurred w x w crop is cv2.resize's: INTER_LANCZOS4 for w <= side (lz_ofs int32 [min(side, side_max) - 19,
+ * side], lz_coef int16 [.., side, 8], row w - 20: OpenCV's 11-bit fixed point), (a + b + c + d + 2) >> 2 for w = 2 side, else INTER_AREA
+ * (ar_ofs, ar_cnt int32 [side_max - side, side], ar_w fp32 [.., side, CA_HAND_AREA_TAPS], row w - side - 1: fp32 weighted sums, rounded
+ * half to even).  side_max = min(h, w): no box is wider. */
+#define CA_HAND_MIN_BOX 20
+#define CA_HAND_AREA_TAPS 16
+int ca_hand_crop(const uint8_t* frames, const int32_t* slots, const double* taps, uint8_t* blurred, void* out, const int32_t* lz_ofs, const int16_t* lz_coef,
+                 const int32_t* ar_ofs, const int32_t* ar_cnt, const float* ar_w, int32_t images, int32_t h, int32_t w, int32_t max_hands, int32_t first, int32_t crops,
+                 int32_t side, int32_t side_max, int32_t blur, int32_t dtype, void* stream);
+
+/* The network's maps of the four scales, fp32 [slots, m, m, CA_HAND_HEAT_COLS] with m = 23, 46, 69, 92, -> raw and smooth fp32 [slots, 21,
+ * 128, 128]: raw = sum over the scales of A_s H_s A_s^T / 4 (A_s: the x8 INTER_LANCZOS4 resize and the INTER_AREA resize to 128 of one
+ * axis composed), smooth its gaussian_filter(sigma = 3) through G A_s.  mats fp32 [2][230][128]: the transposed A_s ([m][128]) of the
+ * four scales behind each other, then the transposed G A_s.  No x8 plane is written. */
+int ca_hand_maps(const float* heat184, const float* heat368, const float* heat552, const float* heat736, const float* mats, float* raw, float* smooth,
+                 int32_t slots, void* stream);
+
+/* Per (slot, part) of raw / smooth fp32 [images * max_hands, 21, 128, 128]: binary = smooth > 0.05; its 8-connected components
+ * (skimage.measure.label(connectivity = 2): numbered by their first pixel in raster order); the one with the largest sum of raw (a
+ * double sum in a fixed order: bit-identical from run to run; the first label on a tie); the first row-major maximum of raw zeroed
+ * outside it (pixel 0 for an empty binary plane).  peaks int32 [slots, 21, 2] = that (x, y) on the 128 grid, mass double [slots, 21] the
+ * winner's sum (0 for none); points int32 [images, 64, 2, 21, 2] (frame pixels; every entry without a slot is -1): int(x * w / 128.0) of the
+ * slot's box, -1 where that is 0, else plus the box origin.  A slot of CA_HAND_MODE_NONE gives no points. */
+int ca_hand_peaks(const float* raw, const float* smooth, const int32_t* slots, int32_t* points, int32_t* peaks, double* mass, int32_t images, int32_t max_hands,
+                  int32_t h, int32_t w, void* stream);
+
+/* ca_pose_draw_faces with hands: per person the 35 body primitives, then per hand (left, right) 20 edges cv2.line(thickness = 2) in their
+ * hsv colours and 21 filled radius-4 circles in (0, 0, 255) (draw_handpose; hand_points int32 [images, 64, 2, 21, 2] through xmap / ymap,
+ * an edge where all four coordinates come out positive, a circle where both do), then the 71 face discs (face_points NULL: none);
+ * primitive person * 188 + k.  A thick line is OpenCV's ThickLine: the corners p0 +- dp, p1 -+ dp at 16 fractional bits through
+ * FillConvexPoly, and a filled radius-1 circle at each end. */
+int ca_pose_draw_hands(const int32_t* coords, const int32_t* people, const float* sin_table, const int32_t* hand_points, const int32_t* face_points,
+                       const int32_t* xmap, const int32_t* ymap, uint32_t* index, uint8_t* map, void* control, int32_t images, int32_t h, int32_t w, int32_t rep,
+                       int32_t control_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,13 @@ every slot for max_faces = 1, 2 and 4 with the cost per face slot and the per-st
 channels_last chain on the same number of crops.
 
     python tools/bench_openpose.py --face > profiles/openpose_face_bench.json
+
+--hand times the hand stage (controlanimate_amd/openpose_hand.py) likewise: the window without and with the stage (the chain's own
+keypoints), the stage alone from planted keypoints that fill every slot for max_hands = 1, 2 and 4 with the cost per hand slot and the
+per-stage times, and the same handpose_model as a torch fp16 channels_last chain on the same number
+of slots at the four sides.
+
+    python tools/bench_openpose.py --hand > profiles/openpose_hand_bench.json
 """
 import argparse
 import json
@@ -83,6 +90,51 @@ def face_mode(a):
     print(json.dumps(result))
 
 
+def hand_mode(a):
+    import hand_ref
+    import pose_ref
+    from controlanimate_amd.openpose import OpenposeAnnotator
+    from controlanimate_amd.openpose_hand import SIDES
+    dev, dtype = "cuda:0", torch.float16 if a.dtype == "fp16" else torch.bfloat16
+    res = min(a.height, a.width)
+    body, hand = pose_ref.pose_state_dict(0), hand_ref.hand_state_dict(0)
+    frames = torch.from_numpy(pose_ref.frames_fixture(a.frames, a.height, a.width)).to(dev)
+    out = torch.empty((2 * a.frames, 3, a.height, a.width), dtype=torch.float16, device=dev)
+    result = {"frames": a.frames, "height": a.height, "width": a.width, "dtype": a.dtype, "weights": "seeded (no trained checkpoint)", "default_max_hands": 2}
+    plain = OpenposeAnnotator(body, device=dev, dtype=dtype, detect_resolution=res, image_resolution=res)
+    result["chain_ms_without_hands"] = _median_ms(lambda: plain.annotate_batch(frames, out=out, rep=2), a.iters)
+    # two people per frame with both arms: boxes of 82, 94, 82 and 94 pixels, taken in order until the slots are full
+    people_list = [{**hand_ref.arm((200, 300), (180, 260), (170, 200)), **hand_ref.arm((300, 310), (320, 250), (330, 200), left=False)},
+                   {**hand_ref.arm((500, 300), (480, 260), (470, 200)), **hand_ref.arm((600, 310), (620, 250), (630, 200), left=False)}]
+    kp = torch.from_numpy(np.stack([hand_ref.keypoints_of(people_list)] * a.frames)).to(dev)
+    people = torch.full((a.frames,), 2, dtype=torch.int32, device=dev)
+    for mh in (1, 2, 4):
+        ann = OpenposeAnnotator(body, device=dev, dtype=dtype, detect_resolution=res, image_resolution=res, hand=hand, max_hands=mh)
+        whole = _median_ms(lambda: ann.annotate_batch(frames, out=out, rep=2), a.iters)
+        _, boxes, _ = ann.hands(frames)
+        stage = _median_ms(lambda: ann._hand.run(frames, kp, people), a.iters)
+        filled = int((ann._hand.workspace(a.frames, a.height, a.width, frames.device)["buf"]["slots"][:, :, 0] >= 0).sum())
+        assert filled == a.frames * mh
+        entry = {"slots": a.frames * mh, "chain_ms_with_hands": whole, "slots_filled_by_the_chain": int((boxes[:, :, :, 3] >= 0).sum()),
+                 "hand_stage_ms_all_slots_filled": stage, "ms_per_hand_slot": round(stage / (a.frames * mh), 4)}
+        ann.timings = {}
+        ann._hand.run(frames, kp, people)
+        torch.cuda.synchronize()
+        entry["stages_ms"] = {k: round(sum(x.elapsed_time(y) for x, y in v), 3) for k, v in ann.timings.items()}
+        ann.timings = None
+        result[f"max_hands_{mh}"] = entry
+        del ann
+        torch.cuda.empty_cache()
+    # the same network in torch: fp16 (or bf16), channels_last, on the default number of slots at the same four sides
+    net = hand_ref.hand_net(hand).to(dev).to(dtype).to(memory_format=torch.channels_last)
+    xs = [torch.randn((a.frames * 2, 3, s, s), device=dev).to(dtype).contiguous(memory_format=torch.channels_last) for s in SIDES]
+    with torch.no_grad():
+        result["torch_channels_last_handnet_ms"] = {"slots": a.frames * 2, "ms": _median_ms(lambda: [net(x) for x in xs], a.iters)}
+    net_ms = sum(v for k, v in result["max_hands_2"]["stages_ms"].items() if k in ("hand_conv", "hand_pool", "hand_copy", "hand_pointwise", "hand_conv7"))
+    result["hip_handnet_ms"] = {"slots": a.frames * 2, "ms": round(net_ms, 3)}
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=16)
@@ -91,9 +143,12 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--dtype", choices=("fp16", "bf16"), default="fp16")
     ap.add_argument("--face", action="store_true", help="time the face stage (see the head of this file)")
+    ap.add_argument("--hand", action="store_true", help="time the hand stage (see the head of this file)")
     a = ap.parse_args()
     if a.face:
         return face_mode(a)
+    if a.hand:
+        return hand_mode(a)
     import pose_ref
     from controlanimate_amd.context import dispatch
     from controlanimate_amd.openpose import OpenposeAnnotator
