@@ -42,6 +42,8 @@ def close(out, ref, dtype, what, rel=None):
 # ------------------------------------------------------------------------------------ GEMM
 GEMM_CASES = [
     # m, n, k1, k2, bias, rowbias, residual, alpha, post, act, geglu, out_f32
+    # small grids: the three-stage k_gemm_dma ring ("128x64_r3"), k_gemm_reg where K is not whole 64-channel tiles ("reg_128x64": K = 40, 32),
+    # and one 128 x 320 ping-pong launch ("pp128x320": 4096 x 1280 x 1280).  tests/test_gemm_plans_gpu.py pins a case to every plan.
     (256, 128, 64, 0, False, False, False, 1.0, 1.0, 0, False, False),
     (200, 320, 320, 0, True, False, True, 1.0, 1.0, 0, False, False),
     (130, 24, 40, 0, True, False, False, 1.0, 1.0, 0, False, False),
@@ -54,13 +56,15 @@ GEMM_CASES = [
     (4096, 1280, 1280, 0, True, False, True, 1.0, 1.0, 0, False, False),
     (1000, 8, 64, 0, True, False, False, 1.0, 1.0, 0, False, False),
     (77, 4, 32, 0, False, False, False, 1.0, 1.0, 0, False, True),
-    # grids of >= 512 blocks take the single-LDS-buffer / 4-blocks-per-CU pipeline
+    # M >= 16384: the weight-resident kernel at K = 320 ("wres160", three cases) and the persistent streaming kernel ("ps128x320", two);
+    # the single-LDS-buffer k_gemm_dma tiles these shapes once took are covered by tests/test_gemm_plans_gpu.py
     (16384, 320, 320, 0, True, False, True, 1.0, 1.0, 0, False, False),
     (16384, 2560, 320, 0, True, False, False, 1.0, 1.0, 0, True, False),
     (16384, 960, 320, 0, False, False, False, 1.0, 1.0, 0, False, False),
     (16384, 1280, 1280, 0, True, True, True, 1.0, 1.0, 0, False, False),
     (65536, 320, 640, 640, True, False, False, 1.0, 1.0, 0, False, False),
-    # <= 192 tiles of 128x128 with >= 16 K tiles: the split-K slab schedule of the 8x8-latent level (ABI v6 workspace)
+    # the 8x8-latent level: K = 5120 splits into four K ranges on 128 x 320 ping-pong tiles ("pp128x320_splitk4", ABI v6 workspace); the
+    # other two have K loops too short to split (20 and 32 K tiles, the rule wants 48) and run "128x64_r3"
     (2048, 1280, 1280, 0, True, False, True, 1.0, 1.0, 0, False, False),
     (2040, 1280, 5120, 0, True, True, True, 0.5, 0.7, 1, False, False),
     (300, 1280, 1024, 1024, True, False, False, 1.0, 1.0, 0, False, False),
