@@ -44,6 +44,7 @@ try:
 except Exception:  # pragma: no cover
     Image = None
 
+from .annotator_base import AnnotatorBase  # noqa: E402
 from .hed import HedAnnotator  # noqa: E402,F401  (the learned HED detector on the GPU; torch is imported when it is used)
 from .lineart import LineartAnnotator  # noqa: E402,F401  (the learned lineart detector on the GPU, likewise)
 from .lineart_anime import LineartAnimeAnnotator  # noqa: E402,F401  (the learned anime line detector on the GPU, likewise)
@@ -119,7 +120,7 @@ def canny(image, low: float = 100, high: float = 200):
     return Image.fromarray(rgb) if Image is not None and not isinstance(image, np.ndarray) else rgb
 
 
-class CannyAnnotator:
+class CannyAnnotator(AnnotatorBase):
     """`canny` on the GPU for a whole window at once: `CannyAnnotator(device)(image)` has the contract of `canny(image)` (PIL RGB in,
     PIL RGB with three equal channels out; an array in, an array out), so it is a drop-in for `annotators={"canny": ...}`, and
     `MultiControlNetResidualsPipeline.prep_control_images` calls `annotate_batch` once per list of frames instead of the callable
@@ -128,21 +129,15 @@ class CannyAnnotator:
     frames of different sizes ValueError; without the library or a GPU a call raises CAHipUnavailable (no CPU fallback: `canny` is
     the host function)."""
 
+    _no_gpu_hint = "(no CPU fallback; annotators.canny is the host function)"
+    _grey_to_rgb = False   # C = 1 or 3 as given, as `canny` takes it: the kernel picks the channel with the largest gradient
+
     def __init__(self, device=None, low: float = 100, high: float = 200):
         self.device = device
         self.low, self.high = int(np.floor(low)), int(np.floor(high))
         if self.low > self.high:
             raise ValueError(f"low={low} > high={high}")
-        self._ws = {}
-        self.timings = None  # a dict: receives (start, end) torch events per launch (classify, label, merge, flatten, emit) -- tools/bench_canny.py
-
-    def _device(self):
-        import torch
-        from . import _capi
-        _capi.lib()  # CAHipUnavailable when the extension is not built
-        if not torch.cuda.is_available():
-            raise _capi.CAHipUnavailable("CannyAnnotator needs a GPU (no CPU fallback; annotators.canny is the host function)")
-        return torch.device(self.device if self.device is not None else "cuda")
+        self._ws = {}   # (`timings` receives events under classify, label, merge, flatten, emit -- tools/bench_canny.py)
 
     def workspace(self, n: int, h: int, w: int):
         """The scratch tensor of a call with n frames of h x w pixels (cached per (n, h, w); contents are never assumed)."""
@@ -153,99 +148,19 @@ class CannyAnnotator:
             self._ws[key] = torch.empty(K.canny_workspace_bytes(n, h, w), dtype=torch.uint8, device=self._device())
         return self._ws[key]
 
-    def _stage(self, name):
-        import torch
-        if self.timings is None:
-            return None
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        self.timings.setdefault(name, []).append(ev)
-        ev[0].record()
-        return ev
-
-    def _frames(self, frames):
-        """-> uint8 device tensor [n, H, W, C], C = 1 or 3.  The type and size checks come before the device is touched.  A PIL
-        image is taken as np.asarray gives it, as `canny` does, so its mode must be L or RGB: convert RGBA / palette frames first."""
-        import torch
-        if isinstance(frames, torch.Tensor):
-            if frames.dtype != torch.uint8:
-                raise TypeError(f"frames must be uint8, got {frames.dtype}")
-            if frames.dim() == 3:
-                frames = frames[..., None]
-            if frames.dim() != 4 or frames.shape[3] not in (1, 3):
-                raise ValueError(f"frames tensor must be [n, H, W] or [n, H, W, C] with C = 1 or 3, got {tuple(frames.shape)}")
-            return frames.to(self._device()).contiguous()
-        host = []
-        for fr in frames:
-            a = np.asarray(fr)
-            if a.dtype != np.uint8:
-                raise TypeError(f"frames must be uint8, got {a.dtype}")
-            if a.ndim == 2:
-                a = a[:, :, None]
-            if a.ndim != 3 or a.shape[2] not in (1, 3):
-                raise ValueError(f"a frame must be [H, W] or [H, W, C] with C = 1 or 3 (PIL mode L or RGB: convert RGBA or palette "
-                                 f"frames with .convert('RGB') first), got {a.shape}" + (f" from PIL mode {fr.mode}" if hasattr(fr, "mode") else ""))
-            host.append(a)
-        if not host:
-            raise ValueError("no frames")
-        if any(a.shape != host[0].shape for a in host):
-            raise ValueError("all frames of a call must share one size")
-        dev = self._device()
-        return torch.from_numpy(np.stack(host)).to(dev)
-
     def _run(self, frames, edges, control, rep):
         from . import kernels as K
         n, h, w, _ = frames.shape
         ws = self.workspace(n, h, w)
-        ev = self._stage("classify")
-        K.canny_classify(frames, self.low, self.high, ws)
-        if ev:
-            ev[1].record()
+        self._timed("classify", K.canny_classify, frames, self.low, self.high, ws)
         if self.timings is None:
             K.canny_link(n, h, w, ws)
         else:  # the same three launches, one at a time, with events around each
             for stage in K.CANNY_LINK_STAGES:
-                ev = self._stage(stage)
-                K.canny_link_stage(n, h, w, ws, stage)
-                ev[1].record()
-        ev = self._stage("emit")
-        K.canny_emit(n, h, w, ws, edges=edges, control=control, rep=rep)
-        if ev:
-            ev[1].record()
+                self._timed(stage, K.canny_link_stage, n, h, w, ws, stage)
+        self._timed("emit", K.canny_emit, n, h, w, ws, edges=edges, control=control, rep=rep)
 
     def edges(self, frames, out=None):
         """frames: a list of PIL images / uint8 arrays of one size, or a uint8 tensor [n, H, W, C] (no host copy when it is on the
         device) -> uint8 device tensor [n, H, W] with 0 / 255, written into `out` when given."""
-        import torch
-        src = self._frames(frames)
-        n, h, w, _ = src.shape
-        if out is None:
-            out = torch.empty((n, h, w), dtype=torch.uint8, device=src.device)
-        elif out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w) or out.device != src.device or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous uint8 tensor {(n, h, w)} on {src.device}")
-        if n:
-            self._run(src, out, None, 1)
-        return out
-
-    def annotate_batch(self, frames, out=None, rep: int = 1, dtype=None):
-        """-> the control tensor [rep * n, 3, H, W] on the device, 0.0 / 1.0 with three equal channels; rep = 2 writes the n frames
-        twice (torch.cat([ctrl] * 2) of classifier-free guidance).  Written into `out` (and `out` returned) when given."""
-        import torch
-        if rep not in (1, 2):
-            raise ValueError(f"rep={rep} (1 or 2)")
-        want = out.dtype if out is not None and dtype is None else (dtype if dtype is not None else torch.float32)
-        if want not in (torch.float32, torch.float16):
-            raise TypeError(f"the control tensor is float32 or float16, got {want}")
-        src = self._frames(frames)
-        n, h, w, _ = src.shape
-        if out is None:
-            out = torch.empty((rep * n, 3, h, w), dtype=want, device=src.device)
-        elif tuple(out.shape) != (rep * n, 3, h, w) or out.device != src.device or not out.is_contiguous() or out.dtype != want:
-            raise ValueError(f"out must be a contiguous {want} tensor {(rep * n, 3, h, w)} on {src.device}")
-        if n:
-            self._run(src, None, out, rep)
-        return out
-
-    def __call__(self, image):
-        e = self.edges([image])[0].cpu().numpy()
-        rgb = np.repeat(e[:, :, None], 3, axis=2)
-        return Image.fromarray(rgb) if Image is not None and not isinstance(image, np.ndarray) else rgb
+        return self._uint8_out(frames, out)

@@ -27,6 +27,7 @@ from typing import List, Sequence, Tuple
 
 import numpy as np
 
+from .annotator_base import HipStages
 from .vid2vid import _like, _to_np
 
 # ---- table / matrix stages (host, shared by the device path and the tests) ----------------------------------------------------
@@ -184,7 +185,7 @@ def finish_u8(o: np.ndarray, normalize: bool) -> np.ndarray:
 # ---- device path ------------------------------------------------------------------------------------------------------------
 
 
-class ColorMatcher:
+class ColorMatcher(HipStages):
     """`match_colors` on the GPU: `ColorMatcher(device)(frames, ref_frame)` has the contract of `vid2vid.match_colors` for uint8
     input -- PIL images or HxWx3 uint8 arrays in, the same kind out, one result per frame -- and is a drop-in for the hooks
     `run_windows(..., match_colors=...)` and `run_video_sharded(..., match_colors_fn=...)`.  All frames of a call share one size
@@ -195,11 +196,12 @@ class ColorMatcher:
     i.e. two device-to-host reads of a few KB (which synchronise the stream) and two uploads of tables.  Non-uint8 input raises
     TypeError; without the library or a GPU the call raises CAHipUnavailable (there is no CPU fallback)."""
 
+    _no_gpu_hint = "(no CPU fallback; vid2vid.match_colors is the host function)"
+
     def __init__(self, device=None, normalize: bool = True):
         self.device = device
         self.normalize = bool(normalize)
-        self._ws = {}
-        self.timings = None  # a dict: receives (start, end) torch events per stage -- tools/bench_color_match.py
+        self._ws = {}   # (`timings` receives events per stage -- tools/bench_color_match.py)
 
     def workspace(self, images: int, pixels: int):
         """The scratch tensor of a call with `images` frames of `pixels` pixels (cached; contents are never assumed)."""
@@ -209,23 +211,6 @@ class ColorMatcher:
         if key not in self._ws:
             self._ws = {key: torch.empty(K.color_match_workspace_bytes(images, pixels), dtype=torch.uint8, device=self._device())}
         return self._ws[key]
-
-    def _device(self):
-        import torch
-        from . import _capi
-        _capi.lib()  # CAHipUnavailable when the extension is not built
-        if not torch.cuda.is_available():
-            raise _capi.CAHipUnavailable("ColorMatcher needs a GPU (no CPU fallback; vid2vid.match_colors is the host function)")
-        return torch.device(self.device if self.device is not None else "cuda")
-
-    def _stage(self, name):
-        import torch
-        if self.timings is None:
-            return None
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        self.timings.setdefault(name, []).append(ev)
-        ev[0].record()
-        return ev
 
     def __call__(self, frames, ref_frame) -> List:
         import torch

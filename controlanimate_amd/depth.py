@@ -50,6 +50,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from .annotator_base import AnnotatorBase, HipStages
 from .clip import _PackedModel
 from .layers import HipConv1x1, HipConv3x3, HipLayerNorm, HipLinear, WeightArena, _f32, pack_concat_bias, pack_concat_rows
 
@@ -412,13 +413,7 @@ class DPTForDepthEstimation(_PackedModel):
         self.pos = arena.add(tuple(emb.position_embeddings.shape[1:]), torch.float32, lambda: _f32(emb.position_embeddings)[0])
         self.cls = arena.add((1, emb.cls_token.shape[2]), dtype, lambda: _f32(emb.cls_token)[0])
 
-    def _stage(self, name):
-        if self.timings is None:
-            return None
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        self.timings.setdefault(name, []).append(ev)
-        ev[0].record()
-        return ev
+    _stage = HipStages._stage   # (events per stage into `timings`, as the annotators record them)
 
     # ---- stages -----------------------------------------------------------------------------------------------------------------------
     def _vit(self, frames_u8: torch.Tensor):
@@ -506,7 +501,7 @@ class DPTForDepthEstimation(_PackedModel):
 
 
 # ---- the annotator --------------------------------------------------------------------------------------------------------------------
-class DepthAnnotator:
+class DepthAnnotator(AnnotatorBase):
     """`DepthAnnotator(model, size, resample, normalize)` for a packed DPTForDepthEstimation with seeded or loaded weights;
     `DepthAnnotator.from_pretrained(local_dir)` for a local Intel/dpt-large style directory.  The surface of the sibling annotators:
     `annotate_batch(frames, out=, rep=, dtype=)` writes the ControlNets' control tensor [rep * n, 3, H, W] in [0, 1]; `depth(frames)` is the
@@ -527,8 +522,7 @@ class DepthAnnotator:
         if normalize not in ("max", "minmax"):
             raise ValueError(f"normalize={normalize!r} ('max' or 'minmax')")
         self.model, self.size, self.normalize, self.device = model, size, normalize, device
-        self._tables = {}
-        self.timings = None  # a dict: receives (start, end) torch events per stage under the keys of STAGES -- tools/bench_depth.py
+        self._tables = {}   # (`timings` receives events under the keys of STAGES -- tools/bench_depth.py)
 
     @classmethod
     def from_pretrained(cls, local_dir, device=None, dtype=torch.float16, normalize: str = "max"):
@@ -554,24 +548,10 @@ class DepthAnnotator:
         model.to(dtype)
         return cls(model, image_size, resample, normalize, device=device)
 
-    # ---- device state ----------------------------------------------------------------------------------------------------------
-    def _device(self):
-        from . import _capi
-        _capi.lib()  # CAHipUnavailable when the extension is not built
-        if not torch.cuda.is_available():
-            raise _capi.CAHipUnavailable("DepthAnnotator needs a GPU (there is no CPU fallback)")
-        return torch.device(self.device if self.device is not None else "cuda")
-
-    def _stage(self, name):
-        if self.timings is None:
-            return None
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        self.timings.setdefault(name, []).append(ev)
-        ev[0].record()
-        return ev
-
+    # ---- input checks ----------------------------------------------------------------------------------------------------------
     def _frames(self, frames) -> torch.Tensor:
-        """-> uint8 device tensor [n, H, W, 3].  The type and size checks come before the device is touched."""
+        """-> uint8 device tensor [n, H, W, 3].  The type and size checks come before the device is touched.  (Its own intake: three
+        channels only, as the pipeline's image processor takes them, with its own messages.)"""
         if isinstance(frames, torch.Tensor):
             if frames.dtype != torch.uint8:
                 raise TypeError(f"frames must be uint8, got {frames.dtype}")
@@ -609,10 +589,7 @@ class DepthAnnotator:
         n, h, w, _ = src.shape
         s = self.size
         self.model.timings = self.timings
-        ev = self._stage("resize")
-        small = K.resize_pil_u8(src, s, s, *self.tables(h, w, src.device))
-        if ev:
-            ev[1].record()
+        small = self._timed("resize", K.resize_pil_u8, src, s, s, *self.tables(h, w, src.device))
         depth = torch.empty((n, s, s), dtype=torch.float32, device=src.device)
         for i0 in range(0, n, self.chunk_frames):
             self.model.predicted_depth(small[i0:i0 + self.chunk_frames], out=depth[i0:i0 + self.chunk_frames])
@@ -634,39 +611,4 @@ class DepthAnnotator:
 
     def depth(self, frames, out=None) -> torch.Tensor:
         """-> the uint8 depth map [n, H, W] on the device, written into `out` when given."""
-        src = self._frames(frames)
-        n, h, w, _ = src.shape
-        if out is None:
-            out = torch.empty((n, h, w), dtype=torch.uint8, device=src.device)
-        elif out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w) or out.device != src.device or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous uint8 tensor {(n, h, w)} on {src.device}")
-        if n:
-            self._run(src, out, None, 1)
-        return out
-
-    def annotate_batch(self, frames, out=None, rep: int = 1, dtype=None) -> torch.Tensor:
-        """-> the control tensor [rep * n, 3, H, W] on the device, map / 255 with three equal channels; rep = 2 writes the n frames twice
-        (torch.cat([ctrl] * 2) of classifier-free guidance).  Written into `out` (and `out` returned) when given."""
-        if rep not in (1, 2):
-            raise ValueError(f"rep={rep} (1 or 2)")
-        want = out.dtype if out is not None and dtype is None else (dtype if dtype is not None else torch.float32)
-        if want not in (torch.float32, torch.float16):
-            raise TypeError(f"the control tensor is float32 or float16, got {want}")
-        src = self._frames(frames)
-        n, h, w, _ = src.shape
-        if out is None:
-            out = torch.empty((rep * n, 3, h, w), dtype=want, device=src.device)
-        elif tuple(out.shape) != (rep * n, 3, h, w) or out.device != src.device or not out.is_contiguous() or out.dtype != want:
-            raise ValueError(f"out must be a contiguous {want} tensor {(rep * n, 3, h, w)} on {src.device}")
-        if n:
-            self._run(src, None, out, rep)
-        return out
-
-    def __call__(self, image):
-        try:
-            from PIL import Image
-        except Exception:  # pragma: no cover
-            Image = None
-        e = self.depth([image])[0].cpu().numpy()
-        rgb = np.repeat(e[:, :, None], 3, axis=2)
-        return Image.fromarray(rgb) if Image is not None and not isinstance(image, np.ndarray) else rgb
+        return self._uint8_out(frames, out)

@@ -23,12 +23,7 @@ from __future__ import annotations
 
 import os
 
-import numpy as np
-
-try:
-    from PIL import Image
-except Exception:  # pragma: no cover
-    Image = None
+from .annotator_base import AnnotatorBase, check_state_dict as _check_state_dict
 
 HED_BLOCKS = ((3, 64, 2), (64, 128, 2), (128, 256, 3), (256, 512, 3), (512, 512, 3))  # (in, out, layers) of block1 .. block5
 WEIGHTS_NAME = "ControlNetHED.pth"
@@ -49,28 +44,21 @@ def hed_key_shapes() -> dict:
 
 def check_state_dict(sd) -> None:
     """KeyError naming a missing tensor, ValueError naming one that is unexpected or has the wrong shape."""
-    want = hed_key_shapes()
-    for k in want:
-        if k not in sd:
-            raise KeyError(f"HED state dict: '{k}' is missing ({len(want)} tensors expected: norm, block1..5.convs.*.weight|bias, block1..5.projection.weight|bias)")
-    for k in sd:
-        if k not in want:
-            raise ValueError(f"HED state dict: unexpected tensor '{k}'")
-    for k, shape in want.items():
-        if tuple(sd[k].shape) != shape:
-            raise ValueError(f"HED state dict: '{k}' has shape {tuple(sd[k].shape)}, expected {shape}")
+    _check_state_dict(sd, hed_key_shapes(), "HED", "norm, block1..5.convs.*.weight|bias, block1..5.projection.weight|bias")
 
 
-class HedAnnotator:
+class HedAnnotator(AnnotatorBase):
     """`HedAnnotator(weights)(image)` has the contract of `annotators.canny(image)` (PIL RGB in, PIL RGB with three equal channels out;
     an array in, an array out), so it plugs into `MultiControlNetResidualsPipeline(annotators={"hed": HedAnnotator.from_pretrained(path)})`,
     whose `prep_control_images` then calls `annotate_batch` once per list of frames.  Nothing makes it a default: the weights are the
     user's file.  Non-uint8 input raises TypeError, frames of different sizes ValueError, sizes out of scope NotImplementedError -- all
     before the device is touched; without the library or a GPU a call raises CAHipUnavailable (there is no CPU fallback)."""
 
+    WEIGHTS_NAME = WEIGHTS_NAME
     # the largest activation of a chunk of frames (block 1's output, 64 channels at full size) stays below what ca_conv3x3's kernels
     # address with 32-bit byte offsets (conv_prepare: operands below 0x7FFFFF00 bytes keep every plan available)
-    max_activation_bytes = 0x7FFFFF00 - 1
+    _bytes_per_pixel = 64 * 2
+    _addressed_by = "the convolutions"
 
     def __init__(self, state_dict_or_path, device=None, dtype=None, detect_resolution: int = 512, image_resolution: int = 512):
         import torch
@@ -92,50 +80,9 @@ class HedAnnotator:
                 convs.append((w.contiguous().to(dtype), sd[f"block{b}.convs.{i}.bias"].detach().float().contiguous()))
             self._host["blocks"].append((convs, sd[f"block{b}.projection.weight"].detach().float().reshape(cout).contiguous(),
                                          sd[f"block{b}.projection.bias"].detach().float().reshape(1).contiguous()))
-        self._dev = None
-        self._ws = {}
-        self.timings = None  # a dict: receives (start, end) torch events per launch under "prep", "conv", "pool_side", "fuse" -- tools/bench_hed.py
-
-    @staticmethod
-    def _load(path):
-        import torch
-        path = os.fspath(path)
-        if os.path.isdir(path):
-            path = os.path.join(path, WEIGHTS_NAME)
-        if not os.path.isfile(path):
-            raise FileNotFoundError(f"{path}: no such file (a local {WEIGHTS_NAME}, or a directory that holds it; nothing is ever downloaded)")
-        sd = torch.load(path, map_location="cpu", weights_only=True)
-        if not isinstance(sd, dict):
-            raise ValueError(f"{path}: not a state dict")
-        return sd
-
-    @classmethod
-    def from_pretrained(cls, path, **kwargs):
-        """path: a local ControlNetHED.pth or a directory that holds it (no network access, ever)."""
-        return cls(cls._load(path), **kwargs)
+        self._ws = {}   # (`timings` receives events under "prep", "conv", "pool_side", "fuse" -- tools/bench_hed.py)
 
     # ---- device state ----------------------------------------------------------------------------------------------------------
-    def _device(self):
-        import torch
-        from . import _capi
-        _capi.lib()  # CAHipUnavailable when the extension is not built
-        if not torch.cuda.is_available():
-            raise _capi.CAHipUnavailable("HedAnnotator needs a GPU (there is no CPU fallback)")
-        return torch.device(self.device if self.device is not None else "cuda")
-
-    def _weights(self, dev):
-        if self._dev is None or self._dev["norm"].device != dev:
-            self._dev = {"norm": self._host["norm"].to(dev),
-                         "blocks": [([(w.to(dev), b.to(dev)) for w, b in convs], pw.to(dev), pb.to(dev)) for convs, pw, pb in self._host["blocks"]]}
-        return self._dev
-
-    def chunk_frames(self, h: int, w: int) -> int:
-        """Frames per pass through the network: as many as keep block 1's output within max_activation_bytes."""
-        per_frame = h * w * 64 * 2
-        if per_frame > self.max_activation_bytes:
-            raise ValueError(f"a {h} x {w} frame alone exceeds what the convolutions address ({per_frame} > {self.max_activation_bytes} bytes)")
-        return self.max_activation_bytes // per_frame
-
     def workspace(self, n: int, h: int, w: int):
         """(two ping-pong activation buffers for a chunk of frames, the five float32 side maps [n, h >> k, w >> k]) of a call with n frames
         of h x w pixels, cached per (n, h, w); contents are never assumed."""
@@ -148,15 +95,6 @@ class HedAnnotator:
                              [torch.empty((n, h >> k, w >> k), dtype=torch.float32, device=dev) for k in range(5)])
         return self._ws[key]
 
-    def _stage(self, name):
-        import torch
-        if self.timings is None:
-            return None
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        self.timings.setdefault(name, []).append(ev)
-        ev[0].record()
-        return ev
-
     # ---- input checks ----------------------------------------------------------------------------------------------------------
     def _check_size(self, h: int, w: int) -> None:
         if not (min(h, w) == self.detect_resolution == self.image_resolution and h % 64 == 0 and w % 64 == 0):
@@ -164,44 +102,6 @@ class HedAnnotator:
                 f"HedAnnotator takes frames for which both resize_image calls of the detector are the identity: min(H, W) == detect_resolution == "
                 f"image_resolution and H % 64 == W % 64 == 0; got {h} x {w} with detect_resolution={self.detect_resolution}, "
                 f"image_resolution={self.image_resolution} (the INTER_AREA / INTER_LANCZOS4 resamplings are not rebuilt)")
-
-    def _frames(self, frames):
-        """-> uint8 device tensor [n, H, W, 3].  The type, size and scope checks come before the device is touched.  A PIL image is taken
-        as np.asarray gives it, so its mode must be L or RGB (a grey frame is repeated to three channels, as the detector's HWC3 does)."""
-        import torch
-        if isinstance(frames, torch.Tensor):
-            if frames.dtype != torch.uint8:
-                raise TypeError(f"frames must be uint8, got {frames.dtype}")
-            if frames.dim() == 3:
-                frames = frames[..., None]
-            if frames.dim() != 4 or frames.shape[3] not in (1, 3):
-                raise ValueError(f"frames tensor must be [n, H, W] or [n, H, W, C] with C = 1 or 3, got {tuple(frames.shape)}")
-            self._check_size(frames.shape[1], frames.shape[2])
-            dev = self._device()
-            if frames.shape[3] == 1:
-                frames = frames.expand(-1, -1, -1, 3)
-            return frames.to(dev).contiguous()
-        host = []
-        for fr in frames:
-            a = np.asarray(fr)
-            if a.dtype != np.uint8:
-                raise TypeError(f"frames must be uint8, got {a.dtype}")
-            if a.ndim == 2:
-                a = a[:, :, None]
-            if a.ndim != 3 or a.shape[2] not in (1, 3):
-                raise ValueError(f"a frame must be [H, W] or [H, W, C] with C = 1 or 3 (PIL mode L or RGB: convert RGBA or palette "
-                                 f"frames with .convert('RGB') first), got {a.shape}" + (f" from PIL mode {fr.mode}" if hasattr(fr, "mode") else ""))
-            host.append(a)
-        if not host:
-            raise ValueError("no frames")
-        if any(a.shape != host[0].shape for a in host):
-            raise ValueError("all frames of a call must share one size")
-        self._check_size(host[0].shape[0], host[0].shape[1])
-        dev = self._device()
-        stack = np.stack(host)
-        if stack.shape[3] == 1:
-            stack = np.repeat(stack, 3, axis=3)
-        return torch.from_numpy(stack).to(dev)
 
     # ---- the chain -------------------------------------------------------------------------------------------------------------
     def _network(self, src, bufs, sides, i0: int) -> None:
@@ -214,24 +114,15 @@ class HedAnnotator:
         def view(buf, hh, ww, c):
             return buf[: n * hh * ww * c].view(n, hh, ww, c)
 
-        ev = self._stage("prep")
-        x = K.hed_prep(src, wts["norm"], view(cur, h, w, _CIN_PAD))
-        if ev:
-            ev[1].record()
+        x = self._timed("prep", K.hed_prep, src, wts["norm"], view(cur, h, w, _CIN_PAD))
         hh, ww = h, w
         for k, (convs, pw, pb) in enumerate(wts["blocks"]):
             for wt, bias in convs:
                 cur, other = other, cur
-                ev = self._stage("conv")
-                x = K.conv3x3(x, wt, bias=bias, act=K.ACT_RELU, out=view(cur, hh, ww, wt.shape[0]))
-                if ev:
-                    ev[1].record()
+                x = self._timed("conv", K.conv3x3, x, wt, bias=bias, act=K.ACT_RELU, out=view(cur, hh, ww, wt.shape[0]))
             last = k == len(wts["blocks"]) - 1
             pooled = None if last else view(other, hh // 2, ww // 2, x.shape[3])
-            ev = self._stage("pool_side")
-            K.hed_pool_side(x, pw, pb, sides[k][i0:i0 + n], pooled)
-            if ev:
-                ev[1].record()
+            self._timed("pool_side", K.hed_pool_side, x, pw, pb, sides[k][i0:i0 + n], pooled)
             if not last:
                 cur, other = other, cur
                 x, hh, ww = pooled, hh // 2, ww // 2
@@ -244,10 +135,7 @@ class HedAnnotator:
         for i0 in range(0, n, step):
             self._network(src[i0:i0 + step], bufs, sides, i0)
         if edges is not None or control is not None:
-            ev = self._stage("fuse")
-            K.hed_fuse(sides, edges=edges, control=control, rep=rep)
-            if ev:
-                ev[1].record()
+            self._timed("fuse", K.hed_fuse, sides, edges=edges, control=control, rep=rep)
         return sides
 
     def side_maps(self, frames):
@@ -258,37 +146,4 @@ class HedAnnotator:
     def edges(self, frames, out=None):
         """frames: a list of PIL images / uint8 arrays of one size, or a uint8 tensor [n, H, W, C] (no host copy when it is on the
         device) -> uint8 device tensor [n, H, W] (the detector's map, 0 .. 255), written into `out` when given."""
-        import torch
-        src = self._frames(frames)
-        n, h, w, _ = src.shape
-        if out is None:
-            out = torch.empty((n, h, w), dtype=torch.uint8, device=src.device)
-        elif out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w) or out.device != src.device or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous uint8 tensor {(n, h, w)} on {src.device}")
-        if n:
-            self._run(src, out, None, 1)
-        return out
-
-    def annotate_batch(self, frames, out=None, rep: int = 1, dtype=None):
-        """-> the control tensor [rep * n, 3, H, W] on the device, level / 255 with three equal channels; rep = 2 writes the n frames
-        twice (torch.cat([ctrl] * 2) of classifier-free guidance).  Written into `out` (and `out` returned) when given."""
-        import torch
-        if rep not in (1, 2):
-            raise ValueError(f"rep={rep} (1 or 2)")
-        want = out.dtype if out is not None and dtype is None else (dtype if dtype is not None else torch.float32)
-        if want not in (torch.float32, torch.float16):
-            raise TypeError(f"the control tensor is float32 or float16, got {want}")
-        src = self._frames(frames)
-        n, h, w, _ = src.shape
-        if out is None:
-            out = torch.empty((rep * n, 3, h, w), dtype=want, device=src.device)
-        elif tuple(out.shape) != (rep * n, 3, h, w) or out.device != src.device or not out.is_contiguous() or out.dtype != want:
-            raise ValueError(f"out must be a contiguous {want} tensor {(rep * n, 3, h, w)} on {src.device}")
-        if n:
-            self._run(src, None, out, rep)
-        return out
-
-    def __call__(self, image):
-        e = self.edges([image])[0].cpu().numpy()
-        rgb = np.repeat(e[:, :, None], 3, axis=2)
-        return Image.fromarray(rgb) if Image is not None and not isinstance(image, np.ndarray) else rgb
+        return self._uint8_out(frames, out)

@@ -37,14 +37,9 @@ from __future__ import annotations
 
 import os
 
-import numpy as np
+from .annotator_base import AnnotatorBase, check_state_dict as _check_state_dict, load_state_dict
 
-try:
-    from PIL import Image
-except Exception:  # pragma: no cover
-    Image = None
-
-WEIGHTS_NAME, WEIGHTS_NAME_COARSE = "sk_model.pth", "sk_model2.pth"
+WEIGHTS_NAME,WEIGHTS_NAME_COARSE = "sk_model.pth", "sk_model2.pth"
 N_RES_BLOCKS = 3
 EPS = 1e-5
 # stages per pass through the network, which is what `timings` counts: 24 stages, 37 launches (an InstanceNorm is two launches, a
@@ -70,17 +65,8 @@ def lineart_key_shapes() -> dict:
 
 def check_state_dict(sd) -> None:
     """KeyError naming a missing tensor, ValueError naming one that is unexpected or has the wrong shape."""
-    want = lineart_key_shapes()
-    for k in want:
-        if k not in sd:
-            raise KeyError(f"lineart state dict: '{k}' is missing ({len(want)} tensors expected: model0.1, model1.{{0,3}}, "
-                           f"model2.{{0,1,2}}.conv_block.{{1,5}}, model3.{{0,3}}, model4.1, each with .weight and .bias)")
-    for k in sd:
-        if k not in want:
-            raise ValueError(f"lineart state dict: unexpected tensor '{k}'")
-    for k, shape in want.items():
-        if tuple(sd[k].shape) != shape:
-            raise ValueError(f"lineart state dict: '{k}' has shape {tuple(sd[k].shape)}, expected {shape}")
+    _check_state_dict(sd, lineart_key_shapes(), "lineart",
+                      "model0.1, model1.{0,3}, model2.{0,1,2}.conv_block.{1,5}, model3.{0,3}, model4.1, each with .weight and .bias")
 
 
 def pack_conv_in(w):
@@ -102,7 +88,7 @@ def pack_convt_phases(w):
     return w.detach().permute(2, 3, 1, 0).contiguous()
 
 
-class LineartAnnotator:
+class LineartAnnotator(AnnotatorBase):
     """`LineartAnnotator(weights)(image)` has the contract of `annotators.canny(image)` (PIL in, PIL RGB with three equal channels
     out; an array in, an array out), so it plugs into `MultiControlNetResidualsPipeline(annotators={"lineart":
     LineartAnnotator.from_pretrained(path)})`, whose `prep_control_images` then calls `annotate_batch` once per list of frames.
@@ -112,8 +98,8 @@ class LineartAnnotator:
 
     # the largest operand of a chunk of frames (the 9 x 64 taps of the second transposed convolution at half size: 288 bytes per
     # frame pixel) stays below what the GEMM and convolution kernels address with 32-bit byte offsets
-    max_activation_bytes = 0x7FFFFF00 - 1
     _bytes_per_pixel = 288
+    WEIGHTS_NAME = WEIGHTS_NAME
 
     def __init__(self, state_dict_or_path, device=None, dtype=None, coarse: bool = False):
         import torch
@@ -137,28 +123,11 @@ class LineartAnnotator:
             "out_w": sd["model4.1.weight"].detach().float()[0].permute(1, 2, 0).contiguous(),
             "out_b": sd["model4.1.bias"].detach().float().reshape(1).contiguous(),
         }
-        self._dev = None
-        self._ws = {}
-        self.timings = None  # a dict: receives (start, end) torch events per stage under the keys of STAGES -- tools/bench_lineart.py
-
-    @staticmethod
-    def _weights_path(path, coarse: bool = False) -> str:
-        path = os.fspath(path)
-        name = WEIGHTS_NAME_COARSE if coarse else WEIGHTS_NAME
-        if os.path.isdir(path):
-            path = os.path.join(path, name)
-        if not os.path.isfile(path):
-            raise FileNotFoundError(f"{path}: no such file (a local {name}, or a directory that holds it; nothing is ever downloaded)")
-        return path
+        self._ws = {}   # (`timings` receives events under the keys of STAGES -- tools/bench_lineart.py)
 
     @classmethod
     def _load(cls, path, coarse: bool = False):
-        import torch
-        path = cls._weights_path(path, coarse)
-        sd = torch.load(path, map_location="cpu", weights_only=True)
-        if not isinstance(sd, dict):
-            raise ValueError(f"{path}: not a state dict")
-        return sd
+        return load_state_dict(path, WEIGHTS_NAME_COARSE if coarse else cls.WEIGHTS_NAME)
 
     @classmethod
     def from_pretrained(cls, path, coarse: bool = False, **kwargs):
@@ -166,28 +135,6 @@ class LineartAnnotator:
         return cls(cls._load(path, coarse), coarse=coarse, **kwargs)
 
     # ---- device state ----------------------------------------------------------------------------------------------------------
-    def _device(self):
-        import torch
-        from . import _capi
-        _capi.lib()  # CAHipUnavailable when the extension is not built
-        if not torch.cuda.is_available():
-            raise _capi.CAHipUnavailable("LineartAnnotator needs a GPU (there is no CPU fallback)")
-        return torch.device(self.device if self.device is not None else "cuda")
-
-    def _weights(self, dev):
-        if self._dev is None or self._dev["out_b"].device != dev:
-            h = self._host
-            self._dev = {"conv_in": h["conv_in"].to(dev), "down": [w.to(dev) for w in h["down"]], "res": [(a.to(dev), b.to(dev)) for a, b in h["res"]],
-                         "up": [w.to(dev) for w in h["up"]], "out_w": h["out_w"].to(dev), "out_b": h["out_b"].to(dev)}
-        return self._dev
-
-    def chunk_frames(self, h: int, w: int) -> int:
-        """Frames per pass through the network: as many as keep the largest operand within max_activation_bytes."""
-        per_frame = h * w * self._bytes_per_pixel
-        if per_frame > self.max_activation_bytes:
-            raise ValueError(f"a {h} x {w} frame alone exceeds what the kernels address ({per_frame} > {self.max_activation_bytes} bytes)")
-        return self.max_activation_bytes // per_frame
-
     def workspace(self, n: int, h: int, w: int):
         """(three activation buffers for a chunk of frames, the tap buffer of the transposed convolutions, the InstanceNorm partial
         sums, the float32 logits [n, h, w]) of a call with n frames of h x w pixels, cached per (n, h, w); contents are never assumed."""
@@ -205,59 +152,12 @@ class LineartAnnotator:
                              torch.empty((n, h, w), dtype=torch.float32, device=dev))
         return self._ws[key]
 
-    def _stage(self, name):
-        import torch
-        if self.timings is None:
-            return None
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        self.timings.setdefault(name, []).append(ev)
-        ev[0].record()
-        return ev
-
     # ---- input checks ----------------------------------------------------------------------------------------------------------
     def _check_size(self, h: int, w: int) -> None:
         if h < 64 or w < 64 or h % 64 or w % 64:
             raise NotImplementedError(
                 f"LineartAnnotator takes frames with H % 64 == W % 64 == 0 (what the reference produces, and for which both resamplings of "
                 f"the detector are the identity at detect_resolution = image_resolution = min(H, W)); got {h} x {w}")
-
-    def _frames(self, frames):
-        """-> uint8 device tensor [n, H, W, 3].  The type, size and scope checks come before the device is touched.  A PIL image is taken
-        as np.asarray gives it, so its mode must be L or RGB (a grey frame is repeated to three channels, as the detector's HWC3 does)."""
-        import torch
-        if isinstance(frames, torch.Tensor):
-            if frames.dtype != torch.uint8:
-                raise TypeError(f"frames must be uint8, got {frames.dtype}")
-            if frames.dim() == 3:
-                frames = frames[..., None]
-            if frames.dim() != 4 or frames.shape[3] not in (1, 3):
-                raise ValueError(f"frames tensor must be [n, H, W] or [n, H, W, C] with C = 1 or 3, got {tuple(frames.shape)}")
-            self._check_size(frames.shape[1], frames.shape[2])
-            dev = self._device()
-            if frames.shape[3] == 1:
-                frames = frames.expand(-1, -1, -1, 3)
-            return frames.to(dev).contiguous()
-        host = []
-        for fr in frames:
-            a = np.asarray(fr)
-            if a.dtype != np.uint8:
-                raise TypeError(f"frames must be uint8, got {a.dtype}")
-            if a.ndim == 2:
-                a = a[:, :, None]
-            if a.ndim != 3 or a.shape[2] not in (1, 3):
-                raise ValueError(f"a frame must be [H, W] or [H, W, C] with C = 1 or 3 (PIL mode L or RGB: convert RGBA or palette "
-                                 f"frames with .convert('RGB') first), got {a.shape}" + (f" from PIL mode {fr.mode}" if hasattr(fr, "mode") else ""))
-            host.append(a)
-        if not host:
-            raise ValueError("no frames")
-        if any(a.shape != host[0].shape for a in host):
-            raise ValueError("all frames of a call must share one size")
-        self._check_size(host[0].shape[0], host[0].shape[1])
-        dev = self._device()
-        stack = np.stack(host)
-        if stack.shape[3] == 1:
-            stack = np.repeat(stack, 3, axis=3)
-        return torch.from_numpy(stack).to(dev)
 
     # ---- the chain -------------------------------------------------------------------------------------------------------------
     def _network(self, src, ws, i0: int) -> None:
@@ -271,12 +171,7 @@ class LineartAnnotator:
         def view(buf, hh, ww, ch):
             return buf[: n * hh * ww * ch].view(n, hh, ww, ch)
 
-        def timed(name, fn, *args, **kw):
-            ev = self._stage(name)
-            out = fn(*args, **kw)
-            if ev:
-                ev[1].record()
-            return out
+        timed = self._timed
 
         def norm(x, out, **kw):
             return timed("instnorm", K.instance_norm, x, out=out, partials=partials, eps=EPS, **kw)
@@ -315,10 +210,7 @@ class LineartAnnotator:
         for i0 in range(0, n, step):
             self._network(src[i0:i0 + step], ws, i0)
         if edges is not None or control is not None:
-            ev = self._stage("finish")
-            K.lineart_finish(ws[3], edges=edges, control=control, rep=rep)
-            if ev:
-                ev[1].record()
+            self._timed("finish", K.lineart_finish, ws[3], edges=edges, control=control, rep=rep)
         return ws[3]
 
     def logits(self, frames):
@@ -329,37 +221,4 @@ class LineartAnnotator:
     def edges(self, frames, out=None):
         """frames: a list of PIL images / uint8 arrays of one size, or a uint8 tensor [n, H, W, C] (no host copy when it is on the
         device) -> uint8 device tensor [n, H, W] (the detector's map: dark background 0, lines up to 255), written into `out` when given."""
-        import torch
-        src = self._frames(frames)
-        n, h, w, _ = src.shape
-        if out is None:
-            out = torch.empty((n, h, w), dtype=torch.uint8, device=src.device)
-        elif out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w) or out.device != src.device or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous uint8 tensor {(n, h, w)} on {src.device}")
-        if n:
-            self._run(src, out, None, 1)
-        return out
-
-    def annotate_batch(self, frames, out=None, rep: int = 1, dtype=None):
-        """-> the control tensor [rep * n, 3, H, W] on the device, map / 255 with three equal channels; rep = 2 writes the n frames
-        twice (torch.cat([ctrl] * 2) of classifier-free guidance).  Written into `out` (and `out` returned) when given."""
-        import torch
-        if rep not in (1, 2):
-            raise ValueError(f"rep={rep} (1 or 2)")
-        want = out.dtype if out is not None and dtype is None else (dtype if dtype is not None else torch.float32)
-        if want not in (torch.float32, torch.float16):
-            raise TypeError(f"the control tensor is float32 or float16, got {want}")
-        src = self._frames(frames)
-        n, h, w, _ = src.shape
-        if out is None:
-            out = torch.empty((rep * n, 3, h, w), dtype=want, device=src.device)
-        elif tuple(out.shape) != (rep * n, 3, h, w) or out.device != src.device or not out.is_contiguous() or out.dtype != want:
-            raise ValueError(f"out must be a contiguous {want} tensor {(rep * n, 3, h, w)} on {src.device}")
-        if n:
-            self._run(src, None, out, rep)
-        return out
-
-    def __call__(self, image):
-        e = self.edges([image])[0].cpu().numpy()
-        rgb = np.repeat(e[:, :, None], 3, axis=2)
-        return Image.fromarray(rgb) if Image is not None and not isinstance(image, np.ndarray) else rgb
+        return self._uint8_out(frames, out)

@@ -46,6 +46,7 @@ from __future__ import annotations
 
 import os
 
+from .annotator_base import check_state_dict as _check_state_dict
 from .lineart import LineartAnnotator
 
 WEIGHTS_NAME = "netG.pth"
@@ -91,17 +92,8 @@ def strip_module_prefix(sd) -> dict:
 
 def check_state_dict(sd) -> None:
     """KeyError naming a missing tensor, ValueError naming one that is unexpected or has the wrong shape."""
-    want = lineart_anime_key_shapes()
-    for k in want:
-        if k not in sd:
-            raise KeyError(f"lineart_anime state dict: '{k}' is missing ({len(want)} tensors expected: model.model.{{0,3}}, and per level "
-                           f"model.model.1[.model.3 ...].model.{{1,5}} (innermost: {{1,3}}), each with .weight and .bias)")
-    for k in sd:
-        if k not in want:
-            raise ValueError(f"lineart_anime state dict: unexpected tensor '{k}'")
-    for k, shape in want.items():
-        if tuple(sd[k].shape) != shape:
-            raise ValueError(f"lineart_anime state dict: '{k}' has shape {tuple(sd[k].shape)}, expected {shape}")
+    _check_state_dict(sd, lineart_anime_key_shapes(), "lineart_anime", "model.model.{0,3}, and per level "
+                      "model.model.1[.model.3 ...].model.{1,5} (innermost: {1,3}), each with .weight and .bias")
 
 
 def pack_conv_in(w):
@@ -160,8 +152,8 @@ class LineartAnimeAnnotator(LineartAnnotator):
 
     # the largest operand of a chunk of frames (the concatenation buffer C_0 at half size: 128 channels, 64 bytes per frame pixel)
     # stays below what the kernels address
-    max_activation_bytes = 0x7FFFFF00 - 1
     _bytes_per_pixel = 64
+    WEIGHTS_NAME = WEIGHTS_NAME
 
     def __init__(self, state_dict_or_path, device=None, dtype=None):
         import torch
@@ -185,18 +177,7 @@ class LineartAnimeAnnotator(LineartAnnotator):
             "out_w": sd[keys[0][1] + ".weight"].detach().float()[:, 0].permute(1, 2, 0).contiguous(),   # [4, 4, 128]
             "out_b": sd[keys[0][1] + ".bias"].detach().float().reshape(1).contiguous(),
         }
-        self._dev = None
-        self._ws = {}
-        self.timings = None  # a dict: receives (start, end) torch events per stage under the keys of STAGES -- tools/bench_lineart_anime.py
-
-    @staticmethod
-    def _weights_path(path, coarse: bool = False) -> str:
-        path = os.fspath(path)
-        if os.path.isdir(path):
-            path = os.path.join(path, WEIGHTS_NAME)
-        if not os.path.isfile(path):
-            raise FileNotFoundError(f"{path}: no such file (a local {WEIGHTS_NAME}, or a directory that holds it; nothing is ever downloaded)")
-        return path
+        self._ws = {}   # (`timings` receives events under the keys of STAGES -- tools/bench_lineart_anime.py)
 
     @classmethod
     def from_pretrained(cls, path, **kwargs):
@@ -204,19 +185,6 @@ class LineartAnimeAnnotator(LineartAnnotator):
         return cls(cls._load(path), **kwargs)
 
     # ---- device state ----------------------------------------------------------------------------------------------------------
-    def _device(self):
-        import torch
-        from . import _capi
-        _capi.lib()  # CAHipUnavailable when the extension is not built
-        if not torch.cuda.is_available():
-            raise _capi.CAHipUnavailable("LineartAnimeAnnotator needs a GPU (there is no CPU fallback)")
-        return torch.device(self.device if self.device is not None else "cuda")
-
-    def _weights(self, dev):
-        if self._dev is None or self._dev["out_b"].device != dev:
-            self._dev = {k: ([w.to(dev) for w in v] if isinstance(v, list) else v.to(dev)) for k, v in self._host.items()}
-        return self._dev
-
     def workspace(self, n: int, h: int, w: int):
         """The buffers of a call with n frames of h x w pixels, cached per (n, h, w); contents are never assumed.  For a chunk of m
         frames: "L" [7] and "C" [7] per level 0 .. 6 (flat), "raw" (a convolution's output before its InstanceNorm), "inner"
@@ -263,13 +231,7 @@ class LineartAnimeAnnotator(LineartAnnotator):
         def view(buf, i, ch):
             return buf[: n * hs[i] * wd[i] * ch].view(n, hs[i], wd[i], ch)
 
-        def timed(name, fn, *args, **kw):
-            ev = self._stage(name)
-            out = fn(*args, **kw)
-            if ev:
-                ev[1].record()
-            return out
-
+        timed = self._timed
         L = [view(ws["L"][i], i, CHANNELS[i]) for i in range(last)]
         C = [view(ws["C"][i], i, 2 * CHANNELS[i]) for i in range(last)]
         timed("conv_in", K.lanime_conv_in, src, wts["conv_in"], wts["in_b"], L[0], C[0])
@@ -292,10 +254,7 @@ class LineartAnimeAnnotator(LineartAnnotator):
         for i0 in range(0, n, step):
             self._network(src[i0:i0 + step], ws, i0)
         if edges is not None or control is not None:
-            ev = self._stage("finish")
-            K.lanime_finish(ws["pre"], edges=edges, control=control, rep=rep)
-            if ev:
-                ev[1].record()
+            self._timed("finish", K.lanime_finish, ws["pre"], edges=edges, control=control, rep=rep)
         return ws["pre"]
 
     def pre_tanh(self, frames):

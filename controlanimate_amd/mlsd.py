@@ -46,12 +46,7 @@ from __future__ import annotations
 
 import os
 
-import numpy as np
-
-try:
-    from PIL import Image
-except Exception:  # pragma: no cover
-    Image = None
+from .annotator_base import AnnotatorBase, BufferPlan, check_state_dict as _check_state_dict
 
 WEIGHTS_NAME = "mlsd_large_512_fp32.pth"
 EPS = 1e-5
@@ -109,17 +104,8 @@ def mlsd_key_shapes() -> dict:
 def check_state_dict(sd) -> None:
     """KeyError naming a missing tensor, ValueError naming one that is unexpected or has the wrong shape.  num_batches_tracked and any
     further backbone. key (layers past features.13 that a checkpoint may keep) are ignored."""
-    want = mlsd_key_shapes()
-    for k in want:
-        if k not in sd:
-            raise KeyError(f"mlsd state dict: '{k}' is missing ({len(want)} tensors expected: backbone.features.0 .. 13 and block15 .. block23 "
-                           f"of MobileV2_MLSD_Large)")
-    for k in sd:
-        if k not in want and not k.endswith("num_batches_tracked") and not k.startswith("backbone."):
-            raise ValueError(f"mlsd state dict: unexpected tensor '{k}'")
-    for k, shape in want.items():
-        if tuple(sd[k].shape) != shape:
-            raise ValueError(f"mlsd state dict: '{k}' has shape {tuple(sd[k].shape)}, expected {shape}")
+    _check_state_dict(sd, mlsd_key_shapes(), "mlsd", "backbone.features.0 .. 13 and block15 .. block23 of MobileV2_MLSD_Large",
+                      ignore=lambda k: k.endswith("num_batches_tracked") or k.startswith("backbone."))
 
 
 def fold_bn(sd, conv: str, bn: str):
@@ -160,7 +146,7 @@ def pack_depthwise(w):
     return w.detach().reshape(w.shape[0], 9).t().contiguous()
 
 
-class MlsdAnnotator:
+class MlsdAnnotator(AnnotatorBase):
     """`MlsdAnnotator(weights)(image)` has the contract of `annotators.canny(image)` (PIL in, PIL RGB with three equal channels out; an
     array in, an array out), so it plugs into `MultiControlNetResidualsPipeline(annotators={"mlsd": MlsdAnnotator.from_pretrained(path)})`,
     whose `prep_control_images` then calls `annotate_batch` once per list of frames.  Nothing makes it a default: the weights are the
@@ -169,8 +155,8 @@ class MlsdAnnotator:
 
     # the largest operand of a chunk of frames (the 128-channel concatenation at half resolution: 64 bytes per frame pixel) stays below
     # what the GEMM and convolution kernels address with 32-bit byte offsets
-    max_activation_bytes = 0x7FFFFF00 - 1
     _bytes_per_pixel = 64
+    WEIGHTS_NAME = WEIGHTS_NAME
 
     def __init__(self, state_dict_or_path, device=None, dtype=None, detect_resolution: int = 512, image_resolution: int = 512,
                  thr_v: float = 0.1, thr_d: float = 0.1):
@@ -206,63 +192,9 @@ class MlsdAnnotator:
             "C": (conv(f["C"][0]), conv(f["C"][1])),
             "head": (torch.nn.functional.pad(head_w, (0, 0, 0, 3)).contiguous().to(dtype), torch.nn.functional.pad(head_b, (0, 3)).contiguous()),
         }
-        self._dev = None
-        self._ws = {}
-        self.timings = None  # a dict: receives (start, end) torch events per stage under the keys of STAGES -- tools/bench_mlsd.py
-
-    @staticmethod
-    def _weights_path(path) -> str:
-        path = os.fspath(path)
-        if os.path.isdir(path):
-            path = os.path.join(path, WEIGHTS_NAME)
-        if not os.path.isfile(path):
-            raise FileNotFoundError(f"{path}: no such file (a local {WEIGHTS_NAME}, or a directory that holds it; nothing is ever downloaded)")
-        return path
-
-    @classmethod
-    def _load(cls, path):
-        import torch
-        path = cls._weights_path(path)
-        sd = torch.load(path, map_location="cpu", weights_only=True)
-        if not isinstance(sd, dict):
-            raise ValueError(f"{path}: not a state dict")
-        return sd
-
-    @classmethod
-    def from_pretrained(cls, path, **kwargs):
-        """path: a local mlsd_large_512_fp32.pth or a directory that holds it (no network access, ever)."""
-        return cls(cls._load(path), **kwargs)
+        self._ws = {}   # (`timings` receives events under the keys of STAGES -- tools/bench_mlsd.py)
 
     # ---- device state ----------------------------------------------------------------------------------------------------------
-    def _device(self):
-        import torch
-        from . import _capi
-        _capi.lib()  # CAHipUnavailable when the extension is not built
-        if not torch.cuda.is_available():
-            raise _capi.CAHipUnavailable("MlsdAnnotator needs a GPU (there is no CPU fallback)")
-        return torch.device(self.device if self.device is not None else "cuda")
-
-    def _weights(self, dev):
-        import torch
-
-        def move(o):
-            if isinstance(o, torch.Tensor):
-                return o.to(dev)
-            if isinstance(o, dict):
-                return {k: move(v) for k, v in o.items()}
-            return type(o)(move(v) for v in o)
-
-        if self._dev is None or self._dev["head"][1].device != dev:
-            self._dev = move(self._host)
-        return self._dev
-
-    def chunk_frames(self, h: int, w: int) -> int:
-        """Frames per pass through the network: as many as keep the largest operand within max_activation_bytes."""
-        per_frame = h * w * self._bytes_per_pixel
-        if per_frame > self.max_activation_bytes:
-            raise ValueError(f"a {h} x {w} frame alone exceeds what the kernels address ({per_frame} > {self.max_activation_bytes} bytes)")
-        return self.max_activation_bytes // per_frame
-
     def workspace(self, n: int, h: int, w: int) -> dict:
         """The buffers of a call with n frames of h x w pixels, cached per (n, h, w): the tpMap float32 [n, h/2, w/2, 8], the segments, the
         counts, the candidate list of the decode, the map that is drawn when only the control tensor is asked for, and a pool of
@@ -281,15 +213,6 @@ class MlsdAnnotator:
                              "pool": [], "plan": [], "planned": False}
         return self._ws[key]
 
-    def _stage(self, name):
-        import torch
-        if self.timings is None:
-            return None
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        self.timings.setdefault(name, []).append(ev)
-        ev[0].record()
-        return ev
-
     # ---- input checks ----------------------------------------------------------------------------------------------------------
     def _check_size(self, h: int, w: int) -> None:
         r = self.resolution
@@ -298,85 +221,14 @@ class MlsdAnnotator:
                 f"MlsdAnnotator takes frames with min(H, W) == detect_resolution == image_resolution (= {r}) and H % 64 == W % 64 == 0, for "
                 f"which every resampling of the detector is the identity; got {h} x {w}")
 
-    def _frames(self, frames):
-        """-> uint8 device tensor [n, H, W, 3].  The type, size and scope checks come before the device is touched.  A PIL image is taken
-        as np.asarray gives it, so its mode must be L or RGB (a grey frame is repeated to three channels, as the detector's HWC3 does)."""
-        import torch
-        if isinstance(frames, torch.Tensor):
-            if frames.dtype != torch.uint8:
-                raise TypeError(f"frames must be uint8, got {frames.dtype}")
-            if frames.dim() == 3:
-                frames = frames[..., None]
-            if frames.dim() != 4 or frames.shape[3] not in (1, 3):
-                raise ValueError(f"frames tensor must be [n, H, W] or [n, H, W, C] with C = 1 or 3, got {tuple(frames.shape)}")
-            self._check_size(frames.shape[1], frames.shape[2])
-            dev = self._device()
-            if frames.shape[3] == 1:
-                frames = frames.expand(-1, -1, -1, 3)
-            return frames.to(dev).contiguous()
-        host = []
-        for fr in frames:
-            a = np.asarray(fr)
-            if a.dtype != np.uint8:
-                raise TypeError(f"frames must be uint8, got {a.dtype}")
-            if a.ndim == 2:
-                a = a[:, :, None]
-            if a.ndim != 3 or a.shape[2] not in (1, 3):
-                raise ValueError(f"a frame must be [H, W] or [H, W, C] with C = 1 or 3 (PIL mode L or RGB: convert RGBA or palette "
-                                 f"frames with .convert('RGB') first), got {a.shape}" + (f" from PIL mode {fr.mode}" if hasattr(fr, "mode") else ""))
-            host.append(a)
-        if not host:
-            raise ValueError("no frames")
-        if any(a.shape != host[0].shape for a in host):
-            raise ValueError("all frames of a call must share one size")
-        self._check_size(host[0].shape[0], host[0].shape[1])
-        dev = self._device()
-        stack = np.stack(host)
-        if stack.shape[3] == 1:
-            stack = np.repeat(stack, 3, axis=3)
-        return torch.from_numpy(stack).to(dev)
-
     # ---- the chain -------------------------------------------------------------------------------------------------------------
     def _network(self, src, ws, i0: int) -> None:
         """The network for the frames `src` (a chunk), the tpMap into ws["tp"][i0 : i0 + len(src)]."""
-        import torch
         from . import kernels as K
         wts = self._weights(src.device)
         n, h, w, _ = src.shape
-        pool, plan = ws["pool"], ws["plan"]  # [[flat buffer, taken]]; the slot of the i-th take of a pass, fixed by the first pass
-        replay, cursor = ws["planned"], [0]
-        if not replay:
-            plan.clear()   # (a first pass that did not finish starts over)
-
-        def take(*shape):
-            numel = int(np.prod(shape))
-            if replay:   # the same buffers in the same order on every pass: nothing is allocated after the first one (a captured graph stays valid)
-                slot = pool[plan[cursor[0]]]
-                cursor[0] += 1
-                assert not slot[1] and slot[0].numel() >= numel
-            else:
-                free = [i for i, sl in enumerate(pool) if not sl[1] and sl[0].numel() >= numel]
-                if not free:
-                    pool.append([torch.empty(numel, dtype=self.dtype, device=src.device), False])
-                    free = [len(pool) - 1]
-                plan.append(min(free, key=lambda i: pool[i][0].numel()))
-                slot = pool[plan[-1]]
-            slot[1] = True
-            return slot[0][:numel].view(*shape)
-
-        def give(t):
-            for slot in pool:
-                if slot[0].data_ptr() == t.data_ptr():
-                    slot[1] = False
-                    return
-            raise AssertionError("not a pool buffer")
-
-        def timed(name, fn, *args, **kw):
-            ev = self._stage(name)
-            out = fn(*args, **kw)
-            if ev:
-                ev[1].record()
-            return out
+        plan = BufferPlan(ws, self.dtype, src.device)   # the same buffers in the same order on every pass
+        take, give, timed = plan.take, plan.give, self._timed
 
         def pw(x, wb, act, out2d=None, residual=None, name="pointwise", out_f32=False):
             """1x1 convolution of NHWC x as a GEMM over its pixels; out2d: a [pixels, N] view (possibly of a wider tensor)."""
@@ -390,8 +242,6 @@ class MlsdAnnotator:
                   out_f32=out_f32)
             return ret
 
-        for slot in pool:
-            slot[1] = False
         x = timed("prep", K.mlsd_prep, src, take(n, h, w, 8))
         y = timed("stem", K.conv3x3, x, wts["stem"][0], bias=wts["stem"][1], stride=2, pad_asym=True, act=K.ACT_RELU6, out=take(n, h // 2, w // 2, 32))
         give(x)
@@ -450,14 +300,8 @@ class MlsdAnnotator:
         for i0 in range(0, n, step):
             self._network(src[i0:i0 + step], ws, i0)
         if edges is not None or control is not None:
-            ev = self._stage("decode")
-            K.mlsd_decode(ws["tp"], self.thr_v, self.thr_d, segments=ws["segments"], count=ws["count"], ws=ws["decode"])
-            if ev:
-                ev[1].record()
-            ev = self._stage("draw")
-            K.mlsd_draw(ws["segments"], ws["count"], h, w, edges=edges if edges is not None else ws["map"], control=control, rep=rep)
-            if ev:
-                ev[1].record()
+            self._timed("decode", K.mlsd_decode, ws["tp"], self.thr_v, self.thr_d, segments=ws["segments"], count=ws["count"], ws=ws["decode"])
+            self._timed("draw", K.mlsd_draw, ws["segments"], ws["count"], h, w, edges=edges if edges is not None else ws["map"], control=control, rep=rep)
         return ws["tp"]
 
     def tpmap(self, frames):
@@ -469,37 +313,4 @@ class MlsdAnnotator:
     def edges(self, frames, out=None):
         """frames: a list of PIL images / uint8 arrays of one size, or a uint8 tensor [n, H, W, C] (no host copy when it is on the
         device) -> uint8 device tensor [n, H, W] (the detector's map: 0, lines 255), written into `out` when given."""
-        import torch
-        src = self._frames(frames)
-        n, h, w, _ = src.shape
-        if out is None:
-            out = torch.empty((n, h, w), dtype=torch.uint8, device=src.device)
-        elif out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w) or out.device != src.device or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous uint8 tensor {(n, h, w)} on {src.device}")
-        if n:
-            self._run(src, out, None, 1)
-        return out
-
-    def annotate_batch(self, frames, out=None, rep: int = 1, dtype=None):
-        """-> the control tensor [rep * n, 3, H, W] on the device, map / 255 with three equal channels; rep = 2 writes the n frames
-        twice (torch.cat([ctrl] * 2) of classifier-free guidance).  Written into `out` (and `out` returned) when given."""
-        import torch
-        if rep not in (1, 2):
-            raise ValueError(f"rep={rep} (1 or 2)")
-        want = out.dtype if out is not None and dtype is None else (dtype if dtype is not None else torch.float32)
-        if want not in (torch.float32, torch.float16):
-            raise TypeError(f"the control tensor is float32 or float16, got {want}")
-        src = self._frames(frames)
-        n, h, w, _ = src.shape
-        if out is None:
-            out = torch.empty((rep * n, 3, h, w), dtype=want, device=src.device)
-        elif tuple(out.shape) != (rep * n, 3, h, w) or out.device != src.device or not out.is_contiguous() or out.dtype != want:
-            raise ValueError(f"out must be a contiguous {want} tensor {(rep * n, 3, h, w)} on {src.device}")
-        if n:
-            self._run(src, None, out, rep)
-        return out
-
-    def __call__(self, image):
-        e = self.edges([image])[0].cpu().numpy()
-        rgb = np.repeat(e[:, :, None], 3, axis=2)
-        return Image.fromarray(rgb) if Image is not None and not isinstance(image, np.ndarray) else rgb
+        return self._uint8_out(frames, out)

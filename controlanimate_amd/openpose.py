@@ -68,10 +68,7 @@ import re
 
 import numpy as np
 
-try:
-    from PIL import Image
-except Exception:  # pragma: no cover
-    Image = None
+from .annotator_base import AnnotatorBase, BufferPlan, check_state_dict as _check_state_dict
 
 WEIGHTS_NAME = "body_pose_model.pth"
 MAX_PEAKS, MAX_PEOPLE, AREA_TAPS = 64, 64, 8
@@ -116,22 +113,121 @@ _PREFIX = re.compile(r"^model\d+(_\d+)?\.")
 
 
 def bare_keys(sd) -> dict:
-    """The checkpoint under its bare layer names: 'model0.conv1_1.weight' / 'model3_2.Mconv1_stage3_L2.weight' lose the module prefix."""
+    """The checkpoint under its bare layer names: 'model0.conv1_1.weight' / 'model3_2.Mconv1_stage3_L2.weight' lose the module prefix
+    (the body's, the face's and the hand's checkpoints alike)."""
     return {_PREFIX.sub("", k): v for k, v in sd.items()}
 
 
 def check_state_dict(sd) -> None:
     """KeyError naming a missing tensor, ValueError naming one that is unexpected or has the wrong shape (bare names)."""
-    want = pose_key_shapes()
-    for k in want:
-        if k not in sd:
-            raise KeyError(f"openpose state dict: '{k}' is missing ({len(want)} tensors expected: the layers of bodypose_model)")
-    for k in sd:
-        if k not in want:
-            raise ValueError(f"openpose state dict: unexpected tensor '{k}'")
-    for k, shape in want.items():
-        if tuple(sd[k].shape) != shape:
-            raise ValueError(f"openpose state dict: '{k}' has shape {tuple(sd[k].shape)}, expected {shape}")
+    _check_state_dict(sd, pose_key_shapes(), "openpose", "the layers of bodypose_model")
+
+
+# ---- packing (the body's network and the face and hand stages') ----------------------------------------------------------------------
+def pack_mconv1(w, heads):
+    """Mconv1's weight [128, maps + 128, 7, 7] on input channels [each head's maps | features 128] -> [128, 7, 7, 128 + columns] on
+    [features 128 | each head's maps, zero-padded to its columns of the concatenation]; heads: ((maps, columns), ...)."""
+    import torch
+    maps = sum(m for m, _ in heads)
+    z = torch.zeros((w.shape[0], 128 + sum(c for _, c in heads), 7, 7), dtype=w.dtype)
+    z[:, 0:128] = w[:, maps:maps + 128]
+    src, dst = 0, 128
+    for m, c in heads:
+        z[:, dst:dst + m] = w[:, src:src + m]
+        src, dst = src + m, dst + c
+    return z.permute(0, 2, 3, 1).contiguous()
+
+
+def cpm_packers(sd, dtype, heads):
+    """(conv, lin, mconv1): the layers of a CPM network out of the state dict `sd` (bare names) as (weight in `dtype`, fp32 bias) in the
+    kernels' layouts; heads: the concatenation's layout behind the features, as pack_mconv1 takes it."""
+    import torch
+    F = torch.nn.functional
+
+    def wb(name):
+        return sd[name + ".weight"].detach().float(), sd[name + ".bias"].detach().float().contiguous()
+
+    def conv(name, pad_in=0):  # [Cout, Cin, k, k] -> [Cout, k, k, Cin (+ pad_in zero channels)]
+        w, b = wb(name)
+        return F.pad(w, (0, 0, 0, 0, 0, pad_in)).permute(0, 2, 3, 1).contiguous().to(dtype), b
+
+    def lin(name, pad_out=0):  # [Cout, Cin, 1, 1] -> [Cout + pad_out zero rows, Cin]
+        w, b = wb(name)
+        return F.pad(w.reshape(w.shape[0], -1), (0, 0, 0, pad_out)).contiguous().to(dtype), F.pad(b, (0, pad_out)).contiguous()
+
+    def mconv1(name):
+        w, b = wb(name)
+        return pack_mconv1(w, heads).to(dtype), b
+
+    return conv, lin, mconv1
+
+
+def pack_crop_cpm_weights(sd, dtype, front, maps: int, rows: int, columns: int) -> dict:
+    """The one-branch CPM network of the face and hand stages, packed: `maps` heat maps, written as `rows` GEMM rows (zero-padded: the
+    GEMM stores 16-byte chunks) into `columns` columns of the concatenation behind the 128 features."""
+    conv, lin, mconv1 = cpm_packers(sd, dtype, ((maps, columns),))
+    pad = rows - maps
+    return {"front": [None if l == "pool" else conv(l[0], 5 if l[0] == "conv1_1" else 0) for l in front],
+            "stage1": {"fc": lin("conv6_1_CPM"), "out": lin("conv6_2_CPM", pad)},
+            "stages": [{"conv7": [mconv1(f"Mconv1_stage{t}")] + [conv(f"Mconv{i}_stage{t}") for i in (2, 3, 4, 5)],
+                        "fc": lin(f"Mconv6_stage{t}"), "out": lin(f"Mconv7_stage{t}", pad)} for t in range(2, 7)]}
+
+
+def crop_cpm_network(owner, ws, wts, prefix: str, front, crop, nc: int, side: int, hl: int, cat_cols: int, out2d, direct: bool) -> None:
+    """The CPM network of the face and hand stages for `nc` crops of side x side pixels, from the crop launch onward: the front end, the
+    feature copy into the concatenation [features 128 | heat | zeros] of `cat_cols` columns at hl x hl, stage 1 and the five 7x7 stages,
+    the last of which writes the fp32 view out2d [nc * hl * hl, heat columns].  crop(out): the stage's crop launch into out
+    [nc, side, side, 8]; prefix: "face" / "hand", in front of the stage names; ws: the dict that holds the pool and its plan (the buffer
+    plan and the per-stage launch counts depend on the order of the takes, gives and launches below)."""
+    from . import kernels as K
+    timed = owner._timed
+    plan = BufferPlan(ws, owner.dtype, out2d.device)   # the body's buffer plan: the same buffers in the same order on every pass
+    take, give = plan.take, plan.give
+
+    def pw(x2d, wb, act, out2d, out_f32=False):
+        timed(prefix + "_pointwise", K.gemm, x2d, wb[0], bias=wb[1], act=act, out=out2d, out_f32=out_f32)
+
+    x = timed(prefix + "_crop", crop, take(nc, side, side, 8))
+    for layer, wb in zip(front, wts["front"]):
+        if layer == "pool":
+            y = timed(prefix + "_pool", K.maxpool2x2, x, take(nc, x.shape[1] // 2, x.shape[2] // 2, x.shape[3]))
+        else:   # split_k=False: the order of an output's sum is then the same whatever the number of crops
+            y = timed(prefix + "_conv", K.conv3x3, x, wb[0], bias=wb[1], act=K.ACT_RELU, out=take(*x.shape[:3], wb[0].shape[0]), split_k=False)
+        give(x)
+        x = y
+    feat = x
+    rows = nc * hl * hl
+    cat = take(nc, hl, hl, cat_cols)
+    cat2d = cat.view(rows, cat_cols)
+    cat2d.zero_()   # the columns behind the heat maps are read (against zero weights) and never written
+    timed(prefix + "_copy", K.copy_cols, feat.view(rows, 128), cat2d, 0)
+    heat_cols = cat2d[:, 128:128 + out2d.shape[1]]
+    fc = take(rows, 512)
+    pw(feat.view(rows, 128), wts["stage1"]["fc"], K.ACT_RELU, fc)
+    give(feat)
+    pw(fc, wts["stage1"]["out"], K.ACT_NONE, heat_cols)
+    give(fc)
+    cols = None if direct else take(rows, 49 * cat_cols)
+    for t, stage in enumerate(wts["stages"]):
+        a = cat
+        for i in range(5):
+            y = take(nc, hl, hl, 128)
+            timed(prefix + "_conv7", K.conv7x7, [a], [stage["conv7"][i][0]], biases=[stage["conv7"][i][1]], relu=True, outs=[y], direct=direct, cols=cols)
+            if i:
+                give(a)
+            a = y
+        fc = take(rows, 128)
+        pw(a.view(rows, 128), stage["fc"], K.ACT_RELU, fc)
+        give(a)
+        if t == len(wts["stages"]) - 1:
+            pw(fc, stage["out"], K.ACT_NONE, out2d, out_f32=True)
+        else:
+            pw(fc, stage["out"], K.ACT_NONE, heat_cols)
+        give(fc)
+    if cols is not None:
+        give(cols)
+    give(cat)
+    ws["planned"] = True
 
 
 # ---- host-side tables ------------------------------------------------------------------------------------------------------------
@@ -222,56 +318,16 @@ def sin_table() -> np.ndarray:
     return np.round(np.sin(np.deg2rad(np.arange(451, dtype=np.float64))), 7).astype(np.float32)
 
 
-class BufferPlan:
-    """The activation buffers of one pass through a network, out of a workspace's pool (ws["pool"]: [[flat buffer, taken]]; ws["plan"]: the
-    slot of the i-th take of a pass, fixed by the first pass; ws["planned"]).  The layers take and give buffers in a fixed order; the first
-    pass allocates them and every later pass gets the same ones in the same order, so nothing is allocated after it and a captured graph
-    stays valid.  The caller sets ws["planned"] when a pass has finished (a first pass that did not finish starts over)."""
-
-    def __init__(self, ws: dict, dtype, device):
-        self.pool, self.plan, self.replay, self.cursor = ws["pool"], ws["plan"], ws["planned"], 0
-        self.dtype, self.device = dtype, device
-        if not self.replay:
-            self.plan.clear()
-        for slot in self.pool:
-            slot[1] = False
-
-    def take(self, *shape):
-        import torch
-        numel = int(np.prod(shape))
-        pool = self.pool
-        if self.replay:
-            slot = pool[self.plan[self.cursor]]
-            self.cursor += 1
-            assert not slot[1] and slot[0].numel() >= numel
-        else:
-            free = [i for i, sl in enumerate(pool) if not sl[1] and sl[0].numel() >= numel]
-            if not free:
-                pool.append([torch.empty(numel, dtype=self.dtype, device=self.device), False])
-                free = [len(pool) - 1]
-            self.plan.append(min(free, key=lambda i: pool[i][0].numel()))
-            slot = pool[self.plan[-1]]
-        slot[1] = True
-        return slot[0][:numel].view(*shape)
-
-    def give(self, t) -> None:
-        for slot in self.pool:
-            if slot[0].data_ptr() == t.data_ptr():
-                slot[1] = False
-                return
-        raise AssertionError("not a pool buffer")
-
-
-class OpenposeAnnotator:
+class OpenposeAnnotator(AnnotatorBase):
     """`OpenposeAnnotator(weights)(image)` has the contract of `annotators.canny(image)` (PIL in, PIL RGB out; an array in, an array out),
     so it plugs into `MultiControlNetResidualsPipeline(annotators={"openpose": OpenposeAnnotator.from_pretrained(path)})`, whose
     `prep_control_images` then calls `annotate_batch` once per list of frames.  Nothing makes it a default: the weights are the user's
     file.  It draws the body skeleton, and the faces when a face network is given (see the module's head).  Non-uint8 input raises TypeError, frames of different sizes
     ValueError, sizes out of scope NotImplementedError -- all before the device is touched; without the library or a GPU a call raises
-    CAHipUnavailable (there is no CPU fallback)."""
+    CAHipUnavailable (there is no CPU fallback).  `from_pretrained(path, face=<a local facenet.pth or a directory that holds it>)` adds the
+    face stage, `hand=<a local hand_pose_model.pth or its directory>` the hand stage (hands())."""
 
-    # the largest 16-bit operand of a chunk of frames stays below what the GEMM and convolution kernels address with 32-bit byte offsets
-    max_activation_bytes = 0x7FFFFF00 - 1
+    WEIGHTS_NAME = WEIGHTS_NAME
     STAGES = STAGES
 
     def __init__(self, state_dict_or_path, device=None, dtype=None, detect_resolution: int = 512, image_resolution: int = 512,
@@ -295,25 +351,8 @@ class OpenposeAnnotator:
         sd = bare_keys(sd)
         check_state_dict(sd)
         self.device, self.dtype, self.resolution = device, dtype, int(detect_resolution)
-        F = torch.nn.functional
-
-        def wb(name):
-            return sd[name + ".weight"].detach().float(), sd[name + ".bias"].detach().float().contiguous()
-
-        def conv(name, pad_in=0):  # [Cout, Cin, k, k] -> [Cout, k, k, Cin (+ pad_in zero channels)]
-            w, b = wb(name)
-            return F.pad(w, (0, 0, 0, 0, 0, pad_in)).permute(0, 2, 3, 1).contiguous().to(dtype), b
-
-        def lin(name, pad_out=0):  # [Cout, Cin, 1, 1] -> [Cout + pad_out zero rows, Cin]
-            w, b = wb(name)
-            return F.pad(w.reshape(w.shape[0], -1), (0, 0, 0, pad_out)).contiguous().to(dtype), F.pad(b, (0, pad_out)).contiguous()
-
-        def mconv1(name):  # input channels [L1 38 | L2 19 | features 128] -> [features 128 | L1 38, 2 zeros | L2 19, 5 zeros]
-            w, b = wb(name)
-            z = torch.zeros((128, 192, 7, 7))
-            z[:, 0:128], z[:, 128:166], z[:, 168:187] = w[:, 57:185], w[:, 0:38], w[:, 38:57]
-            return z.permute(0, 2, 3, 1).contiguous().to(dtype), b
-
+        # Mconv1's input channels [L1 38 | L2 19 | features 128] -> [features 128 | L1 38, 2 zeros | L2 19, 5 zeros]
+        conv, lin, mconv1 = cpm_packers(sd, dtype, ((38, 40), (19, 24)))
         pad_n = {1: 2, 2: 5}  # 38 -> 40, 19 -> 24 output columns: the GEMM stores 16-byte chunks
         # packed once, on the host
         self._host = {"front": [None if l == "pool" else conv(l[0], 5 if l[0] == "conv1_1" else 0) for l in FRONT],
@@ -322,8 +361,7 @@ class OpenposeAnnotator:
                       "stages": [[{"conv7": [mconv1(f"Mconv1_stage{t}_L{br}")] + [conv(f"Mconv{i}_stage{t}_L{br}") for i in (2, 3, 4, 5)],
                                    "fc": lin(f"Mconv6_stage{t}_L{br}"), "out": lin(f"Mconv7_stage{t}_L{br}", pad_n[br])} for br in (1, 2)]
                                  for t in range(2, 7)]}
-        self._dev = None
-        self._ws = {}
+        self._ws = {}   # (`timings` receives events under the keys of STAGES -- tools/bench_openpose.py)
         self._tables = {}
         self._face = None
         if include_face:
@@ -335,57 +373,8 @@ class OpenposeAnnotator:
             from .openpose_hand import HAND_STAGES, HandStage
             self._hand = HandStage(self, hand, max_hands)   # (key and shape checks before the device is touched)
             self.STAGES = {**self.STAGES, **HAND_STAGES}
-        self.timings = None  # a dict: receives (start, end) torch events per stage under the keys of STAGES -- tools/bench_openpose.py
-
-    @staticmethod
-    def _weights_path(path) -> str:
-        path = os.fspath(path)
-        if os.path.isdir(path):
-            path = os.path.join(path, WEIGHTS_NAME)
-        if not os.path.isfile(path):
-            raise FileNotFoundError(f"{path}: no such file (a local {WEIGHTS_NAME}, or a directory that holds it; nothing is ever downloaded)")
-        return path
-
-    @classmethod
-    def _load(cls, path):
-        import torch
-        path = cls._weights_path(path)
-        sd = torch.load(path, map_location="cpu", weights_only=True)
-        if not isinstance(sd, dict):
-            raise ValueError(f"{path}: not a state dict")
-        return sd
-
-    @classmethod
-    def from_pretrained(cls, path, **kwargs):
-        """path: a local body_pose_model.pth or a directory that holds it (no network access, ever).  face=<a local facenet.pth or a
-        directory that holds it> adds the face stage, hand=<a local hand_pose_model.pth or its directory> the hand stage (hands())."""
-        return cls(cls._load(path), **kwargs)
 
     # ---- device state ----------------------------------------------------------------------------------------------------------
-    def _device(self):
-        import torch
-        from . import _capi
-        _capi.lib()  # CAHipUnavailable when the extension is not built
-        if not torch.cuda.is_available():
-            raise _capi.CAHipUnavailable("OpenposeAnnotator needs a GPU (there is no CPU fallback)")
-        return torch.device(self.device if self.device is not None else "cuda")
-
-    def _weights(self, dev):
-        import torch
-
-        def move(o):
-            if o is None:
-                return None
-            if isinstance(o, torch.Tensor):
-                return o.to(dev)
-            if isinstance(o, dict):
-                return {k: move(v) for k, v in o.items()}
-            return type(o)(move(v) for v in o)
-
-        if self._dev is None or self._dev["front"][0][1].device != dev:
-            self._dev = move(self._host)
-        return self._dev
-
     def host_tables(self, h: int, w: int) -> dict:
         """The host-side tables of an h x w frame (cached): the geometry, the AREA tables of both axes, the float64 composite matrices
         (ax, gax [w, wl]; ay, gay [h, hl]) and OpenCV's sine table."""
@@ -432,15 +421,6 @@ class OpenposeAnnotator:
                              "pool": [], "plan": [], "planned": False}
         return self._ws[key]
 
-    def _stage(self, name):
-        import torch
-        if self.timings is None:
-            return None
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        self.timings.setdefault(name, []).append(ev)
-        ev[0].record()
-        return ev
-
     # ---- input checks ----------------------------------------------------------------------------------------------------------
     def _check_size(self, h: int, w: int) -> None:
         r = self.resolution
@@ -448,44 +428,6 @@ class OpenposeAnnotator:
             raise NotImplementedError(
                 f"OpenposeAnnotator takes frames with min(H, W) == detect_resolution == image_resolution (= {r}), H % 64 == W % 64 == 0, "
                 f"192 <= H, H % 184 != 0 and H, W <= 2048; got {h} x {w}")
-
-    def _frames(self, frames):
-        """-> uint8 device tensor [n, H, W, 3].  The type, size and scope checks come before the device is touched.  A PIL image is taken
-        as np.asarray gives it, so its mode must be L or RGB (a grey frame is repeated to three channels, as the detector's HWC3 does)."""
-        import torch
-        if isinstance(frames, torch.Tensor):
-            if frames.dtype != torch.uint8:
-                raise TypeError(f"frames must be uint8, got {frames.dtype}")
-            if frames.dim() == 3:
-                frames = frames[..., None]
-            if frames.dim() != 4 or frames.shape[3] not in (1, 3):
-                raise ValueError(f"frames tensor must be [n, H, W] or [n, H, W, C] with C = 1 or 3, got {tuple(frames.shape)}")
-            self._check_size(frames.shape[1], frames.shape[2])
-            dev = self._device()
-            if frames.shape[3] == 1:
-                frames = frames.expand(-1, -1, -1, 3)
-            return frames.to(dev).contiguous()
-        host = []
-        for fr in frames:
-            a = np.asarray(fr)
-            if a.dtype != np.uint8:
-                raise TypeError(f"frames must be uint8, got {a.dtype}")
-            if a.ndim == 2:
-                a = a[:, :, None]
-            if a.ndim != 3 or a.shape[2] not in (1, 3):
-                raise ValueError(f"a frame must be [H, W] or [H, W, C] with C = 1 or 3 (PIL mode L or RGB: convert RGBA or palette "
-                                 f"frames with .convert('RGB') first), got {a.shape}" + (f" from PIL mode {fr.mode}" if hasattr(fr, "mode") else ""))
-            host.append(a)
-        if not host:
-            raise ValueError("no frames")
-        if any(a.shape != host[0].shape for a in host):
-            raise ValueError("all frames of a call must share one size")
-        self._check_size(host[0].shape[0], host[0].shape[1])
-        dev = self._device()
-        stack = np.stack(host)
-        if stack.shape[3] == 1:
-            stack = np.repeat(stack, 3, axis=3)
-        return torch.from_numpy(stack).to(dev)
 
     # ---- the chain -------------------------------------------------------------------------------------------------------------
     def _network(self, src, ws, i0: int) -> None:
@@ -496,14 +438,7 @@ class OpenposeAnnotator:
         n = src.shape[0]
         g = ws["geometry"]
         plan = BufferPlan(ws, self.dtype, src.device)
-        take, give = plan.take, plan.give
-
-        def timed(name, fn, *args, **kw):
-            ev = self._stage(name)
-            out = fn(*args, **kw)
-            if ev:
-                ev[1].record()
-            return out
+        take, give, timed = plan.take, plan.give, self._timed
 
         def conv3(x, wb):
             # split_k=False: the order of an output's sum is then the same whatever the number of frames
@@ -583,10 +518,7 @@ class OpenposeAnnotator:
         ws["chunk"] = max(ws.get("chunk", 0), min(step, n)) if ws["planned"] else min(step, n)
         for i0 in range(0, n, step):
             self._network(src[i0:i0 + step], ws, i0)
-        ev = self._stage("maps")
-        K.pose_maps(ws["low"], ws["mx"], ws["my"], ws["raw"], ws["smooth"], ws["paf"], ws["maps_ws"])
-        if ev:
-            ev[1].record()
+        self._timed("maps", K.pose_maps, ws["low"], ws["mx"], ws["my"], ws["raw"], ws["smooth"], ws["paf"], ws["maps_ws"])
         if decode:
             K.pose_decode(ws["raw"], ws["smooth"], ws["paf"], ws["decode"], stage=self._stage)
         drawn = skeleton is not None or control is not None
@@ -669,36 +601,12 @@ class OpenposeAnnotator:
         """frames: a list of PIL images / uint8 arrays of one size, or a uint8 tensor [n, H, W, C] (no host copy when it is on the
         device) -> uint8 device tensor [n, H, W, 3] (RGB: the detector's drawing on black, with the face dots when there is a face
         network), written into `out` when given."""
-        import torch
-        src = self._frames(frames)
-        n, h, w, _ = src.shape
-        if out is None:
-            out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=src.device)
-        elif out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w, 3) or out.device != src.device or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous uint8 tensor {(n, h, w, 3)} on {src.device}")
-        if n:
-            self._run(src, out, None, 1)
-        return out
-
-    def annotate_batch(self, frames, out=None, rep: int = 1, dtype=None):
-        """-> the control tensor [rep * n, 3, H, W] on the device, skeleton / 255 in RGB order; rep = 2 writes the n frames twice
-        (torch.cat([ctrl] * 2) of classifier-free guidance).  Written into `out` (and `out` returned) when given."""
-        import torch
-        if rep not in (1, 2):
-            raise ValueError(f"rep={rep} (1 or 2)")
-        want = out.dtype if out is not None and dtype is None else (dtype if dtype is not None else torch.float32)
-        if want not in (torch.float32, torch.float16):
-            raise TypeError(f"the control tensor is float32 or float16, got {want}")
-        src = self._frames(frames)
-        n, h, w, _ = src.shape
-        if out is None:
-            out = torch.empty((rep * n, 3, h, w), dtype=want, device=src.device)
-        elif tuple(out.shape) != (rep * n, 3, h, w) or out.device != src.device or not out.is_contiguous() or out.dtype != want:
-            raise ValueError(f"out must be a contiguous {want} tensor {(rep * n, 3, h, w)} on {src.device}")
-        if n:
-            self._run(src, None, out, rep)
-        return out
+        return self._uint8_out(frames, out, channels_last=3)
 
     def __call__(self, image):
+        try:
+            from PIL import Image
+        except Exception:  # pragma: no cover
+            Image = None
         rgb = self.skeleton([image])[0].cpu().numpy()
         return Image.fromarray(rgb) if Image is not None and not isinstance(image, np.ndarray) else rgb

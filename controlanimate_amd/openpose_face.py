@@ -52,6 +52,10 @@ import os
 
 import numpy as np
 
+from . import openpose as _body
+from .annotator_base import check_state_dict, device_weights, load_state_dict
+from .openpose import bare_keys  # noqa: F401  (one function for the three checkpoints)
+
 WEIGHTS_NAME = "facenet.pth"
 FACE_SIZE, FACE_HEAT, FACE_PARTS, FACE_MAPS, MIN_SIDE, TAPS = 384, 48, 71, 72, 11, 8
 SPAN_ROWS = 13   # source rows under two output rows that ca_face_crop keeps in LDS (kRowsIn)
@@ -86,41 +90,9 @@ def face_key_shapes() -> dict:
     return out
 
 
-def bare_keys(sd) -> dict:
-    """The checkpoint under its bare layer names: 'model1_0.conv1_1.weight' / 'model3.Mconv1_stage3.weight' lose the module prefix."""
-    return {k.split(".", 1)[1] if k.startswith("model") and k.count(".") >= 2 else k: v for k, v in sd.items()}
-
-
 def check_face_state_dict(sd) -> None:
     """KeyError naming a missing tensor, ValueError naming one that is unexpected or has the wrong shape (bare names)."""
-    want = face_key_shapes()
-    for k in want:
-        if k not in sd:
-            raise KeyError(f"openpose face state dict: '{k}' is missing ({len(want)} tensors expected: the layers of FaceNet)")
-    for k in sd:
-        if k not in want:
-            raise ValueError(f"openpose face state dict: unexpected tensor '{k}'")
-    for k, shape in want.items():
-        if tuple(sd[k].shape) != shape:
-            raise ValueError(f"openpose face state dict: '{k}' has shape {tuple(sd[k].shape)}, expected {shape}")
-
-
-def weights_path(path) -> str:
-    path = os.fspath(path)
-    if os.path.isdir(path):
-        path = os.path.join(path, WEIGHTS_NAME)
-    if not os.path.isfile(path):
-        raise FileNotFoundError(f"{path}: no such file (a local {WEIGHTS_NAME}, or a directory that holds it; nothing is ever downloaded)")
-    return path
-
-
-def load_face_state_dict(path) -> dict:
-    import torch
-    path = weights_path(path)
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    if not isinstance(sd, dict):
-        raise ValueError(f"{path}: not a state dict")
-    return sd
+    check_state_dict(sd, face_key_shapes(), "openpose face", "the layers of FaceNet")
 
 
 # ---- the resize choice on the host (what ca_face_boxes writes into a slot) --------------------------------------------------------------
@@ -229,36 +201,11 @@ def pixel_map(side: int) -> np.ndarray:
 # ---- packing -----------------------------------------------------------------------------------------------------------------------------
 def pack_mconv1(w):
     """Mconv1's weight [128, 199, 7, 7] on input channels [heat 71 | features 128] -> [128, 7, 7, 224] on [features 128 | heat 71, 25 zeros]."""
-    import torch
-    z = torch.zeros((w.shape[0], CAT, 7, 7), dtype=w.dtype)
-    z[:, 0:128], z[:, 128:128 + FACE_PARTS] = w[:, FACE_PARTS:FACE_PARTS + 128], w[:, 0:FACE_PARTS]
-    return z.permute(0, 2, 3, 1).contiguous()
+    return _body.pack_mconv1(w, ((FACE_PARTS, CAT - 128),))
 
 
 def pack_face_weights(sd, dtype) -> dict:
-    import torch
-    F = torch.nn.functional
-
-    def wb(name):
-        return sd[name + ".weight"].detach().float(), sd[name + ".bias"].detach().float().contiguous()
-
-    def conv(name, pad_in=0):  # [Cout, Cin, k, k] -> [Cout, k, k, Cin (+ pad_in zero channels)]
-        w, b = wb(name)
-        return F.pad(w, (0, 0, 0, 0, 0, pad_in)).permute(0, 2, 3, 1).contiguous().to(dtype), b
-
-    def lin(name, pad_out=0):  # [Cout, Cin, 1, 1] -> [Cout + pad_out zero rows, Cin]
-        w, b = wb(name)
-        return F.pad(w.reshape(w.shape[0], -1), (0, 0, 0, pad_out)).contiguous().to(dtype), F.pad(b, (0, pad_out)).contiguous()
-
-    def mconv1(name):
-        w, b = wb(name)
-        return pack_mconv1(w).to(dtype), b
-
-    pad = FACE_MAPS - FACE_PARTS
-    return {"front": [None if l == "pool" else conv(l[0], 5 if l[0] == "conv1_1" else 0) for l in FRONT],
-            "stage1": {"fc": lin("conv6_1_CPM"), "out": lin("conv6_2_CPM", pad)},
-            "stages": [{"conv7": [mconv1(f"Mconv1_stage{t}")] + [conv(f"Mconv{i}_stage{t}") for i in (2, 3, 4, 5)],
-                        "fc": lin(f"Mconv6_stage{t}"), "out": lin(f"Mconv7_stage{t}", pad)} for t in range(2, 7)]}
+    return _body.pack_crop_cpm_weights(sd, dtype, FRONT, FACE_PARTS, FACE_MAPS, CAT - 128)
 
 
 class FaceStage:
@@ -268,7 +215,7 @@ class FaceStage:
     def __init__(self, owner, state_dict_or_path, max_faces: int = 2):
         if not 1 <= int(max_faces) <= 64:
             raise ValueError(f"max_faces={max_faces} (1 .. 64)")
-        sd = load_face_state_dict(state_dict_or_path) if isinstance(state_dict_or_path, (str, os.PathLike)) else state_dict_or_path
+        sd = load_state_dict(state_dict_or_path, WEIGHTS_NAME) if isinstance(state_dict_or_path, (str, os.PathLike)) else state_dict_or_path
         sd = bare_keys(sd)
         check_face_state_dict(sd)
         self.owner, self.max_faces = owner, int(max_faces)
@@ -276,21 +223,7 @@ class FaceStage:
         self._dev = None
         self._ws = {}
 
-    def _weights(self, dev):
-        import torch
-
-        def move(o):
-            if o is None:
-                return None
-            if isinstance(o, torch.Tensor):
-                return o.to(dev)
-            if isinstance(o, dict):
-                return {k: move(v) for k, v in o.items()}
-            return type(o)(move(v) for v in o)
-
-        if self._dev is None or self._dev["stage1"]["fc"][1].device != dev:
-            self._dev = move(self._host)
-        return self._dev
+    _weights = device_weights
 
     def chunk_crops(self, direct: bool) -> int:
         """Crops per pass through the network: as many as keep the largest 16-bit operand (conv1's output, or the im2col tensor of the
@@ -319,65 +252,12 @@ class FaceStage:
     def _network(self, src, ws, c0: int, nc: int, direct: bool) -> None:
         """Crops c0 .. c0 + nc - 1 of the frames `src`: the resized input and the network, the 72 maps into ws["heat"][c0 : c0 + nc]."""
         from . import kernels as K
-        from .openpose import BufferPlan
-        owner = self.owner
-        wts = self._weights(src.device)
-        plan = BufferPlan(ws, owner.dtype, src.device)   # the body's buffer plan: the same buffers in the same order on every pass
-        take, give = plan.take, plan.give
 
-        def timed(name, fn, *args, **kw):
-            ev = owner._stage(name)
-            out = fn(*args, **kw)
-            if ev:
-                ev[1].record()
-            return out
+        def crop(out):
+            return K.face_crop(src, ws["buf"]["slots"], ws["tables"], out, first=c0)
 
-        def pw(x2d, wb, act, out2d, out_f32=False):
-            timed("face_pointwise", K.gemm, x2d, wb[0], bias=wb[1], act=act, out=out2d, out_f32=out_f32)
-
-        x = timed("face_crop", K.face_crop, src, ws["buf"]["slots"], ws["tables"], take(nc, FACE_SIZE, FACE_SIZE, 8), first=c0)
-        for layer, wb in zip(FRONT, wts["front"]):
-            if layer == "pool":
-                y = timed("face_pool", K.maxpool2x2, x, take(nc, x.shape[1] // 2, x.shape[2] // 2, x.shape[3]))
-            else:   # split_k=False: the order of an output's sum is then the same whatever the number of crops
-                y = timed("face_conv", K.conv3x3, x, wb[0], bias=wb[1], act=K.ACT_RELU, out=take(*x.shape[:3], wb[0].shape[0]), split_k=False)
-            give(x)
-            x = y
-        feat = x
-        hl = FACE_HEAT
-        rows = nc * hl * hl
-        cat = take(nc, hl, hl, CAT)
-        cat2d = cat.view(rows, CAT)
-        cat2d.zero_()   # columns 200 .. 223 are read (against zero weights) and never written
-        timed("face_copy", K.copy_cols, feat.view(rows, 128), cat2d, 0)
-        heat_cols = cat2d[:, 128:128 + FACE_MAPS]
-        fc = take(rows, 512)
-        pw(feat.view(rows, 128), wts["stage1"]["fc"], K.ACT_RELU, fc)
-        give(feat)
-        pw(fc, wts["stage1"]["out"], K.ACT_NONE, heat_cols)
-        give(fc)
-        cols = None if direct else take(rows, 49 * CAT)
-        out2d = ws["heat"][c0:c0 + nc].view(rows, FACE_MAPS)
-        for t, stage in enumerate(wts["stages"]):
-            a = cat
-            for i in range(5):
-                y = take(nc, hl, hl, 128)
-                timed("face_conv7", K.conv7x7, [a], [stage["conv7"][i][0]], biases=[stage["conv7"][i][1]], relu=True, outs=[y], direct=direct, cols=cols)
-                if i:
-                    give(a)
-                a = y
-            fc = take(rows, 128)
-            pw(a.view(rows, 128), stage["fc"], K.ACT_RELU, fc)
-            give(a)
-            if t == len(wts["stages"]) - 1:
-                pw(fc, stage["out"], K.ACT_NONE, out2d, out_f32=True)
-            else:
-                pw(fc, stage["out"], K.ACT_NONE, heat_cols)
-            give(fc)
-        if cols is not None:
-            give(cols)
-        give(cat)
-        ws["planned"] = True
+        _body.crop_cpm_network(self.owner, ws, self._weights(src.device), "face", FRONT, crop, nc, FACE_SIZE, FACE_HEAT, CAT,
+                               ws["heat"][c0:c0 + nc].view(nc * FACE_HEAT * FACE_HEAT, FACE_MAPS), direct)
 
     def run(self, src, keypoints, people, overflow_in=None, direct: bool = True) -> dict:
         """frames uint8 [n, H, W, 3] on the device, keypoints int32 [n, 64, 18, 2], people int32 [n] (and the body's overflow int32 [n]) ->
@@ -392,14 +272,8 @@ class FaceStage:
             ws["pool"], ws["plan"], ws["planned"] = [], [], False   # the other form of the 7x7 convolutions, or a larger chunk than was planned
         ws["direct"] = bool(direct)
         ws["chunk"] = max(ws.get("chunk", 0), min(step, total)) if ws["planned"] else min(step, total)
-        ev = owner._stage("face_boxes")
-        K.face_boxes(keypoints, people, h, w, ws["buf"], overflow_in)
-        if ev:
-            ev[1].record()
+        owner._timed("face_boxes", K.face_boxes, keypoints, people, h, w, ws["buf"], overflow_in)
         for c0 in range(0, total, step):
             self._network(src, ws, c0, min(step, total - c0), direct)
-        ev = owner._stage("face_peaks")
-        K.face_peaks(ws["heat"], ws["buf"]["slots"], ws["buf"]["points"], h, w)
-        if ev:
-            ev[1].record()
+        owner._timed("face_peaks", K.face_peaks, ws["heat"], ws["buf"]["slots"], ws["buf"]["points"], h, w)
         return ws

@@ -54,7 +54,10 @@ import os
 
 import numpy as np
 
-from .openpose_face import FRONT, bare_keys, pixel_map
+from . import openpose as _body
+from .annotator_base import check_state_dict, device_weights, load_state_dict
+from .openpose import bare_keys
+from .openpose_face import FRONT, pixel_map
 
 WEIGHTS_NAME = "hand_pose_model.pth"
 HAND_PARTS, HAND_MAPS, HEAT_COLS, MAP_SIZE, MIN_BOX = 21, 22, 24, 128, 20
@@ -90,34 +93,11 @@ def hand_key_shapes() -> dict:
 
 def check_hand_state_dict(sd) -> None:
     """KeyError naming a missing tensor, ValueError naming one that is unexpected or has the wrong shape (bare names)."""
-    want = hand_key_shapes()
-    for k in want:
-        if k not in sd:
-            raise KeyError(f"openpose hand state dict: '{k}' is missing ({len(want)} tensors expected: the layers of handpose_model)")
-    for k in sd:
-        if k not in want:
-            raise ValueError(f"openpose hand state dict: unexpected tensor '{k}'")
-    for k, shape in want.items():
-        if tuple(sd[k].shape) != shape:
-            raise ValueError(f"openpose hand state dict: '{k}' has shape {tuple(sd[k].shape)}, expected {shape}")
-
-
-def weights_path(path) -> str:
-    path = os.fspath(path)
-    if os.path.isdir(path):
-        path = os.path.join(path, WEIGHTS_NAME)
-    if not os.path.isfile(path):
-        raise FileNotFoundError(f"{path}: no such file (a local {WEIGHTS_NAME}, or a directory that holds it; nothing is ever downloaded)")
-    return path
+    check_state_dict(sd, hand_key_shapes(), "openpose hand", "the layers of handpose_model")
 
 
 def load_hand_state_dict(path) -> dict:
-    import torch
-    path = weights_path(path)
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    if not isinstance(sd, dict):
-        raise ValueError(f"{path}: not a state dict")
-    return sd
+    return load_state_dict(path, WEIGHTS_NAME)
 
 
 # ---- the resize choice on the host -------------------------------------------------------------------------------------------------------
@@ -188,36 +168,11 @@ def hand_colors() -> np.ndarray:
 # ---- packing -----------------------------------------------------------------------------------------------------------------------------
 def pack_mconv1(w):
     """Mconv1's weight [128, 150, 7, 7] on input channels [heat 22 | features 128] -> [128, 7, 7, 160] on [features 128 | heat 22, 10 zeros]."""
-    import torch
-    z = torch.zeros((w.shape[0], CAT, 7, 7), dtype=w.dtype)
-    z[:, 0:128], z[:, 128:128 + HAND_MAPS] = w[:, HAND_MAPS:HAND_MAPS + 128], w[:, 0:HAND_MAPS]
-    return z.permute(0, 2, 3, 1).contiguous()
+    return _body.pack_mconv1(w, ((HAND_MAPS, CAT - 128),))
 
 
 def pack_hand_weights(sd, dtype) -> dict:
-    import torch
-    F = torch.nn.functional
-
-    def wb(name):
-        return sd[name + ".weight"].detach().float(), sd[name + ".bias"].detach().float().contiguous()
-
-    def conv(name, pad_in=0):  # [Cout, Cin, k, k] -> [Cout, k, k, Cin (+ pad_in zero channels)]
-        w, b = wb(name)
-        return F.pad(w, (0, 0, 0, 0, 0, pad_in)).permute(0, 2, 3, 1).contiguous().to(dtype), b
-
-    def lin(name, pad_out=0):  # [Cout, Cin, 1, 1] -> [Cout + pad_out zero rows, Cin]
-        w, b = wb(name)
-        return F.pad(w.reshape(w.shape[0], -1), (0, 0, 0, pad_out)).contiguous().to(dtype), F.pad(b, (0, pad_out)).contiguous()
-
-    def mconv1(name):
-        w, b = wb(name)
-        return pack_mconv1(w).to(dtype), b
-
-    pad = HEAT_COLS - HAND_MAPS
-    return {"front": [None if l == "pool" else conv(l[0], 5 if l[0] == "conv1_1" else 0) for l in FRONT],
-            "stage1": {"fc": lin("conv6_1_CPM"), "out": lin("conv6_2_CPM", pad)},
-            "stages": [{"conv7": [mconv1(f"Mconv1_stage{t}")] + [conv(f"Mconv{i}_stage{t}") for i in (2, 3, 4, 5)],
-                        "fc": lin(f"Mconv6_stage{t}"), "out": lin(f"Mconv7_stage{t}", pad)} for t in range(2, 7)]}
+    return _body.pack_crop_cpm_weights(sd, dtype, FRONT, HAND_MAPS, HEAT_COLS, CAT - 128)
 
 
 # ---- the crop's tables -------------------------------------------------------------------------------------------------------------------
@@ -265,21 +220,7 @@ class HandStage:
         self._dev = None
         self._ws = {}
 
-    def _weights(self, dev):
-        import torch
-
-        def move(o):
-            if o is None:
-                return None
-            if isinstance(o, torch.Tensor):
-                return o.to(dev)
-            if isinstance(o, dict):
-                return {k: move(v) for k, v in o.items()}
-            return type(o)(move(v) for v in o)
-
-        if self._dev is None or self._dev["stage1"]["fc"][1].device != dev:
-            self._dev = move(self._host)
-        return self._dev
+    _weights = device_weights
 
     def chunk_crops(self, side: int, direct: bool) -> int:
         """Crops per pass through the network at one side: as many as keep the largest 16-bit operand (conv1's output -- 69 MB a crop at
@@ -312,66 +253,13 @@ class HandStage:
     def _network(self, src, ws, k: int, c0: int, nc: int, direct: bool, blur: bool) -> None:
         """Crops c0 .. c0 + nc - 1 at side SIDES[k]: the blurred, resized input and the network, the 24 map columns into ws["heat"][k]."""
         from . import kernels as K
-        from .openpose import BufferPlan
-        owner = self.owner
-        wts = self._weights(src.device)
-        net = ws["net"][k]
-        plan = BufferPlan(net, owner.dtype, src.device)   # the body's buffer plan: the same buffers in the same order on every pass
-        take, give = plan.take, plan.give
         side, hl = SIDES[k], MAP_SIDES[k]
 
-        def timed(name, fn, *args, **kw):
-            ev = owner._stage(name)
-            out = fn(*args, **kw)
-            if ev:
-                ev[1].record()
-            return out
+        def crop(out):
+            return K.hand_crop(src, ws["buf"]["slots"], ws["tables"][k], ws["blurred"], out, first=c0, blur=blur)
 
-        def pw(x2d, wb, act, out2d, out_f32=False):
-            timed("hand_pointwise", K.gemm, x2d, wb[0], bias=wb[1], act=act, out=out2d, out_f32=out_f32)
-
-        x = timed("hand_crop", K.hand_crop, src, ws["buf"]["slots"], ws["tables"][k], ws["blurred"], take(nc, side, side, 8), first=c0, blur=blur)
-        for layer, wb in zip(FRONT, wts["front"]):
-            if layer == "pool":
-                y = timed("hand_pool", K.maxpool2x2, x, take(nc, x.shape[1] // 2, x.shape[2] // 2, x.shape[3]))
-            else:   # split_k=False: the order of an output's sum is then the same whatever the number of crops
-                y = timed("hand_conv", K.conv3x3, x, wb[0], bias=wb[1], act=K.ACT_RELU, out=take(*x.shape[:3], wb[0].shape[0]), split_k=False)
-            give(x)
-            x = y
-        feat = x
-        rows = nc * hl * hl
-        cat = take(nc, hl, hl, CAT)
-        cat2d = cat.view(rows, CAT)
-        cat2d.zero_()   # columns 152 .. 159 are read (against zero weights) and never written
-        timed("hand_copy", K.copy_cols, feat.view(rows, 128), cat2d, 0)
-        heat_cols = cat2d[:, 128:128 + HEAT_COLS]
-        fc = take(rows, 512)
-        pw(feat.view(rows, 128), wts["stage1"]["fc"], K.ACT_RELU, fc)
-        give(feat)
-        pw(fc, wts["stage1"]["out"], K.ACT_NONE, heat_cols)
-        give(fc)
-        cols = None if direct else take(rows, 49 * CAT)
-        out2d = ws["heat"][k][c0:c0 + nc].view(rows, HEAT_COLS)
-        for t, stage in enumerate(wts["stages"]):
-            a = cat
-            for i in range(5):
-                y = take(nc, hl, hl, 128)
-                timed("hand_conv7", K.conv7x7, [a], [stage["conv7"][i][0]], biases=[stage["conv7"][i][1]], relu=True, outs=[y], direct=direct, cols=cols)
-                if i:
-                    give(a)
-                a = y
-            fc = take(rows, 128)
-            pw(a.view(rows, 128), stage["fc"], K.ACT_RELU, fc)
-            give(a)
-            if t == len(wts["stages"]) - 1:
-                pw(fc, stage["out"], K.ACT_NONE, out2d, out_f32=True)
-            else:
-                pw(fc, stage["out"], K.ACT_NONE, heat_cols)
-            give(fc)
-        if cols is not None:
-            give(cols)
-        give(cat)
-        net["planned"] = True
+        _body.crop_cpm_network(self.owner, ws["net"][k], self._weights(src.device), "hand", FRONT, crop, nc, side, hl, CAT,
+                               ws["heat"][k][c0:c0 + nc].view(nc * hl * hl, HEAT_COLS), direct)
 
     def run(self, src, keypoints, people, overflow_in=None, direct: bool = True) -> dict:
         """frames uint8 [n, H, W, 3] on the device, keypoints int32 [n, 64, 18, 2], people int32 [n] (and the overflow so far, int32 [n]) ->
@@ -381,10 +269,7 @@ class HandStage:
         n, h, w, _ = src.shape
         ws = self.workspace(n, h, w, src.device)
         total = n * self.max_hands
-        ev = owner._stage("hand_boxes")
-        K.hand_boxes(keypoints, people, h, w, ws["buf"], overflow_in)
-        if ev:
-            ev[1].record()
+        owner._timed("hand_boxes", K.hand_boxes, keypoints, people, h, w, ws["buf"], overflow_in)
         for k in reversed(range(len(SIDES))):   # the largest side first: it blurs the crops, and its buffers serve the smaller sides
             net, step = ws["net"][k], self.chunk_crops(SIDES[k], direct)
             if net["planned"] and (bool(net.get("direct", True)) != bool(direct) or min(step, total) > net.get("chunk", 0)):
@@ -393,12 +278,6 @@ class HandStage:
             net["chunk"] = max(net.get("chunk", 0), min(step, total)) if net["planned"] else min(step, total)
             for c0 in range(0, total, step):
                 self._network(src, ws, k, c0, min(step, total - c0), direct, blur=k == len(SIDES) - 1)
-        ev = owner._stage("hand_maps")
-        K.hand_maps(ws["heat"], ws["mats"], ws["buf"]["raw"], ws["buf"]["smooth"])
-        if ev:
-            ev[1].record()
-        ev = owner._stage("hand_peaks")
-        K.hand_peaks(ws["buf"]["raw"], ws["buf"]["smooth"], ws["buf"], h, w)
-        if ev:
-            ev[1].record()
+        owner._timed("hand_maps", K.hand_maps, ws["heat"], ws["mats"], ws["buf"]["raw"], ws["buf"]["smooth"])
+        owner._timed("hand_peaks", K.hand_peaks, ws["buf"]["raw"], ws["buf"]["smooth"], ws["buf"], h, w)
         return ws
