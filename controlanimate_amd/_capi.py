@@ -17,6 +17,7 @@ CA_ACT_NONE, CA_ACT_SILU = 0, 1
 CA_ACT_RELU = 4  # the VGG stack of the HED annotator (hed.py)
 CA_ACT_RELU6 = 5  # the MobileNetV2 backbone of the M-LSD annotator (mlsd.py)
 CA_ACT_LEAKY02 = 6  # LeakyReLU(0.2): the U-Net and the SFT branches of the GFPGAN face restorer (gfpgan.py)
+CA_ACT_LEAKY001 = 7  # LeakyReLU(0.01): the decoder of the NormalBae annotator (normalbae.py)
 CA_MLSD_TOPK = 200
 CA_POSE_MAX_PEAKS, CA_POSE_MAX_PEOPLE, CA_POSE_AREA_TAPS = 64, 64, 8  # the OpenPose annotator (openpose.py)
 CA_POSE_OVERFLOW_PEAKS, CA_POSE_OVERFLOW_PEOPLE = 1, 2
@@ -349,6 +350,16 @@ SYMBOLS = {
     "ca_hand_maps": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] + [C.c_void_p]),
     "ca_hand_peaks": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_void_p]),
     "ca_pose_draw_hands": (C.c_int, [C.c_void_p] * 10 + [C.c_int32] * 5 + [C.c_void_p]),
+    # added to ABI v16 likewise: the NormalBae annotator's stages beside ca_gemm / ca_conv3x3 / ca_upsample2x_bilinear_ac (controlanimate_amd/normalbae.py)
+    "ca_nbae_stem": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p]),
+    "ca_dwconv_same_partials_floats": (C.c_int64, [C.c_int32] * 5),
+    "ca_dwconv_same": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 7 + [C.c_void_p]),
+    "ca_se_gate": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_float, C.c_void_p]),
+    "ca_scale_channels": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "ca_nbae_cat_pred": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "ca_nbae_normalize": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
+    "ca_nbae_refine": (C.c_int, [C.c_void_p] * 11 + [C.c_int32] * 4 + [C.c_float, C.c_int32, C.c_void_p]),
+    "ca_nbae_finish": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
 }
 
 _lib = None

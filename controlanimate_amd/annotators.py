@@ -28,6 +28,9 @@ device from a local body_pose_model.pth, opt-in through `annotators={"openpose":
 control_v11p_sd15_openpose and sd-controlnet-openpose alike).  Given a face network (`face=<facenet.pth>`) it also draws the face
 keypoints of the reference's hand_and_face=True (openpose_face.py); without one it draws the BODY skeleton only.  Given a hand network
 (`hand=<hand_pose_model.pth>`) it draws the hands too (openpose_hand.py); with both, the drawing is the reference's hand_and_face=True.
+So is normalbae, the last of the reference's nine branches: `NormalBaeAnnotator` (normalbae.py, re-exported here) runs the EfficientNet-B5
+encoder, the decoder and the per-pixel refinement stages of controlnet_aux's NormalBaeDetector from a local scannet.pt, opt-in through
+`annotators={"normalbae": NormalBaeAnnotator.from_pretrained(path)}`; its encoder is pinned against transformers' EfficientNetModel.
 (The face restorer of the emitted frames is not an annotator and lives in gfpgan.py: GFPGANv1Clean for aligned 512 x 512 faces on the HIP
 kernels, around a caller-supplied helper for detection, warp and paste-back; UNPINNED against gfpgan and real weights; no CPU fallback.)
 
@@ -51,6 +54,7 @@ from .lineart_anime import LineartAnimeAnnotator  # noqa: E402,F401  (the learne
 from .mlsd import MlsdAnnotator  # noqa: E402,F401  (the learned straight-line detector on the GPU, likewise)
 from .softedge import SoftedgeAnnotator  # noqa: E402,F401  (the learned soft-edge detector on the GPU, likewise)
 from .openpose import OpenposeAnnotator  # noqa: E402,F401  (the learned body-pose detector on the GPU, likewise)
+from .normalbae import NormalBaeAnnotator  # noqa: E402,F401  (the learned surface-normal detector on the GPU, likewise)
 
 
 def __getattr__(name):

@@ -49,6 +49,7 @@ class Dispatch:
     pdc_block_fused = True  # ca_pdc_block for the C = 64 blocks of the softedge annotator (else ca_dwconv_k + ca_gemm with the skip as its residual)
     dpt_head_fused = False  # ca_dpt_head (one launch, the upsampled plane never written) for the tail of the depth annotator's head; off: the composed form (ca_upsample2x_bilinear_ac + ca_conv3x3 + ca_dpt_logit) is 2.5x faster at 192^2 -> 384^2 x 128 channels (tools/bench_depth.py, profiles/depth_bench.json)
     pose_conv7_direct = True  # ca_conv7x7 (the implicit GEMM from an LDS halo tile) for the 7x7 convolutions of the OpenPose annotator's refinement stages; off: ca_im2col7x7 + ca_gemm (tools/bench_openpose.py)
+    nbae_refine_fused = True  # ca_nbae_refine (one launch per refinement stage of the NormalBae annotator, hidden activations in LDS) where C is 128, 256 or 512; off: the composed form (ca_upsample2x_bilinear_ac + ca_nbae_cat_pred + 4 ca_gemm + ca_nbae_normalize) (tools/bench_normalbae.py, profiles/normalbae_bench.json)
     controlnet_streams = 2  # HIP streams the bodies of a stack of >= 3 ControlNets are spread over (independent up to the summed residuals)
 
 

@@ -24,7 +24,9 @@ through `annotators={"depth": DepthAnnotator.from_pretrained(local_dir)}` (contr
 and control_v11f1p_sd15_depth), and openpose, the first ControlNet of three sample configs, from the user's body_pose_model.pth through
 `annotators={"openpose": OpenposeAnnotator.from_pretrained(path)}` (controlanimate_amd/openpose.py; the key serves
 control_v11p_sd15_openpose and sd-controlnet-openpose; the body skeleton, and with `face=<facenet.pth>` the face keypoints of the
-reference's hand_and_face=True -- and with `hand=<hand_pose_model.pth>` its hands).  For any other net pass already-annotated control images, or plug a callable in through `annotators`.  Of the keys contained in a ControlNet's name the longest wins (the reference tests `lineart_anime` before
+reference's hand_and_face=True -- and with `hand=<hand_pose_model.pth>` its hands), and normalbae, the IP-Adapter sample config's
+control_v11p_sd15_normalbae, from the user's scannet.pt through `annotators={"normalbae": NormalBaeAnnotator.from_pretrained(path)}`
+(controlanimate_amd/normalbae.py).  For any other net pass already-annotated control images, or plug a callable in through `annotators`.  Of the keys contained in a ControlNet's name the longest wins (the reference tests `lineart_anime` before
 `lineart`): a `lineart` annotator never serves a `lineart_anime` net.
 """
 from __future__ import annotations

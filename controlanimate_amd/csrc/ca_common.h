@@ -177,6 +177,7 @@ __device__ __forceinline__ float act_f(float x, int act) {
   if (act == CA_ACT_RELU) return fmaxf(x, 0.0f);
   if (act == CA_ACT_RELU6) return fminf(fmaxf(x, 0.0f), 6.0f);
   if (act == CA_ACT_LEAKY02) return x > 0.0f ? x : 0.2f * x;
+  if (act == CA_ACT_LEAKY001) return x > 0.0f ? x : 0.01f * x;
   return x;
 }
 

@@ -2103,3 +2103,152 @@ def pose_draw_hands(coords: torch.Tensor, people: torch.Tensor, sin_table: torch
     check(lib().ca_pose_draw_hands(_p(coords), _p(people), _p(sin_table), _p(hand_points), _p(face_points), _p(xmap), _p(ymap), _p(index), _p(skeleton), _p(control),
                                    n, h, w, int(rep), dt, _stream()), "ca_pose_draw_hands")
     return skeleton
+
+
+# ---- added to ABI v16: the NormalBae annotator's stages beside gemm / conv3x3 / upsample2x_bilinear_ac (controlanimate_amd/normalbae.py: NormalBaeAnnotator) ----
+ACT_LEAKY001 = _capi.CA_ACT_LEAKY001  # nn.LeakyReLU() (slope 0.01) in the epilogue of conv3x3 / gemm
+
+
+def same_out(size: int, stride: int) -> int:
+    """The output size of a TensorFlow-SAME convolution: ceil(size / stride)."""
+    return -(-size // stride)
+
+
+def nbae_stem(frames: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """uint8 RGB [images, H, W, 3] -> `out` [images, H/2, W/2, cout]: swish(Conv3x3 stride 2, SAME padding, of the ImageNet-normalised frame +
+    bias) (ca_nbae_stem).  wt: float32 [27, cout] (row (ky * 3 + kx) * 3 + channel, BatchNorm folded); bias: float32 [cout]."""
+    _req_cuda(frames, wt, bias, out)
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
+    n, h, w, _ = frames.shape
+    cout = out.shape[3]
+    assert wt.dtype == torch.float32 and tuple(wt.shape) == (27, cout) and wt.is_contiguous() and bias.dtype == torch.float32 and bias.numel() == cout
+    assert h % 2 == 0 and w % 2 == 0 and tuple(out.shape) == (n, h // 2, w // 2, cout) and out.is_contiguous()
+    check(lib().ca_nbae_stem(_p(frames), _p(wt), _p(bias), _p(out), n, h, w, cout, dt_code(out.dtype), _stream()), "ca_nbae_stem")
+    return out
+
+
+def dwconv_same_partials_floats(images: int, h: int, w: int, c: int, stride: int) -> int:
+    n = int(lib().ca_dwconv_same_partials_floats(images, h, w, c, stride))
+    if n <= 0:
+        raise _capi.CAHipError(f"ca_dwconv_same_partials_floats: images={images} h={h} w={w} c={c} stride={stride} out of range")
+    return n
+
+
+def dwconv_same(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, stride: int = 1, out: Optional[torch.Tensor] = None, sums: Optional[torch.Tensor] = None,
+                partials: Optional[torch.Tensor] = None):
+    """Depthwise k x k (3 or 5) convolution with TensorFlow-SAME padding + bias + swish of NHWC x [images, H, W, C] (ca_dwconv_same).
+    w: [k * k, C] of x's dtype (tap ky * k + kx of every channel), bias float32 [C].  -> (out [images, ceil(H / stride), ceil(W / stride), C],
+    sums float32 [images, C]: the sum over the plane of the stored values).  partials: float32 scratch of dwconv_same_partials_floats."""
+    _req_cuda(x, w, bias, out, sums, partials)
+    assert x.dim() == 4 and x.is_contiguous() and stride in (1, 2)
+    n, h, ww, c = x.shape
+    assert w.dim() == 2 and w.shape[0] in (9, 25) and w.shape[1] == c and w.is_contiguous() and w.dtype == x.dtype, "w: [9 or 25, C] of x's dtype"
+    assert bias.dtype == torch.float32 and bias.numel() == c and bias.is_contiguous()
+    ksize = 3 if w.shape[0] == 9 else 5
+    oshape = (n, same_out(h, stride), same_out(ww, stride), c)
+    if out is None:
+        out = torch.empty(oshape, dtype=x.dtype, device=x.device)
+    if sums is None:
+        sums = torch.empty((n, c), dtype=torch.float32, device=x.device)
+    need = dwconv_same_partials_floats(n, h, ww, c, stride)
+    if partials is None:
+        partials = torch.empty(need, dtype=torch.float32, device=x.device)
+    assert tuple(out.shape) == oshape and out.is_contiguous() and out.dtype == x.dtype
+    assert sums.dtype == torch.float32 and tuple(sums.shape) == (n, c) and sums.is_contiguous()
+    assert partials.dtype == torch.float32 and partials.numel() >= need and partials.is_contiguous()
+    check(lib().ca_dwconv_same(_p(x), _p(w), _p(bias), _p(out), _p(sums), _p(partials), n, h, ww, c, ksize, int(stride), dt_code(x.dtype), _stream()), "ca_dwconv_same")
+    return out, sums
+
+
+def se_gate(sums: torch.Tensor, w_reduce: torch.Tensor, b_reduce: torch.Tensor, w_expand_t: torch.Tensor, b_expand: torch.Tensor, pixels: int,
+            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gate float32 [images, C] = sigmoid(W_e swish(W_r (sums / pixels) + b_r) + b_e), all float32 (ca_se_gate).  w_reduce [r, C], b_reduce [r],
+    w_expand_t [r, C] (the expand weight transposed), b_expand [C]."""
+    _req_cuda(sums, w_reduce, b_reduce, w_expand_t, b_expand, out)
+    n, c = sums.shape
+    r = w_reduce.shape[0]
+    for t, shape in ((sums, (n, c)), (w_reduce, (r, c)), (b_reduce, (r,)), (w_expand_t, (r, c)), (b_expand, (c,))):
+        assert t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous()
+    if out is None:
+        out = torch.empty((n, c), dtype=torch.float32, device=sums.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (n, c) and out.is_contiguous()
+    check(lib().ca_se_gate(_p(sums), _p(w_reduce), _p(b_reduce), _p(w_expand_t), _p(b_expand), _p(out), n, c, r, 1.0 / float(pixels), _stream()), "ca_se_gate")
+    return out
+
+
+def scale_channels(x: torch.Tensor, gate: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """round(x * gate[image, channel]) for NHWC x and gate float32 [images, C]; out=x scales in place (ca_scale_channels)."""
+    _req_cuda(x, gate, out)
+    assert x.dim() == 4 and x.is_contiguous()
+    n, h, w, c = x.shape
+    assert gate.dtype == torch.float32 and tuple(gate.shape) == (n, c) and gate.is_contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and out.dtype == x.dtype and out.is_contiguous()
+    check(lib().ca_scale_channels(_p(x), _p(gate), _p(out), n, h * w, c, dt_code(x.dtype), _stream()), "ca_scale_channels")
+    return out
+
+
+def nbae_cat_pred(pred: torch.Tensor, out: torch.Tensor, col0: int = 0) -> torch.Tensor:
+    """The float32 prediction [images, h, w, 4], x2 bilinear with align_corners in float32, rounded into columns col0 .. col0 + 3 of `out`
+    [images, 2h, 2w, ld] and zeros into col0 + 4 .. col0 + 7 (ca_nbae_cat_pred)."""
+    _req_cuda(pred, out)
+    assert pred.dtype == torch.float32 and pred.dim() == 4 and pred.shape[3] == 4 and pred.is_contiguous()
+    n, h, w, _ = pred.shape
+    assert out.dim() == 4 and tuple(out.shape[:3]) == (n, 2 * h, 2 * w) and out.is_contiguous()
+    check(lib().ca_nbae_cat_pred(_p(pred), _p(out), n, h, w, out.shape[3], int(col0), dt_code(out.dtype), _stream()), "ca_nbae_cat_pred")
+    return out
+
+
+NBAE_MIN_KAPPA = 0.01
+
+
+def nbae_normalize(raw: torch.Tensor, out: torch.Tensor, min_kappa: float = NBAE_MIN_KAPPA) -> torch.Tensor:
+    """norm_normalize of the first four of raw's float32 columns [rows, ld] -> `out` float32 [rows, 4]: xyz / (|xyz| + 1e-10),
+    elu(kappa) + 1 + min_kappa (ca_nbae_normalize)."""
+    _req_cuda(raw, out)
+    assert raw.dtype == torch.float32 and raw.dim() == 2 and raw.is_contiguous() and raw.shape[1] % 4 == 0
+    assert out.dtype == torch.float32 and out.numel() == raw.shape[0] * 4 and out.is_contiguous()
+    check(lib().ca_nbae_normalize(_p(raw), raw.shape[1], _p(out), raw.shape[0], float(min_kappa), _stream()), "ca_nbae_normalize")
+    return out
+
+
+NBAE_REFINE_C = (128, 256, 512)   # the feature widths ca_nbae_refine is built for (hidden width 128)
+
+
+def nbae_refine(feat: torch.Tensor, pred: torch.Tensor, frags, biases, out: torch.Tensor, min_kappa: float = NBAE_MIN_KAPPA) -> torch.Tensor:
+    """One refinement stage in one launch (ca_nbae_refine): feat [images, h, w, C], C in NBAE_REFINE_C, and the float32 prediction
+    [images, h, w, 4] -> `out` float32 [images, 2h, 2w, 4].  frags: the four weight fragments of normalbae.pack_mlp_frag; biases: float32
+    [128] x 3 and [4]."""
+    _req_cuda(feat, pred, out, *frags, *biases)
+    assert feat.dim() == 4 and feat.is_contiguous() and feat.shape[3] in NBAE_REFINE_C
+    n, h, w, c = feat.shape
+    kp = (c + 8 + 31) // 32 * 32
+    assert pred.dtype == torch.float32 and tuple(pred.shape) == (n, h, w, 4) and pred.is_contiguous()
+    assert out.dtype == torch.float32 and tuple(out.shape) == (n, 2 * h, 2 * w, 4) and out.is_contiguous()
+    for f, elems in zip(frags, (128 * kp, 128 * 128, 128 * 128, 16 * 128)):
+        assert f.dtype == feat.dtype and f.numel() == elems and f.is_contiguous()
+    for b, elems in zip(biases, (128, 128, 128, 4)):
+        assert b.dtype == torch.float32 and b.numel() == elems and b.is_contiguous()
+    if _plan_sink is not None:
+        _plan_sink.append(f"nbae_refine_c{c}")
+    check(lib().ca_nbae_refine(_p(feat), _p(pred), *[_p(f) for f in frags], *[_p(b) for b in biases], _p(out), n, h, w, c, float(min_kappa), dt_code(feat.dtype),
+                               _stream()), "ca_nbae_refine")
+    return out
+
+
+def nbae_finish(pred: torch.Tensor, map: Optional[torch.Tensor] = None, control: Optional[torch.Tensor] = None, rep: int = 1) -> None:
+    """float32 prediction [images, H, W, 4] -> the uint8 map [images, H, W, 3] = trunc(clip(clip((xyz + 1) * 0.5, 0, 1) * 255, 0, 255)) and / or
+    the control tensor [rep * images, 3, H, W] (float32 / float16, map / 255) in one launch (ca_nbae_finish)."""
+    _req_cuda(pred, map, control)
+    assert pred.dtype == torch.float32 and pred.dim() == 4 and pred.shape[3] == 4 and pred.is_contiguous()
+    n, h, w, _ = pred.shape
+    if map is not None:
+        assert map.dtype == torch.uint8 and tuple(map.shape) == (n, h, w, 3) and map.is_contiguous()
+    dt = _capi.CA_F32
+    if control is not None:
+        if control.dtype not in _CANNY_DT:
+            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
+        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
+        dt = _CANNY_DT[control.dtype]
+    check(lib().ca_nbae_finish(_p(pred), n, h, w, _p(map), _p(control), int(rep), dt, _stream()), "ca_nbae_finish")

@@ -47,6 +47,7 @@ extern "C" {
 #define CA_ACT_RELU 4       /* max(x, 0): the VGG stack of the HED annotator (added to ABI v16) */
 #define CA_ACT_RELU6 5      /* min(max(x, 0), 6): the MobileNetV2 backbone of the M-LSD annotator (added to ABI v16) */
 #define CA_ACT_LEAKY02 6    /* x > 0 ? x : 0.2 x: the U-Net and the SFT branches of the GFPGAN face restorer (added to ABI v16) */
+#define CA_ACT_LEAKY001 7   /* x > 0 ? x : 0.01 x: nn.LeakyReLU() of the NormalBae decoder (added to ABI v16) */
 
 int ca_abi_version(void);
 const char* ca_last_error(void);
@@ -1323,6 +1324,55 @@ int ca_hand_peaks(const float* raw, const float* smooth, const int32_t* slots, i
 int ca_pose_draw_hands(const int32_t* coords, const int32_t* people, const float* sin_table, const int32_t* hand_points, const int32_t* face_points,
                        const int32_t* xmap, const int32_t* ymap, uint32_t* index, uint8_t* map, void* control, int32_t images, int32_t h, int32_t w, int32_t rep,
                        int32_t control_dtype, void* stream);
+
+/* ---- added to ABI v16 likewise: the NormalBae annotator's stages beside ca_gemm / ca_conv3x3 / ca_upsample2x_bilinear_ac
+ * (controlanimate_amd/normalbae.py; csrc/ca_normalbae.hip).  Tensors are NHWC of dtype CA_F16 / CA_BF16 with fp32 accumulation; no entry
+ * point reads device data on the host or uses floating-point atomics: two runs give the same bits.  Anything out of range is
+ * CA_ERR_INVALID_ARG before any launch. ---- */
+
+/* The EfficientNet stem: uint8 RGB src [images, h, w, 3] (h, w even) -> y [images, h/2, w/2, cout] = swish(conv3x3 stride 2 of
+ * (src / 255 - mean) / std + bias), ImageNet mean / std, TensorFlow-SAME padding (0 before, 1 after) whose zeros lie in the NORMALISED
+ * image.  wt fp32 [27][cout], row (ky * 3 + kx) * 3 + channel, BatchNorm folded; bias fp32 [cout]; cout a multiple of 8 up to 64. */
+int ca_nbae_stem(const uint8_t* src, const float* wt, const float* bias, void* y, int32_t images, int32_t h, int32_t w, int32_t cout, int32_t dtype, void* stream);
+
+/* Depthwise ksize x ksize (3 or 5) convolution, stride 1 or 2, TensorFlow-SAME padding (out = ceil(in / stride), total =
+ * max((out - 1) * stride + ksize - in, 0), total / 2 in front), + fp32 bias [c], swish: x [images, h, w, c] -> y [images, ho, wo, c];
+ * wt [ksize * ksize][c] of dtype (tap ky * ksize + kx of every channel); c a multiple of 8 up to 3072; planes down to 1 x 1.  It also
+ * writes sums fp32 [images][c]: the sum over the plane of the values it STORED (the rounded ones) in a fixed order, through partials
+ * (ca_dwconv_same_partials_floats(images, h, w, c, stride) floats of scratch; 0 for arguments out of range).  y must not overlap x. */
+int64_t ca_dwconv_same_partials_floats(int32_t images, int32_t h, int32_t w, int32_t c, int32_t stride);
+int ca_dwconv_same(const void* x, const void* wt, const float* bias, void* y, float* sums, float* partials, int32_t images, int32_t h, int32_t w, int32_t c,
+                   int32_t ksize, int32_t stride, int32_t dtype, void* stream);
+
+/* The squeeze-and-excite gate of the whole batch in one launch, fp32 throughout: gate[n][c] = sigmoid(W_e swish(W_r (sums[n] *
+ * inv_pixels) + b_r) + b_e).  w_reduce [r][c], b_reduce [r], w_expand_t [r][c] (the expand weight [c][r] transposed), b_expand [c];
+ * c up to 3072, r up to 256 (any value: no multiple of 8 is asked for). */
+int ca_se_gate(const float* sums, const float* w_reduce, const float* b_reduce, const float* w_expand_t, const float* b_expand, float* gate, int32_t images,
+               int32_t c, int32_t r, float inv_pixels, void* stream);
+
+/* y[n][p][c] = round(x[n][p][c] * gate[n][c]) for x [images, pixels, c] of dtype, gate fp32 [images][c]; y == x is allowed. */
+int ca_scale_channels(const void* x, const float* gate, void* y, int32_t images, int64_t pixels, int32_t c, int32_t dtype, void* stream);
+
+/* The pieces of a refinement stage run as GEMMs: ca_nbae_cat_pred interpolates the fp32 prediction pred [images, h, w, 4] x2 (bilinear,
+ * align_corners, fp32) and rounds it into columns col0 .. col0 + 3 of y [images, 2h, 2w, ld] of dtype, zeros into col0 + 4 .. col0 + 7
+ * (the MLP's input width C + 4 padded to C + 8); ca_nbae_normalize is norm_normalize on the first four of ld fp32 columns of raw [rows]:
+ * pred [rows][4] = (xyz / (sqrt(x^2 + y^2 + z^2) + 1e-10), elu(k) + 1 + min_kappa). */
+int ca_nbae_cat_pred(const float* pred, void* y, int32_t images, int32_t h, int32_t w, int64_t ld, int32_t col0, int32_t dtype, void* stream);
+int ca_nbae_normalize(const float* raw, int64_t ld, float* pred, int64_t rows, float min_kappa, void* stream);
+
+/* One refinement stage in ONE launch: feat [images, h, w, c] of dtype (c = 128, 256 or 512) and the fp32 prediction pred [images, h, w, 4],
+ * both x2 (bilinear, align_corners; the feature row rounded as ca_upsample2x_bilinear_ac rounds it, the prediction as ca_nbae_cat_pred),
+ * through the MLP (c + 4) -> 128 -> 128 -> 128 -> 4 (ReLU, hidden activations rounded to dtype, kept in LDS) on the MFMA, norm_normalize ->
+ * out fp32 [images, 2h, 2w, 4].  w0 .. w3: the weights as MFMA fragments of dtype, fragment (ks, t) = 64 lanes x 8 elements at
+ * ((ks * T + t) * 64 + lane) * 8 holding W[t * 16 + lane % 16][ks * 32 + lane / 16 * 8 + e], T = 8 (w3: T = 1, rows 4 .. 15 zero), K
+ * padded with zeros to a multiple of 32 (w0: c + 4 -> the next multiple of 32 at or above c + 8); b0 .. b2 fp32 [128], b3 fp32 [4]. */
+int ca_nbae_refine(const void* feat, const float* pred, const void* w0, const void* w1, const void* w2, const void* w3, const float* b0, const float* b1,
+                   const float* b2, const float* b3, float* out, int32_t images, int32_t h, int32_t w, int32_t c, float min_kappa, int32_t dtype, void* stream);
+
+/* pred fp32 [images, h, w, 4] (xyz in the first three) -> map uint8 [images, h, w, 3] = trunc(clip(clip((xyz + 1) * 0.5, 0, 1) * 255, 0,
+ * 255)), every operation in fp32 and rounded by itself (byte-exact against numpy), and / or control [rep * images, 3, h, w] = map / 255
+ * (CA_F32 or CA_F16; rep = 2 writes the frames twice).  h * w a multiple of 4. */
+int ca_nbae_finish(const float* pred, int32_t images, int32_t h, int32_t w, uint8_t* map, void* control, int32_t rep, int32_t control_dtype, void* stream);
 
 #ifdef __cplusplus
 }
