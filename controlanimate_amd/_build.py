@@ -19,7 +19,7 @@ from concurrent.futures import ThreadPoolExecutor
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libcontrolanimate_hip.so")
 SOURCES = ["ca_gemm.hip", "ca_gemm_pp.hip", "ca_gemm_ar.hip", "ca_norm.hip", "ca_attention.hip", "ca_elementwise.hip", "ca_upscale.hip", "ca_color.hip", "ca_canny.hip", "ca_perceiver.hip", "ca_hed.hip", "ca_lineart.hip", "ca_mlsd.hip", "ca_softedge.hip", "ca_lineart_anime.hip", "ca_gfpgan.hip", "ca_depth.hip", "ca_openpose.hip", "ca_openpose_face.hip", "ca_openpose_hand.hip", "ca_normalbae.hip"]
-HEADERS = ["ca_common.h", "ca_gemm_core.h", "ca_gemm_plan.h", "ca_gemm_pp2.h", "ca_gemm_wres.h", "ca_gemm_ps.h", "ca_gemm_pq.h", "ca_gemm_ar.h", "ca_ff_fused.h", "ca_attn_out.h", "ca_tattn_fused.h", "ca_xattn_fused.h", "ca_gemm_seq.h", "ca_conv_wino.h", os.path.join("..", "..", "include", "controlanimate_hip.h")]
+HEADERS = ["ca_common.h", "ca_annot.h", "ca_gemm_core.h", "ca_gemm_plan.h", "ca_gemm_pp2.h", "ca_gemm_wres.h", "ca_gemm_ps.h", "ca_gemm_pq.h", "ca_gemm_ar.h", "ca_ff_fused.h", "ca_attn_out.h", "ca_tattn_fused.h", "ca_xattn_fused.h", "ca_gemm_seq.h", "ca_conv_wino.h", os.path.join("..", "..", "include", "controlanimate_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          # keep MFMA accumulators in the (unified) VGPR file: without it hipcc parks them in AGPRs and the
          # attention kernel spends ~200 v_accvgpr_read/write per K/V tile on the softmax rescale

@@ -6,12 +6,13 @@
 //   link      k_label_tile   union-find over the candidates of one 64 x 16 tile in LDS; label = global linear index of the root
 //             k_merge_tiles  unions of the 8-neighbour pairs that straddle a tile border, atomicMin on the int32 labels in HBM
 //             k_flatten      label = root for every candidate; one byte per root: the component holds a strong pixel
-//   emit      k_emit         edge = candidate whose root is marked -> uint8 0 / 255 and / or the control tensor 0.0 / 1.0
+//   emit      k_emit         edge = candidate whose root is marked -> uint8 0 / 255 and / or the control tensor 0.0 / 1.0 (ca_annot.h)
 //
 // Everything is int32, so the result equals the host function's byte for byte.  The hysteresis result is the unique fixed point
 // "every candidate 8-connected to a strong pixel through candidates": the order in which the unions happen does not show.
 // No launch depends on device data on the host side: the chain can be captured in a hipGraph.
 #include "ca_common.h"
+#include "ca_annot.h"
 
 namespace {
 
@@ -21,7 +22,6 @@ constexpr int kRawRows = kTH + 4;        // 2-pixel halo: a neighbour's magnitud
 constexpr int kRawDwords = 52;           // (kTW + 4) * 3 bytes + up to 3 bytes of misalignment = 207 <= 208
 constexpr int kMergeThreads = kTW + 2 * kTH;  // k_merge_tiles: a tile's top row, left column and right column
 constexpr int kMagW = kTW + 2, kMagH = kTH + 2;
-constexpr int64_t kMaxPixels = ((int64_t)1 << 31) - 1;  // labels are int32 linear indices
 
 static_assert((kTW + 4) * 3 + 3 <= kRawDwords * 4, "a raw row of the RGB tile with its halo fits its LDS row");
 
@@ -266,11 +266,6 @@ __global__ __launch_bounds__(256) void k_flatten(const uint8_t* __restrict__ cls
 }
 
 // ---- emit ------------------------------------------------------------------------------------------------------------------------
-template <typename T>
-struct alignas(4 * sizeof(T)) Vec4 {
-  T v[4];
-};
-
 // 4 consecutive pixels per thread.  vec: h * w is a multiple of 4 and the outputs are aligned for 4-element stores.
 template <typename T>
 __global__ __launch_bounds__(256) void k_emit(const int* __restrict__ label, const uint8_t* __restrict__ flag, uint8_t* __restrict__ edges,
@@ -303,25 +298,18 @@ __global__ __launch_bounds__(256) void k_emit(const int* __restrict__ label, con
     if (vec && cnt == 4) {
       const int frame = (int)(g0 / hw);
       const int64_t p = g0 - (int64_t)frame * hw;
-      Vec4<T> v;
+      Vec4<T> v;  // (levels 0 / 255 of the contract: `one` is 255 / 255 in T)
 #pragma unroll
       for (int k = 0; k < 4; ++k) v.v[k] = e[k] ? one : zero;
-      for (int r = 0; r < rep; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) *(Vec4<T>*)(ctrl + (((int64_t)r * images + frame) * 3 + c) * hw + p) = v;
+      const Vec4<T> v3[3] = {v, v, v};
+      emit_vec4(ctrl, images, frame, hw, p, rep, v3);
     } else {
       for (int k = 0; k < cnt; ++k) {
         const int frame = (int)((g0 + k) / hw);
-        const int64_t p = g0 + k - (int64_t)frame * hw;
-        for (int r = 0; r < rep; ++r)
-          for (int c = 0; c < 3; ++c) ctrl[(((int64_t)r * images + frame) * 3 + c) * hw + p] = e[k] ? one : zero;
+        emit_control1(ctrl, images, frame, hw, g0 + k - (int64_t)frame * hw, rep, e[k] ? 255 : 0);
       }
     }
   }
-}
-
-inline bool sizes_ok(int32_t images, int32_t h, int32_t w) {
-  return images >= 1 && h >= 1 && w >= 1 && (int64_t)images * h * w <= kMaxPixels;
 }
 
 inline Geom geom(int32_t h, int32_t w) { return Geom{h, w, (w + kTW - 1) / kTW, (h + kTH - 1) / kTH}; }
@@ -403,15 +391,12 @@ extern "C" int ca_canny_link_stage(int32_t images, int32_t h, int32_t w, void* w
 extern "C" int ca_canny_emit(int32_t images, int32_t h, int32_t w, const void* workspace, int64_t workspace_bytes, uint8_t* edges,
                              void* control, int32_t rep, int32_t control_dtype, void* stream) {
   CA_CANNY_SIZES("ca_canny_emit");
-  CA_REQUIRE(edges || control, "ca_canny_emit: edges or control is required");
-  CA_REQUIRE(rep == 1 || rep == 2, "ca_canny_emit: rep=%d (1 or 2)", rep);
-  CA_REQUIRE(control_dtype == CA_F16 || control_dtype == CA_F32, "ca_canny_emit: control_dtype=%d (CA_F16 or CA_F32)", control_dtype);
+  if (const int rc = control_out_checks("ca_canny_emit", false, h, w, "edges", edges || control, rep, control_dtype)) return rc;
   CA_CANNY_WORKSPACE("ca_canny_emit");
   const int total = (int)((int64_t)images * h * w);
   const int hw = (int)((int64_t)h * w);
-  const int esize = control_dtype == CA_F32 ? 4 : 2;
-  CA_REQUIRE(!control || ((uintptr_t)control & (esize - 1)) == 0, "ca_canny_emit: control is not aligned to its element size");
-  const int vec = hw % 4 == 0 && (!edges || ((uintptr_t)edges & 3) == 0) && (!control || ((uintptr_t)control & (4 * esize - 1)) == 0);
+  CA_REQUIRE(ctrl_aligned(control, control_dtype, 1), "ca_canny_emit: control is not aligned to its element size");
+  const int vec = hw % 4 == 0 && ((uintptr_t)edges & 3) == 0 && ctrl_aligned(control, control_dtype, 4);  // (a NULL output is aligned)
   const int* label = (const int*)((const char*)workspace + l.label);
   const uint8_t* flag = (const uint8_t*)workspace + l.flag;
   const dim3 grid((unsigned)(((int64_t)total + 1023) / 1024)), block(256);

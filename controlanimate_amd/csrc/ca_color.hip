@@ -12,7 +12,7 @@ namespace {
 constexpr int kSortTile = 4096;   // keys per block and pass: 4 waves x 16 rounds x 64 lanes
 constexpr int kMomBlocks = 64;    // partial sums per image (ca_color_moments_f64)
 constexpr int kMmBlocks = 64;     // min / max partials per (image, channel) plane (ca_color_rank_map_f64)
-constexpr int64_t kMaxPixels = (int64_t)1 << 30;
+constexpr int64_t kMaxSortPixels = (int64_t)1 << 30;
 
 struct WsLayout {
   int64_t counts, base, mom, mm, total;  // byte offsets; the second key buffer is at 0
@@ -341,12 +341,12 @@ static_assert(3 * kMmBlocks <= 256, "k_finish_u8 reduces the min / max partials 
 }  // namespace
 
 extern "C" int64_t ca_color_match_workspace_bytes(int32_t images, int64_t pixels) {
-  if (images <= 0 || pixels <= 0 || pixels > kMaxPixels || images > 65535 / 3) return 0;
+  if (images <= 0 || pixels <= 0 || pixels > kMaxSortPixels || images > 65535 / 3) return 0;
   return ws_layout(images, pixels).total;
 }
 
 #define CA_COLOR_SIZES(name)                                                                                              \
-  CA_REQUIRE(images > 0 && images <= 65535 / 3 && pixels > 0 && pixels <= kMaxPixels, name ": images=%d pixels=%lld", images, \
+  CA_REQUIRE(images > 0 && images <= 65535 / 3 && pixels > 0 && pixels <= kMaxSortPixels, name ": images=%d pixels=%lld", images, \
              (long long)pixels)
 
 extern "C" int ca_hist_u8x3(const uint8_t* src, uint32_t* hist, int32_t images, int64_t pixels, void* stream) {
@@ -391,7 +391,7 @@ extern "C" int ca_color_transform_f64(const uint8_t* src, const double* lut, con
 extern "C" int ca_sort_f64_segments(const double* keys, double* sorted, int32_t segments, int64_t n, void* workspace,
                                     int64_t workspace_bytes, void* stream) {
   CA_REQUIRE(keys && sorted, "ca_sort_f64_segments: keys and sorted are required");
-  CA_REQUIRE(segments > 0 && segments <= 65535 && n > 0 && n <= kMaxPixels, "ca_sort_f64_segments: segments=%d n=%lld", segments, (long long)n);
+  CA_REQUIRE(segments > 0 && segments <= 65535 && n > 0 && n <= kMaxSortPixels, "ca_sort_f64_segments: segments=%d n=%lld", segments, (long long)n);
   CA_REQUIRE(aligned8(keys) && aligned8(sorted) && aligned8(workspace), "ca_sort_f64_segments: float64 buffers must be 8-byte aligned");
   const WsLayout l = ws_layout((segments + 2) / 3, n);
   CA_REQUIRE(workspace && workspace_bytes >= l.total, "ca_sort_f64_segments: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,

@@ -80,6 +80,19 @@ struct Elem<CA_F16> {
   }
 };
 
+// Runs stmt with `constexpr int DT` bound to the 16-bit element type: a launch is written once, as k<DT>.  The caller has checked that
+// dtype is CA_BF16 or CA_F16.
+#define CA_DISPATCH_DT(dtype, ...)   \
+  do {                               \
+    if ((dtype) == CA_BF16) {        \
+      constexpr int DT = CA_BF16;    \
+      __VA_ARGS__;                   \
+    } else {                         \
+      constexpr int DT = CA_F16;     \
+      __VA_ARGS__;                   \
+    }                                \
+  } while (0)
+
 // Two fp32 values -> one register of two 16-bit elements, round to nearest even.  (Round 4: written as a vector conversion hipcc
 // emits ONE v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32 instead of the 3-4 instructions below -- measured on the whole step: no gain
 // (61.04 / 60.74 vs 60.89 / 60.36 ms), and the bf16 d = 40 attention kernel then returns wrong values (rel 0.1; cause not

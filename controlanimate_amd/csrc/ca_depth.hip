@@ -19,22 +19,16 @@
 //             k_dpt_logit       the last step of the composed head (ca_upsample2x_bilinear_ac + ca_conv3x3(RELU, fp32 out) + this): 32 -> 1
 //   tail      k_bicubic_f32     torch's interpolate(mode = "bicubic", align_corners = False) of fp32 planes, with the per-frame max and min
 //                               through order-preserving integer atomics (values can be negative: the float bits are not ordered as they are)
-//   finish    k_depth_finish    the uint8 map of either normalisation and / or the control tensor, from the device-side max / min
+//   finish    k_depth_finish    the uint8 map of either normalisation and / or the control tensor (ca_annot.h), from the device-side max / min
 //
 // No launch depends on device data on the host side: the chain can be captured in a hipGraph.  Max and min do not depend on the order of
 // the atomics: two runs give the same bits.
 #include "ca_common.h"
+#include "ca_annot.h"
 
 namespace {
 
-constexpr int64_t kMaxPixels = ((int64_t)1 << 31) - 1;
-constexpr int64_t kMaxBytes = 0x7FFFFF00;
 constexpr int PIL_PRECISION_BITS = 32 - 8 - 2;
-
-inline bool sizes_ok(int32_t images, int32_t h, int32_t w, int64_t scale = 1) {
-  return images >= 1 && h >= 1 && w >= 1 && (int64_t)images * h * w * scale <= kMaxPixels;
-}
-inline bool dtype_ok(int32_t dtype) { return dtype == CA_BF16 || dtype == CA_F16; }
 
 // ---- Pillow's resampler: one axis -----------------------------------------------------------------------------------------------------
 // in [outer][in_len][inner] -> out [outer][out_len][inner] (horizontal: outer = rows, inner = 3; vertical: outer = images, inner = 3 * width).
@@ -297,9 +291,6 @@ __global__ void k_minmax_values(const unsigned* __restrict__ keys, float* __rest
   if (i < 2 * images) out[i] = key_value(keys[i]);
 }
 
-__device__ __forceinline__ void ctrl_store(float* p, int level) { *p = __fdiv_rn((float)level, 255.0f); }
-__device__ __forceinline__ void ctrl_store(u16* p, int level) { *p = Elem<CA_F16>::from_f(__fdiv_rn((float)level, 255.0f)); }
-
 // mode 0 ("max"): d * 255 / max;  mode 1 ("minmax"): (d - min) / (max - min) * 255; fp32 operation for operation as numpy's, truncated toward
 // zero into 0 .. 255: a value <= -1 saturates to 0 (numpy's cast there is platform-defined), a NaN counts as 0.  max <= 0 or max <= min: 0.
 template <typename T>
@@ -319,10 +310,7 @@ __global__ __launch_bounds__(256) void k_depth_finish(const float* __restrict__ 
   v = !(v > 0.f) ? 0.f : (v > 255.f ? 255.f : v);
   const int level = (int)v;
   if (map) map[g] = (uint8_t)level;
-  if (ctrl)
-    for (int r = 0; r < rep; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) ctrl_store(ctrl + (((int64_t)r * images + img) * 3 + c) * hw + p, level);
+  if (ctrl) emit_control1(ctrl, images, img, hw, p, rep, level);
 }
 
 }  // namespace
@@ -354,8 +342,7 @@ extern "C" int ca_dpt_patches(const uint8_t* src, void* out, int32_t images, int
   CA_REQUIRE(((uintptr_t)out & 15) == 0, "ca_dpt_patches: out must be 16-byte aligned");
   const int64_t total = (int64_t)images * size * size * 3 / 8;
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_dpt_patches<CA_BF16>, grid, block, 0, (hipStream_t)stream, src, (u16*)out, total, (int)size, (int)patch);
-  else hipLaunchKernelGGL(k_dpt_patches<CA_F16>, grid, block, 0, (hipStream_t)stream, src, (u16*)out, total, (int)size, (int)patch);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_dpt_patches<DT>, grid, block, 0, (hipStream_t)stream, src, (u16*)out, total, (int)size, (int)patch));
   CA_CHECK_LAUNCH("ca_dpt_patches");
   return CA_OK;
 }
@@ -395,10 +382,7 @@ extern "C" int ca_dpt_head(const void* x, const void* w2, const float* b2, const
   const int64_t blocks = (int64_t)images * tx * ty;
   CA_REQUIRE(blocks < ((int64_t)1 << 31), "ca_dpt_head: grid too large");
   const dim3 grid((unsigned)blocks), block(256);
-  if (dtype == CA_BF16)
-    hipLaunchKernelGGL(k_dpt_head<CA_BF16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, (const u16*)w2, b2, w3, b3, out, (int)h, (int)w, (int)cmid, tx, ty);
-  else
-    hipLaunchKernelGGL(k_dpt_head<CA_F16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, (const u16*)w2, b2, w3, b3, out, (int)h, (int)w, (int)cmid, tx, ty);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_dpt_head<DT>, grid, block, 0, (hipStream_t)stream, (const u16*)x, (const u16*)w2, b2, w3, b3, out, (int)h, (int)w, (int)cmid, tx, ty));
   CA_CHECK_LAUNCH("ca_dpt_head");
   return CA_OK;
 }
@@ -434,17 +418,14 @@ extern "C" int ca_depth_finish(const float* depth, const void* minmax_keys, int3
   CA_REQUIRE(depth && minmax_keys, "ca_depth_finish: depth and minmax_keys are required");
   CA_REQUIRE(sizes_ok(images, h, w, 6), "ca_depth_finish: images=%d h=%d w=%d (each >= 1, images * h * w * 6 < 2^31)", images, h, w);
   CA_REQUIRE(mode == 0 || mode == 1, "ca_depth_finish: mode=%d (0 max, 1 minmax)", mode);
-  CA_REQUIRE(map || control, "ca_depth_finish: map or control is required");
-  CA_REQUIRE(rep == 1 || rep == 2, "ca_depth_finish: rep=%d (1 or 2)", rep);
-  CA_REQUIRE(control_dtype == CA_F16 || control_dtype == CA_F32, "ca_depth_finish: control_dtype=%d (CA_F16 or CA_F32)", control_dtype);
-  CA_REQUIRE((((uintptr_t)depth | (uintptr_t)minmax_keys) & 3) == 0 && ((uintptr_t)control & (control_dtype == CA_F32 ? 3 : 1)) == 0,
+  if (const int rc = control_out_checks("ca_depth_finish", false, h, w, "map", map || control, rep, control_dtype)) return rc;
+  CA_REQUIRE((((uintptr_t)depth | (uintptr_t)minmax_keys) & 3) == 0 && ctrl_aligned(control, control_dtype, 1),
              "ca_depth_finish: depth and minmax_keys must be 4-byte aligned, control aligned to its element");
   const int64_t hw = (int64_t)h * w, total = (int64_t)images * hw;
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (control_dtype == CA_F32)
-    hipLaunchKernelGGL(k_depth_finish<float>, grid, block, 0, st, depth, (const unsigned*)minmax_keys, map, (float*)control, (int)images, hw, (int)mode, (int)rep);
-  else hipLaunchKernelGGL(k_depth_finish<u16>, grid, block, 0, st, depth, (const unsigned*)minmax_keys, map, (u16*)control, (int)images, hw, (int)mode, (int)rep);
+  CA_DISPATCH_CTRL(control_dtype,
+                   hipLaunchKernelGGL(k_depth_finish<T>, grid, block, 0, st, depth, (const unsigned*)minmax_keys, map, (T*)control, (int)images, hw, (int)mode, (int)rep));
   CA_CHECK_LAUNCH("ca_depth_finish");
   return CA_OK;
 }

@@ -170,8 +170,7 @@ extern "C" int ca_add_bcast(const void* a, const void* b, void* out, int64_t n, 
   CA_REQUIRE(n > 0 && n % 8 == 0 && b_period > 0 && b_period % 8 == 0, "ca_add_bcast: n=%lld period=%lld must be multiples of 8", (long long)n, (long long)b_period);
   CA_REQUIRE(dtype == CA_BF16 || dtype == CA_F16, "ca_add_bcast: dtype %d", dtype);
   const unsigned blocks = blocks_for(n / 8, 256, 8192);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_add_bcast<CA_BF16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const u16*)a, (const u16*)b, (u16*)out, n / 8, b_period / 8);
-  else hipLaunchKernelGGL(k_add_bcast<CA_F16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const u16*)a, (const u16*)b, (u16*)out, n / 8, b_period / 8);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_add_bcast<DT>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const u16*)a, (const u16*)b, (u16*)out, n / 8, b_period / 8));
   CA_CHECK_LAUNCH("ca_add_bcast");
   return CA_OK;
 }
@@ -255,8 +254,7 @@ extern "C" int ca_softmax_rows(const float* x, void* y, int64_t rows, int32_t co
   CA_REQUIRE(dtype == CA_BF16 || dtype == CA_F16, "ca_softmax_rows: dtype %d", dtype);
   const float sl2 = scale * 1.4426950408889634f;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_softmax_rows<CA_BF16>, dim3((unsigned)rows), dim3(256), 0, st, x, (u16*)y, cols, ldx, ldy, sl2);
-  else hipLaunchKernelGGL(k_softmax_rows<CA_F16>, dim3((unsigned)rows), dim3(256), 0, st, x, (u16*)y, cols, ldx, ldy, sl2);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_softmax_rows<DT>, dim3((unsigned)rows), dim3(256), 0, st, x, (u16*)y, cols, ldx, ldy, sl2));
   CA_CHECK_LAUNCH("ca_softmax_rows");
   return CA_OK;
 }
@@ -272,8 +270,7 @@ extern "C" int ca_timestep_embedding(const float* t_dev, float t_host, void* out
   CA_REQUIRE(out && batch > 0 && dim > 0 && dim % 2 == 0, "ca_timestep_embedding: bad args");
   CA_REQUIRE(dtype == CA_BF16 || dtype == CA_F16, "ca_timestep_embedding: dtype %d", dtype);
   const int n = batch * (dim / 2);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_timestep_embedding<CA_BF16>, dim3(blocks_for(n, 128)), dim3(128), 0, (hipStream_t)stream, t_dev, t_host, (u16*)out, batch, dim);
-  else hipLaunchKernelGGL(k_timestep_embedding<CA_F16>, dim3(blocks_for(n, 128)), dim3(128), 0, (hipStream_t)stream, t_dev, t_host, (u16*)out, batch, dim);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_timestep_embedding<DT>, dim3(blocks_for(n, 128)), dim3(128), 0, (hipStream_t)stream, t_dev, t_host, (u16*)out, batch, dim));
   CA_CHECK_LAUNCH("ca_timestep_embedding");
   return CA_OK;
 }
@@ -284,8 +281,7 @@ extern "C" int ca_latents_to_nhwc(const float* latents, void* out, int32_t b0, i
   CA_REQUIRE(b0 > 0 && c > 0 && f > 0 && h > 0 && w > 0 && cpad >= c && cpad % 8 == 0 && rep >= 1, "ca_latents_to_nhwc: bad sizes");
   CA_REQUIRE(dtype == CA_BF16 || dtype == CA_F16, "ca_latents_to_nhwc: dtype %d", dtype);
   const int64_t npix = (int64_t)b0 * f * h * w;
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_latents_to_nhwc<CA_BF16>, dim3(blocks_for(npix, 256)), dim3(256), 0, (hipStream_t)stream, latents, (u16*)out, b0, c, f, h, w, cpad, rep, in_scale);
-  else hipLaunchKernelGGL(k_latents_to_nhwc<CA_F16>, dim3(blocks_for(npix, 256)), dim3(256), 0, (hipStream_t)stream, latents, (u16*)out, b0, c, f, h, w, cpad, rep, in_scale);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_latents_to_nhwc<DT>, dim3(blocks_for(npix, 256)), dim3(256), 0, (hipStream_t)stream, latents, (u16*)out, b0, c, f, h, w, cpad, rep, in_scale));
   CA_CHECK_LAUNCH("ca_latents_to_nhwc");
   return CA_OK;
 }
@@ -296,8 +292,7 @@ extern "C" int ca_nhwc_to_ncfhw_f32(const void* x, float* out, int32_t b, int32_
   CA_REQUIRE(b > 0 && c > 0 && f > 0 && h > 0 && w > 0 && ldx >= c, "ca_nhwc_to_ncfhw_f32: bad sizes");
   CA_REQUIRE(dtype == CA_BF16 || dtype == CA_F16, "ca_nhwc_to_ncfhw_f32: dtype %d", dtype);
   const int64_t n = (int64_t)b * c * f * h * w;
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_nhwc_to_ncfhw_f32<CA_BF16>, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, out, b, c, f, h, w, ldx, x_is_f32);
-  else hipLaunchKernelGGL(k_nhwc_to_ncfhw_f32<CA_F16>, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, out, b, c, f, h, w, ldx, x_is_f32);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_nhwc_to_ncfhw_f32<DT>, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, out, b, c, f, h, w, ldx, x_is_f32));
   CA_CHECK_LAUNCH("ca_nhwc_to_ncfhw_f32");
   return CA_OK;
 }
@@ -311,8 +306,7 @@ extern "C" int ca_ncfhw_to_nhwc(const void* x, int32_t x_kind, const int64_t str
   Strides5 st;
   for (int i = 0; i < 5; ++i) st.s[i] = strides[i];
   const int64_t n = (int64_t)b * f * h * w * cpad;
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_ncfhw_to_nhwc<CA_BF16>, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, x_kind, st, (u16*)out, b, c, f, h, w, cpad);
-  else hipLaunchKernelGGL(k_ncfhw_to_nhwc<CA_F16>, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, x_kind, st, (u16*)out, b, c, f, h, w, cpad);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_ncfhw_to_nhwc<DT>, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, x_kind, st, (u16*)out, b, c, f, h, w, cpad));
   CA_CHECK_LAUNCH("ca_ncfhw_to_nhwc");
   return CA_OK;
 }

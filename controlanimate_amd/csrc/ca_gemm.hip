@@ -571,8 +571,7 @@ extern "C" int ca_pack_w_wino(const void* w, int32_t cout, int32_t cin, int32_t 
   CA_REQUIRE(w && dst, "ca_pack_w_wino: null operand");
   CA_REQUIRE(cout > 0 && cin > 0 && (dtype == CA_BF16 || dtype == CA_F16), "ca_pack_w_wino: cout=%d cin=%d dtype=%d", cout, cin, dtype);
   const int64_t n = (int64_t)cout * cin;
-  if (dtype == CA_BF16) hipLaunchKernelGGL((k_pack_w_wino<CA_BF16>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const u16*)w, (u16*)dst, cout, cin);
-  else hipLaunchKernelGGL((k_pack_w_wino<CA_F16>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const u16*)w, (u16*)dst, cout, cin);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_pack_w_wino<DT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const u16*)w, (u16*)dst, cout, cin));
   CA_CHECK_LAUNCH("ca_pack_w_wino");
   return CA_OK;
 }

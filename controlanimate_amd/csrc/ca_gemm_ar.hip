@@ -236,8 +236,7 @@ extern "C" int ca_xattn_pack_kv(const void* kv, int64_t ld, int32_t kv_batches, 
   CA_REQUIRE(dtype == CA_BF16 || dtype == CA_F16, "ca_xattn_pack_kv: dtype %d", dtype);
   CA_REQUIRE(((uintptr_t)dst & 15) == 0 && scale > 0.f, "ca_xattn_pack_kv: dst must be 16-byte aligned, scale > 0");
   const float sl2 = scale * 1.4426950408889634f;
-  if (dtype == CA_BF16) hipLaunchKernelGGL((k_xattn_pack_kv<CA_BF16>), dim3((unsigned)kv_batches * 8), dim3(64), 0, (hipStream_t)stream, (const u16*)kv, ld, rows_per_batch, row_offset, nk, sl2, (u16*)dst);
-  else hipLaunchKernelGGL((k_xattn_pack_kv<CA_F16>), dim3((unsigned)kv_batches * 8), dim3(64), 0, (hipStream_t)stream, (const u16*)kv, ld, rows_per_batch, row_offset, nk, sl2, (u16*)dst);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_xattn_pack_kv<DT>), dim3((unsigned)kv_batches * 8), dim3(64), 0, (hipStream_t)stream, (const u16*)kv, ld, rows_per_batch, row_offset, nk, sl2, (u16*)dst));
   CA_CHECK_LAUNCH("ca_xattn_pack_kv");
   return CA_OK;
 }

@@ -110,7 +110,6 @@ int ca_launch_gemm_pp(const ca_gemm_detail::GemmKParams& p0, int dtype, int mode
   static const int dbg = CA_KNOB("CA_PP_DBG", 0);  // (timing experiments: 1 = no epilogue, 2 = no main loop)
   ca_gemm_detail::GemmKParams p = p0;
   p.dbg = dbg;
-  if (mode == 2) return dtype == CA_BF16 ? launch_up2<CA_BF16>(p, kind, tiles, st) : launch_up2<CA_F16>(p, kind, tiles, st);
-  if (dtype == CA_BF16) return mode ? launch_pp<CA_BF16, 1>(p, kind, tiles, st) : launch_pp<CA_BF16, 0>(p, kind, tiles, st);
-  return mode ? launch_pp<CA_F16, 1>(p, kind, tiles, st) : launch_pp<CA_F16, 0>(p, kind, tiles, st);
+  if (mode == 2) CA_DISPATCH_DT(dtype, return launch_up2<DT>(p, kind, tiles, st));
+  CA_DISPATCH_DT(dtype, return mode ? launch_pp<DT, 1>(p, kind, tiles, st) : launch_pp<DT, 0>(p, kind, tiles, st));
 }

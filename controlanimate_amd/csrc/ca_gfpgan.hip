@@ -22,11 +22,9 @@
 //
 // No launch depends on device data on the host side: the chain can be captured in a hipGraph.  No atomics: two runs give the same bits.
 #include "ca_common.h"
+#include "ca_annot.h"
 
 namespace {
-
-constexpr int64_t kMaxPixels = ((int64_t)1 << 31) - 1;
-constexpr int64_t kMaxBytes = 0x7FFFFF00;  // an operand stays below this: the kernels index elements with 64-bit offsets
 
 __device__ __forceinline__ float leaky02(float v) { return v > 0.f ? v : 0.2f * v; }
 
@@ -454,10 +452,6 @@ __global__ __launch_bounds__(256) void k_gfp_finish(const float* __restrict__ pr
   }
 }
 
-inline bool sizes_ok(int32_t images, int32_t h, int32_t w, int64_t scale = 1) {
-  return images >= 1 && h >= 1 && w >= 1 && (int64_t)images * h * w * scale <= kMaxPixels;
-}
-inline bool dtype_ok(int32_t dtype) { return dtype == CA_BF16 || dtype == CA_F16; }
 inline bool mc_c_ok(int32_t c) { return c == 64 || c == 128 || c == 256 || c == 512; }
 
 template <int DT>
@@ -484,8 +478,7 @@ extern "C" int ca_gfp_prep(const uint8_t* src, const float* wt, const float* bia
   CA_REQUIRE(((uintptr_t)y & 15) == 0 && (((uintptr_t)wt | (uintptr_t)bias) & 3) == 0, "ca_gfp_prep: y must be 16-byte aligned, wt and bias 4-byte aligned");
   const int64_t pixels = (int64_t)images * h * w, total = pixels * (cout / 8);
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_gfp_prep<CA_BF16>, grid, block, 0, (hipStream_t)stream, src, wt, bias, (u16*)y, pixels, (int)cout, (int)reverse_channels);
-  else hipLaunchKernelGGL(k_gfp_prep<CA_F16>, grid, block, 0, (hipStream_t)stream, src, wt, bias, (u16*)y, pixels, (int)cout, (int)reverse_channels);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_gfp_prep<DT>, grid, block, 0, (hipStream_t)stream, src, wt, bias, (u16*)y, pixels, (int)cout, (int)reverse_channels));
   CA_CHECK_LAUNCH("ca_gfp_prep");
   return CA_OK;
 }
@@ -503,11 +496,9 @@ extern "C" int ca_resample2x(const void* x, void* y, int32_t images, int32_t h, 
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
   if (up) {
-    if (dtype == CA_BF16) hipLaunchKernelGGL(k_gfp_up2<CA_BF16>, grid, block, 0, st, (const u16*)x, (u16*)y, total, (int)h, (int)w, (int)c);
-    else hipLaunchKernelGGL(k_gfp_up2<CA_F16>, grid, block, 0, st, (const u16*)x, (u16*)y, total, (int)h, (int)w, (int)c);
+    CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_gfp_up2<DT>, grid, block, 0, st, (const u16*)x, (u16*)y, total, (int)h, (int)w, (int)c));
   } else {
-    if (dtype == CA_BF16) hipLaunchKernelGGL(k_gfp_down2<CA_BF16>, grid, block, 0, st, (const u16*)x, (u16*)y, total, (int)h, (int)w, (int)c);
-    else hipLaunchKernelGGL(k_gfp_down2<CA_F16>, grid, block, 0, st, (const u16*)x, (u16*)y, total, (int)h, (int)w, (int)c);
+    CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_gfp_down2<DT>, grid, block, 0, st, (const u16*)x, (u16*)y, total, (int)h, (int)w, (int)c));
   }
   CA_CHECK_LAUNCH("ca_resample2x");
   return CA_OK;
@@ -591,13 +582,8 @@ extern "C" int ca_gfp_modulate(const void* x, const float* s, int64_t s_stride, 
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
   const u16* xs = (const u16*)x;
-  if (dtype == CA_BF16) {
-    if (upsample) hipLaunchKernelGGL((k_gfp_modulate<CA_BF16, true>), grid, block, 0, st, xs, s, s_stride, (u16*)y, total, (int)h, (int)w, (int)c, (int)x_shared);
-    else hipLaunchKernelGGL((k_gfp_modulate<CA_BF16, false>), grid, block, 0, st, xs, s, s_stride, (u16*)y, total, (int)h, (int)w, (int)c, (int)x_shared);
-  } else {
-    if (upsample) hipLaunchKernelGGL((k_gfp_modulate<CA_F16, true>), grid, block, 0, st, xs, s, s_stride, (u16*)y, total, (int)h, (int)w, (int)c, (int)x_shared);
-    else hipLaunchKernelGGL((k_gfp_modulate<CA_F16, false>), grid, block, 0, st, xs, s, s_stride, (u16*)y, total, (int)h, (int)w, (int)c, (int)x_shared);
-  }
+  CA_DISPATCH_DT(dtype, if (upsample) hipLaunchKernelGGL((k_gfp_modulate<DT, true>), grid, block, 0, st, xs, s, s_stride, (u16*)y, total, (int)h, (int)w, (int)c, (int)x_shared);
+    else hipLaunchKernelGGL((k_gfp_modulate<DT, false>), grid, block, 0, st, xs, s, s_stride, (u16*)y, total, (int)h, (int)w, (int)c, (int)x_shared));
   CA_CHECK_LAUNCH("ca_gfp_modulate");
   return CA_OK;
 }
@@ -618,12 +604,8 @@ extern "C" int ca_gfp_style_epilogue(const void* t, const float* demod, int64_t 
   const int64_t hw = (int64_t)h * w, total = (int64_t)images * hw * (c / 8);
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == CA_BF16)
-    hipLaunchKernelGGL(k_gfp_style_epilogue<CA_BF16>, grid, block, 0, st, (const u16*)t, demod, demod_stride, noise, noise_weight, bias, (const u16*)sft_scale,
-                       (const u16*)sft_shift, (u16*)y, total, hw, (int)c);
-  else
-    hipLaunchKernelGGL(k_gfp_style_epilogue<CA_F16>, grid, block, 0, st, (const u16*)t, demod, demod_stride, noise, noise_weight, bias, (const u16*)sft_scale,
-                       (const u16*)sft_shift, (u16*)y, total, hw, (int)c);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_gfp_style_epilogue<DT>, grid, block, 0, st, (const u16*)t, demod, demod_stride, noise, noise_weight, bias, (const u16*)sft_scale,
+                       (const u16*)sft_shift, (u16*)y, total, hw, (int)c));
   CA_CHECK_LAUNCH("ca_gfp_style_epilogue");
   return CA_OK;
 }
@@ -643,10 +625,7 @@ extern "C" int ca_gfp_to_rgb(const void* x, const float* wt, const float* s, int
   const int64_t blocks = (int64_t)images * bpi;
   CA_REQUIRE(blocks < ((int64_t)1 << 31), "ca_gfp_to_rgb: grid too large");
   const dim3 grid((unsigned)blocks), block(256);
-  if (dtype == CA_BF16)
-    hipLaunchKernelGGL(k_gfp_to_rgb<CA_BF16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, wt, s, s_stride, bias, prev, out, (int)h, (int)w, (int)cin, bpi);
-  else
-    hipLaunchKernelGGL(k_gfp_to_rgb<CA_F16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, wt, s, s_stride, bias, prev, out, (int)h, (int)w, (int)cin, bpi);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_gfp_to_rgb<DT>, grid, block, 0, (hipStream_t)stream, (const u16*)x, wt, s, s_stride, bias, prev, out, (int)h, (int)w, (int)cin, bpi));
   CA_CHECK_LAUNCH("ca_gfp_to_rgb");
   return CA_OK;
 }

@@ -2,36 +2,30 @@
 // tests/hed_ref.py, restated from the published ControlNetHED_Apache2 / HEDdetector).  The thirteen 3x3 convolutions of the VGG
 // stack run on ca_conv3x3 with CA_ACT_RELU; around them:
 //
-//   prep       k_hed_prep       uint8 RGB [n,H,W,3] -> NHWC [n,H,W,8] fp16 / bf16: channel c < 3 = (float)src[c] - norm[c], 3..7 = 0
+//   prep       HedFill          uint8 RGB [n,H,W,3] -> NHWC [n,H,W,8] fp16 / bf16: channel c < 3 = (float)src[c] - norm[c], 3..7 = 0
 //                               (the first convolution's weight is zero-padded to cin = 8): one 16-byte store per pixel
 //   pool_side  k_hed_pool_side  ONE pass over a block's output [n,h,w,C]: the 1x1 projection to the side map (fp32 [n,h,w], fp32
 //                               accumulation) and, unless the block is the last, the 2x2 / stride-2 max pool [n,h/2,w/2,C]
 //   fuse       k_hed_fuse       per output pixel: the five side maps sampled as cv2.resize(INTER_LINEAR) samples float32, their fp32
 //                               mean, the float64 sigmoid, x 255, truncation -> uint8 [n,H,W] and / or the control tensor
-//                               [rep * n,3,H,W] with level / 255 (as ca_canny_emit)
+//                               [rep * n,3,H,W] with level / 255 (ca_annot.h)
 //
 // Compiled with -ffp-contract=off: the bilinear sample is a * w0 + b * w1 with three roundings, as numpy computes it.
 // No launch depends on device data on the host side: the chain can be captured in a hipGraph.
 #include "ca_common.h"
+#include "ca_annot.h"
 
 namespace {
 
-constexpr int64_t kMaxPixels = ((int64_t)1 << 31) - 1;
-
 // ---- prep ------------------------------------------------------------------------------------------------------------------------
-template <int DT>
-__global__ __launch_bounds__(256) void k_hed_prep(const uint8_t* __restrict__ src, const float* __restrict__ norm, u16* __restrict__ dst, int64_t pixels) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= pixels) return;
-  const uint8_t* s = src + i * 3;
-  const float r = (float)s[0] - norm[0], g = (float)s[1] - norm[1], b = (float)s[2] - norm[2];
-  u32x4 v;
-  v[0] = pack2<DT>(r, g);
-  v[1] = (unsigned)Elem<DT>::from_f(b);
-  v[2] = 0u;
-  v[3] = 0u;
-  st16(dst + i * 8, v);
-}
+struct HedFill {
+  const float* norm;
+  __device__ __forceinline__ void operator()(const uint8_t* s, float f[8]) const {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) f[c] = (float)s[c] - norm[c];
+    f[3] = f[4] = f[5] = f[6] = f[7] = 0.f;
+  }
+};
 
 // ---- projection + max pool ---------------------------------------------------------------------------------------------------------
 // A group of G lanes (G = the power of two >= C / 8, 8 .. 64) owns one 2x2 quad of pixels; lane j of the group holds channels
@@ -113,14 +107,6 @@ struct Sides {
   const float* s[5];
 };
 
-template <typename T>
-struct alignas(4 * sizeof(T)) Vec4 {
-  T v[4];
-};
-
-__device__ __forceinline__ void ctrl_from_level(int level, float& out) { out = __fdiv_rn((float)level, 255.0f); }
-__device__ __forceinline__ void ctrl_from_level(int level, u16& out) { out = Elem<CA_F16>::from_f(__fdiv_rn((float)level, 255.0f)); }
-
 // 4 consecutive pixels of one row per thread (w % 16 == 0): one 4-byte store to edges, 16 / 8-byte stores to the control tensor
 template <typename T>
 __global__ __launch_bounds__(256) void k_hed_fuse(Sides sd, uint8_t* __restrict__ edges, T* __restrict__ ctrl, int images, int h, int w, int rep) {
@@ -163,34 +149,15 @@ __global__ __launch_bounds__(256) void k_hed_fuse(Sides sd, uint8_t* __restrict_
     e = e < 0.0 ? 0.0 : (e > 255.0 ? 255.0 : e);
     level[i] = (int)e;  // truncation, as astype(uint8) of a value in [0, 255]
   }
-  if (edges) *(uint32_t*)(edges + g0) = (uint32_t)level[0] | ((uint32_t)level[1] << 8) | ((uint32_t)level[2] << 16) | ((uint32_t)level[3] << 24);
-  if (ctrl) {
-    Vec4<T> v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ctrl_from_level(level[i], v.v[i]);
-    for (int r = 0; r < rep; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) *(Vec4<T>*)(ctrl + (((int64_t)r * images + img) * 3 + c) * hw + p) = v;
-  }
-}
-
-inline bool sizes_ok(int32_t images, int32_t h, int32_t w) {
-  return images >= 1 && h >= 1 && w >= 1 && (int64_t)images * h * w <= kMaxPixels;
+  if (edges) *(uint32_t*)(edges + g0) = pack_levels4(level);
+  if (ctrl) emit_control4(ctrl, images, img, hw, p, rep, level);
 }
 
 }  // namespace
 
 extern "C" int ca_hed_prep(const uint8_t* src, const float* norm, void* dst, int32_t images, int32_t h, int32_t w, int32_t dtype, void* stream) {
-  CA_REQUIRE(src && norm && dst, "ca_hed_prep: src, norm and dst are required");
-  CA_REQUIRE(sizes_ok(images, h, w), "ca_hed_prep: images=%d h=%d w=%d (each >= 1, images * h * w < 2^31)", images, h, w);
-  CA_REQUIRE(dtype == CA_BF16 || dtype == CA_F16, "ca_hed_prep: dtype %d", dtype);
-  CA_REQUIRE(((uintptr_t)dst & 15) == 0 && ((uintptr_t)norm & 3) == 0, "ca_hed_prep: dst must be 16-byte aligned, norm 4-byte aligned");
-  const int64_t pixels = (int64_t)images * h * w;
-  const dim3 grid((unsigned)((pixels + 255) / 256)), block(256);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_hed_prep<CA_BF16>, grid, block, 0, (hipStream_t)stream, src, norm, (u16*)dst, pixels);
-  else hipLaunchKernelGGL(k_hed_prep<CA_F16>, grid, block, 0, (hipStream_t)stream, src, norm, (u16*)dst, pixels);
-  CA_CHECK_LAUNCH("ca_hed_prep");
-  return CA_OK;
+  return launch_rgb8_prep("ca_hed_prep", "src, norm and dst", src && norm && dst, src, dst, images, h, w, dtype, ((uintptr_t)norm & 3) == 0,
+                          "dst must be 16-byte aligned, norm 4-byte aligned", stream, HedFill{norm});
 }
 
 extern "C" int ca_hed_pool_side(const void* x, const float* proj_w, const float* proj_bias, float* side, void* pooled, int32_t images, int32_t h,
@@ -199,7 +166,7 @@ extern "C" int ca_hed_pool_side(const void* x, const float* proj_w, const float*
   CA_REQUIRE(sizes_ok(images, h, w), "ca_hed_pool_side: images=%d h=%d w=%d (each >= 1, images * h * w < 2^31)", images, h, w);
   CA_REQUIRE(h % 2 == 0 && w % 2 == 0, "ca_hed_pool_side: h=%d w=%d must be even", h, w);
   CA_REQUIRE(c >= 64 && c <= 512 && c % 8 == 0, "ca_hed_pool_side: c=%d must be a multiple of 8 in 64 .. 512", c);
-  CA_REQUIRE(dtype == CA_BF16 || dtype == CA_F16, "ca_hed_pool_side: dtype %d", dtype);
+  CA_REQUIRE(dtype_ok(dtype), "ca_hed_pool_side: dtype %d", dtype);
   CA_REQUIRE((((uintptr_t)x | (uintptr_t)pooled | (uintptr_t)proj_w) & 15) == 0 && ((uintptr_t)side & 7) == 0 && ((uintptr_t)proj_bias & 3) == 0,
              "ca_hed_pool_side: x, pooled and proj_w must be 16-byte aligned, side 8-byte aligned, proj_bias 4-byte aligned");
   int glog = 3;
@@ -208,10 +175,7 @@ extern "C" int ca_hed_pool_side(const void* x, const float* proj_w, const float*
   const int64_t threads = quads << glog;
   CA_REQUIRE((threads + 255) / 256 < ((int64_t)1 << 31), "ca_hed_pool_side: grid too large");
   const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
-  if (dtype == CA_BF16)
-    hipLaunchKernelGGL(k_hed_pool_side<CA_BF16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, proj_w, proj_bias, side, (u16*)pooled, quads, h / 2, w / 2, (int)c, glog);
-  else
-    hipLaunchKernelGGL(k_hed_pool_side<CA_F16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, proj_w, proj_bias, side, (u16*)pooled, quads, h / 2, w / 2, (int)c, glog);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_hed_pool_side<DT>, grid, block, 0, (hipStream_t)stream, (const u16*)x, proj_w, proj_bias, side, (u16*)pooled, quads, h / 2, w / 2, (int)c, glog));
   CA_CHECK_LAUNCH("ca_hed_pool_side");
   return CA_OK;
 }
@@ -221,21 +185,17 @@ extern "C" int ca_hed_fuse(const float* side0, const float* side1, const float* 
   CA_REQUIRE(side0 && side1 && side2 && side3 && side4, "ca_hed_fuse: the five side maps are required");
   CA_REQUIRE(sizes_ok(images, h, w), "ca_hed_fuse: images=%d h=%d w=%d (each >= 1, images * h * w < 2^31)", images, h, w);
   CA_REQUIRE(h % 16 == 0 && w % 16 == 0, "ca_hed_fuse: h=%d w=%d must be multiples of 16 (five levels, the k-th of (h >> k, w >> k))", h, w);
-  CA_REQUIRE(edges || control, "ca_hed_fuse: edges or control is required");
-  CA_REQUIRE(rep == 1 || rep == 2, "ca_hed_fuse: rep=%d (1 or 2)", rep);
-  CA_REQUIRE(control_dtype == CA_F16 || control_dtype == CA_F32, "ca_hed_fuse: control_dtype=%d (CA_F16 or CA_F32)", control_dtype);
-  const int esize = control_dtype == CA_F32 ? 4 : 2;
+  if (const int rc = control_out_checks("ca_hed_fuse", false, h, w, "edges", edges || control, rep, control_dtype)) return rc;
   CA_REQUIRE(((uintptr_t)side0 & 15) == 0 && (((uintptr_t)side1 | (uintptr_t)side2 | (uintptr_t)side3 | (uintptr_t)side4) & 3) == 0,
              "ca_hed_fuse: side0 must be 16-byte aligned, the other side maps 4-byte aligned");
-  CA_REQUIRE(((uintptr_t)edges & 3) == 0 && ((uintptr_t)control & (4 * esize - 1)) == 0,
+  CA_REQUIRE(((uintptr_t)edges & 3) == 0 && ctrl_aligned(control, control_dtype, 4),
              "ca_hed_fuse: edges must be 4-byte aligned, control aligned to four of its elements");
   Sides sd;
   sd.s[0] = side0, sd.s[1] = side1, sd.s[2] = side2, sd.s[3] = side3, sd.s[4] = side4;
   const int64_t total = (int64_t)images * h * w;
   const dim3 grid((unsigned)((total / 4 + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (control_dtype == CA_F32) hipLaunchKernelGGL(k_hed_fuse<float>, grid, block, 0, st, sd, edges, (float*)control, (int)images, (int)h, (int)w, (int)rep);
-  else hipLaunchKernelGGL(k_hed_fuse<u16>, grid, block, 0, st, sd, edges, (u16*)control, (int)images, (int)h, (int)w, (int)rep);
+  CA_DISPATCH_CTRL(control_dtype, hipLaunchKernelGGL(k_hed_fuse<T>, grid, block, 0, st, sd, edges, (T*)control, (int)images, (int)h, (int)w, (int)rep));
   CA_CHECK_LAUNCH("ca_hed_fuse");
   return CA_OK;
 }

@@ -17,14 +17,13 @@
 //   conv_out  k_lineart_conv_out  64 -> 1, 7x7, reflection padding 3 -> fp32 logits [n,H,W]: an LDS tile of the input per 16x16
 //                                 outputs, fp32 weights through the scalar cache, fp32 accumulation
 //   finish    k_lineart_finish    255 - trunc(clip(sigmoid(logit) * 255)) -> the uint8 map and / or the control tensor
-//                                 [rep * n,3,H,W] with map / 255 (the contract of ca_hed_fuse)
+//                                 [rep * n,3,H,W] with map / 255 (the contract in ca_annot.h)
 //
 // No launch depends on device data on the host side: the chain can be captured in a hipGraph.  No atomics: two runs give the same bits.
 #include "ca_common.h"
+#include "ca_annot.h"
 
 namespace {
-
-constexpr int64_t kMaxPixels = ((int64_t)1 << 31) - 1;
 
 // index i of an axis of n >= 2 samples padded by reflection (no repeated edge); an index that reflection does not bring inside --
 // a tile's overhang past the image, never read by a live output -- is clamped
@@ -284,14 +283,6 @@ __global__ __launch_bounds__(256) void k_lineart_conv_out(const u16* __restrict_
 }
 
 // ---- sigmoid, quantise, invert ----------------------------------------------------------------------------------------------------------
-template <typename T>
-struct alignas(4 * sizeof(T)) Vec4 {
-  T v[4];
-};
-
-__device__ __forceinline__ void ctrl_from_level(int level, float& out) { out = __fdiv_rn((float)level, 255.0f); }
-__device__ __forceinline__ void ctrl_from_level(int level, u16& out) { out = Elem<CA_F16>::from_f(__fdiv_rn((float)level, 255.0f)); }
-
 // 4 consecutive pixels per thread (h * w % 4 == 0): one 4-byte store to the map, 16 / 8-byte stores to the control tensor
 template <typename T>
 __global__ __launch_bounds__(256) void k_lineart_finish(const float* __restrict__ logits, uint8_t* __restrict__ map, T* __restrict__ ctrl, int images, int64_t hw,
@@ -308,21 +299,10 @@ __global__ __launch_bounds__(256) void k_lineart_finish(const float* __restrict_
     e = !(e > 0.0) ? 0.0 : (e > 255.0 ? 255.0 : e);  // (a NaN logit counts as 0)
     level[i] = 255 - (int)e;                         // truncation, as astype(uint8) of a value in [0, 255]
   }
-  if (map) *(uint32_t*)(map + g0) = (uint32_t)level[0] | ((uint32_t)level[1] << 8) | ((uint32_t)level[2] << 16) | ((uint32_t)level[3] << 24);
-  if (ctrl) {
-    Vec4<T> o;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ctrl_from_level(level[i], o.v[i]);
-    for (int r = 0; r < rep; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) *(Vec4<T>*)(ctrl + (((int64_t)r * images + img) * 3 + c) * hw + p) = o;
-  }
+  if (map) *(uint32_t*)(map + g0) = pack_levels4(level);
+  if (ctrl) emit_control4(ctrl, images, img, hw, p, rep, level);
 }
 
-inline bool sizes_ok(int32_t images, int32_t h, int32_t w, int64_t scale = 1) {
-  return images >= 1 && h >= 1 && w >= 1 && (int64_t)images * h * w * scale <= kMaxPixels;
-}
-inline bool dtype_ok(int32_t dtype) { return dtype == CA_BF16 || dtype == CA_F16; }
 inline bool in_c_ok(int32_t c) { return c == 64 || c == 128 || c == 256; }
 
 }  // namespace
@@ -336,8 +316,7 @@ extern "C" int ca_lineart_conv_in(const uint8_t* src, const void* w_packed, void
   const int64_t blocks = (int64_t)images * tx * ty;
   CA_REQUIRE(blocks < ((int64_t)1 << 31), "ca_lineart_conv_in: grid too large");
   const dim3 grid((unsigned)blocks), block(256);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_lineart_conv_in<CA_BF16>, grid, block, 0, (hipStream_t)stream, src, (const u16*)w_packed, (u16*)dst, (int)h, (int)w, tx, ty);
-  else hipLaunchKernelGGL(k_lineart_conv_in<CA_F16>, grid, block, 0, (hipStream_t)stream, src, (const u16*)w_packed, (u16*)dst, (int)h, (int)w, tx, ty);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_lineart_conv_in<DT>, grid, block, 0, (hipStream_t)stream, src, (const u16*)w_packed, (u16*)dst, (int)h, (int)w, tx, ty));
   CA_CHECK_LAUNCH("ca_lineart_conv_in");
   return CA_OK;
 }
@@ -363,8 +342,7 @@ extern "C" int ca_instnorm_stats(const void* x, float* partials, int32_t images,
   if (rc != CA_OK) return rc;
   const int chunks = in_chunks((int64_t)h * w, c);
   const dim3 grid((unsigned)((int64_t)images * chunks)), block(256);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_in_stats<CA_BF16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, partials, (int)h, (int)w, (int)c, (int)in_ring, chunks);
-  else hipLaunchKernelGGL(k_in_stats<CA_F16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, partials, (int)h, (int)w, (int)c, (int)in_ring, chunks);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_in_stats<DT>, grid, block, 0, (hipStream_t)stream, (const u16*)x, partials, (int)h, (int)w, (int)c, (int)in_ring, chunks));
   CA_CHECK_LAUNCH("ca_instnorm_stats");
   return CA_OK;
 }
@@ -380,12 +358,8 @@ extern "C" int ca_instnorm_apply(const void* x, const float* partials, const voi
   CA_REQUIRE(eps > 0.f, "ca_instnorm_apply: eps=%g must be positive", (double)eps);
   const int chunks = in_chunks((int64_t)h * w, c);
   const dim3 grid((unsigned)((int64_t)images * chunks)), block(256);
-  if (dtype == CA_BF16)
-    hipLaunchKernelGGL(k_in_apply<CA_BF16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, partials, (const u16*)residual, (u16*)y, (int)h, (int)w, (int)c,
-                       (int)in_ring, (int)res_ring, (int)out_pad, (int)relu, chunks, eps);
-  else
-    hipLaunchKernelGGL(k_in_apply<CA_F16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, partials, (const u16*)residual, (u16*)y, (int)h, (int)w, (int)c,
-                       (int)in_ring, (int)res_ring, (int)out_pad, (int)relu, chunks, eps);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_in_apply<DT>, grid, block, 0, (hipStream_t)stream, (const u16*)x, partials, (const u16*)residual, (u16*)y, (int)h, (int)w, (int)c,
+                       (int)in_ring, (int)res_ring, (int)out_pad, (int)relu, chunks, eps));
   CA_CHECK_LAUNCH("ca_instnorm_apply");
   return CA_OK;
 }
@@ -399,8 +373,7 @@ extern "C" int ca_convt3x3s2_gather(const void* taps, void* y, int32_t images, i
   const int64_t total = (int64_t)images * 4 * h * w * (cout / 8);
   CA_REQUIRE((total + 255) / 256 < ((int64_t)1 << 31), "ca_convt3x3s2_gather: grid too large");
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_convt_gather<CA_BF16>, grid, block, 0, (hipStream_t)stream, (const u16*)taps, (u16*)y, total, (int)h, (int)w, (int)cout);
-  else hipLaunchKernelGGL(k_convt_gather<CA_F16>, grid, block, 0, (hipStream_t)stream, (const u16*)taps, (u16*)y, total, (int)h, (int)w, (int)cout);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_convt_gather<DT>, grid, block, 0, (hipStream_t)stream, (const u16*)taps, (u16*)y, total, (int)h, (int)w, (int)cout));
   CA_CHECK_LAUNCH("ca_convt3x3s2_gather");
   return CA_OK;
 }
@@ -416,8 +389,7 @@ extern "C" int ca_lineart_conv_out(const void* x, const float* wt, const float* 
   const int64_t blocks = (int64_t)images * tx * ty;
   CA_REQUIRE(blocks < ((int64_t)1 << 31), "ca_lineart_conv_out: grid too large");
   const dim3 grid((unsigned)blocks), block(256);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_lineart_conv_out<CA_BF16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, wt, bias, logits, (int)h, (int)w, tx, ty);
-  else hipLaunchKernelGGL(k_lineart_conv_out<CA_F16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, wt, bias, logits, (int)h, (int)w, tx, ty);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_lineart_conv_out<DT>, grid, block, 0, (hipStream_t)stream, (const u16*)x, wt, bias, logits, (int)h, (int)w, tx, ty));
   CA_CHECK_LAUNCH("ca_lineart_conv_out");
   return CA_OK;
 }
@@ -426,18 +398,13 @@ extern "C" int ca_lineart_finish(const float* logits, int32_t images, int32_t h,
                                  void* stream) {
   CA_REQUIRE(logits, "ca_lineart_finish: logits are required");
   CA_REQUIRE(sizes_ok(images, h, w), "ca_lineart_finish: images=%d h=%d w=%d (each >= 1, images * h * w < 2^31)", images, h, w);
-  CA_REQUIRE(((int64_t)h * w) % 4 == 0, "ca_lineart_finish: h * w = %d x %d must be a multiple of 4", h, w);
-  CA_REQUIRE(map || control, "ca_lineart_finish: map or control is required");
-  CA_REQUIRE(rep == 1 || rep == 2, "ca_lineart_finish: rep=%d (1 or 2)", rep);
-  CA_REQUIRE(control_dtype == CA_F16 || control_dtype == CA_F32, "ca_lineart_finish: control_dtype=%d (CA_F16 or CA_F32)", control_dtype);
-  const int esize = control_dtype == CA_F32 ? 4 : 2;
-  CA_REQUIRE(((uintptr_t)logits & 15) == 0 && ((uintptr_t)map & 3) == 0 && ((uintptr_t)control & (4 * esize - 1)) == 0,
+  if (const int rc = control_out_checks("ca_lineart_finish", true, h, w, "map", map || control, rep, control_dtype)) return rc;
+  CA_REQUIRE(((uintptr_t)logits & 15) == 0 && ((uintptr_t)map & 3) == 0 && ctrl_aligned(control, control_dtype, 4),
              "ca_lineart_finish: logits must be 16-byte aligned, map 4-byte aligned, control aligned to four of its elements");
   const int64_t hw = (int64_t)h * w, total = (int64_t)images * hw;
   const dim3 grid((unsigned)((total / 4 + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (control_dtype == CA_F32) hipLaunchKernelGGL(k_lineart_finish<float>, grid, block, 0, st, logits, map, (float*)control, (int)images, hw, (int)rep);
-  else hipLaunchKernelGGL(k_lineart_finish<u16>, grid, block, 0, st, logits, map, (u16*)control, (int)images, hw, (int)rep);
+  CA_DISPATCH_CTRL(control_dtype, hipLaunchKernelGGL(k_lineart_finish<T>, grid, block, 0, st, logits, map, (T*)control, (int)images, hw, (int)rep));
   CA_CHECK_LAUNCH("ca_lineart_finish");
   return CA_OK;
 }

@@ -23,15 +23,13 @@
 //                               launch, a block per image; larger ones as statistics + apply over chunks sized to fill the chip
 //   conv_out  k_lanime_conv_out 128 -> 1 transposed convolution + bias on the VALU: a thread owns one source pixel and its four output
 //                               phases, fp32 weights through the scalar cache, fp32 accumulation in a fixed order
-//   finish    k_lanime_finish   255 - trunc(clip(tanh(t) * 127.5 + 127.5)) -> the uint8 map and / or the control tensor
+//   finish    k_lanime_finish   255 - trunc(clip(tanh(t) * 127.5 + 127.5)) -> the uint8 map and / or the control tensor (ca_annot.h)
 //
 // No launch depends on device data on the host side: the chain can be captured in a hipGraph.  No atomics: two runs give the same bits.
 #include "ca_common.h"
+#include "ca_annot.h"
 
 namespace {
-
-constexpr int64_t kMaxPixels = ((int64_t)1 << 31) - 1;
-constexpr int64_t kMaxBytes = 0x7FFFFF00;  // an operand stays below this: the kernels index elements with 64-bit offsets, the callers chunk by it
 
 enum { ACT_NONE_ = 0, ACT_RELU_ = 1, ACT_LEAKY_ = 2 };
 __device__ __forceinline__ float act3(float v, int act) { return act == ACT_RELU_ ? fmaxf(v, 0.f) : (act == ACT_LEAKY_ ? (v > 0.f ? v : 0.2f * v) : v); }
@@ -426,14 +424,6 @@ __global__ __launch_bounds__(256) void k_lanime_conv_out(const u16* __restrict__
 }
 
 // ---- tanh, quantise, invert -------------------------------------------------------------------------------------------------------------
-template <typename T>
-struct alignas(4 * sizeof(T)) Vec4 {
-  T v[4];
-};
-
-__device__ __forceinline__ void ctrl_from_level(int level, float& out) { out = __fdiv_rn((float)level, 255.0f); }
-__device__ __forceinline__ void ctrl_from_level(int level, u16& out) { out = Elem<CA_F16>::from_f(__fdiv_rn((float)level, 255.0f)); }
-
 // 4 consecutive pixels per thread (h * w % 4 == 0): one 4-byte store to the map, 16 / 8-byte stores to the control tensor
 template <typename T>
 __global__ __launch_bounds__(256) void k_lanime_finish(const float* __restrict__ pre, uint8_t* __restrict__ map, T* __restrict__ ctrl, int images, int64_t hw,
@@ -450,21 +440,10 @@ __global__ __launch_bounds__(256) void k_lanime_finish(const float* __restrict__
     e = !(e > 0.0) ? 0.0 : (e > 255.0 ? 255.0 : e);  // (a NaN counts as 0)
     level[i] = 255 - (int)e;                         // truncation, as astype(uint8) of a value in [0, 255]
   }
-  if (map) *(uint32_t*)(map + g0) = (uint32_t)level[0] | ((uint32_t)level[1] << 8) | ((uint32_t)level[2] << 16) | ((uint32_t)level[3] << 24);
-  if (ctrl) {
-    Vec4<T> o;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ctrl_from_level(level[i], o.v[i]);
-    for (int r = 0; r < rep; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) *(Vec4<T>*)(ctrl + (((int64_t)r * images + img) * 3 + c) * hw + p) = o;
-  }
+  if (map) *(uint32_t*)(map + g0) = pack_levels4(level);
+  if (ctrl) emit_control4(ctrl, images, img, hw, p, rep, level);
 }
 
-inline bool sizes_ok(int32_t images, int32_t h, int32_t w, int64_t scale = 1) {
-  return images >= 1 && h >= 1 && w >= 1 && (int64_t)images * h * w * scale <= kMaxPixels;
-}
-inline bool dtype_ok(int32_t dtype) { return dtype == CA_BF16 || dtype == CA_F16; }
 inline bool ina_c_ok(int32_t c) { return c == 64 || c == 128 || c == 256 || c == 512; }
 inline bool act_ok(int32_t a) { return a == ACT_NONE_ || a == ACT_RELU_ || a == ACT_LEAKY_; }
 
@@ -490,10 +469,7 @@ extern "C" int ca_lanime_conv_in(const uint8_t* src, const void* w_packed, const
   const int64_t blocks = (int64_t)images * tx * ty;
   CA_REQUIRE(blocks < ((int64_t)1 << 31), "ca_lanime_conv_in: grid too large");
   const dim3 grid((unsigned)blocks), block(256);
-  if (dtype == CA_BF16)
-    hipLaunchKernelGGL(k_lanime_conv_in<CA_BF16>, grid, block, 0, (hipStream_t)stream, src, (const u16*)w_packed, bias, (u16*)l0, (u16*)c0, (int)h, (int)w, tx, ty);
-  else
-    hipLaunchKernelGGL(k_lanime_conv_in<CA_F16>, grid, block, 0, (hipStream_t)stream, src, (const u16*)w_packed, bias, (u16*)l0, (u16*)c0, (int)h, (int)w, tx, ty);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_lanime_conv_in<DT>, grid, block, 0, (hipStream_t)stream, src, (const u16*)w_packed, bias, (u16*)l0, (u16*)c0, (int)h, (int)w, tx, ty));
   CA_CHECK_LAUNCH("ca_lanime_conv_in");
   return CA_OK;
 }
@@ -516,10 +492,7 @@ extern "C" int ca_conv4x4s2(const void* x, const void* wt, const float* bias, vo
   const int64_t blocks = (int64_t)images * tx * ty * (cout / 128);
   CA_REQUIRE(blocks < ((int64_t)1 << 31), "ca_conv4x4s2: grid too large");
   const dim3 grid((unsigned)blocks);
-  if (dtype == CA_BF16)
-    launch_tile<CA_BF16, 4, 2, 32, 4>(4, grid, (hipStream_t)stream, (const u16*)x, (const u16*)wt, bias, (u16*)y, h, w, cin, cout, gh, gw, tx, ty, relu);
-  else
-    launch_tile<CA_F16, 4, 2, 32, 4>(4, grid, (hipStream_t)stream, (const u16*)x, (const u16*)wt, bias, (u16*)y, h, w, cin, cout, gh, gw, tx, ty, relu);
+  CA_DISPATCH_DT(dtype, launch_tile<DT, 4, 2, 32, 4>(4, grid, (hipStream_t)stream, (const u16*)x, (const u16*)wt, bias, (u16*)y, h, w, cin, cout, gh, gw, tx, ty, relu));
   CA_CHECK_LAUNCH("ca_conv4x4s2");
   return CA_OK;
 }
@@ -557,13 +530,8 @@ extern "C" int ca_convt4x4s2(const void* x, const void* w_phase, void* y, int32_
   const dim3 grid((unsigned)blocks);
   hipStream_t st = (hipStream_t)stream;
   const u16 *xs = (const u16*)x, *ws = (const u16*)w_phase;
-  if (dtype == CA_BF16) {
-    if (ctl == 8) launch_tile<CA_BF16, 2, 1, 64, 8>(rt, grid, st, xs, ws, nullptr, (u16*)y, h, w, cin, cout, h, w, tx, ty, 0);
-    else launch_tile<CA_BF16, 2, 1, 64, 4>(rt, grid, st, xs, ws, nullptr, (u16*)y, h, w, cin, cout, h, w, tx, ty, 0);
-  } else {
-    if (ctl == 8) launch_tile<CA_F16, 2, 1, 64, 8>(rt, grid, st, xs, ws, nullptr, (u16*)y, h, w, cin, cout, h, w, tx, ty, 0);
-    else launch_tile<CA_F16, 2, 1, 64, 4>(rt, grid, st, xs, ws, nullptr, (u16*)y, h, w, cin, cout, h, w, tx, ty, 0);
-  }
+  CA_DISPATCH_DT(dtype, if (ctl == 8) launch_tile<DT, 2, 1, 64, 8>(rt, grid, st, xs, ws, nullptr, (u16*)y, h, w, cin, cout, h, w, tx, ty, 0);
+    else launch_tile<DT, 2, 1, 64, 4>(rt, grid, st, xs, ws, nullptr, (u16*)y, h, w, cin, cout, h, w, tx, ty, 0));
   CA_CHECK_LAUNCH("ca_convt4x4s2");
   return CA_OK;
 }
@@ -598,16 +566,12 @@ extern "C" int ca_instnorm_act(const void* x, float* partials, void* y0, int32_t
   const dim3 grid((unsigned)((int64_t)images * chunks)), block(256);
   hipStream_t st = (hipStream_t)stream;
   if (chunks == 1) {  // one launch: a block per image computes its sums and applies them
-    if (dtype == CA_BF16) hipLaunchKernelGGL((k_ina_apply<CA_BF16, true>), grid, block, 0, st, (const u16*)x, (const float*)partials, o, hw, (int)c, 1, per, eps);
-    else hipLaunchKernelGGL((k_ina_apply<CA_F16, true>), grid, block, 0, st, (const u16*)x, (const float*)partials, o, hw, (int)c, 1, per, eps);
+    CA_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_ina_apply<DT, true>), grid, block, 0, st, (const u16*)x, (const float*)partials, o, hw, (int)c, 1, per, eps));
   } else {
-    if (dtype == CA_BF16) {
-      hipLaunchKernelGGL(k_ina_stats<CA_BF16>, grid, block, 0, st, (const u16*)x, partials, hw, (int)c, chunks, per);
-      hipLaunchKernelGGL((k_ina_apply<CA_BF16, false>), grid, block, 0, st, (const u16*)x, (const float*)partials, o, hw, (int)c, chunks, per, eps);
-    } else {
-      hipLaunchKernelGGL(k_ina_stats<CA_F16>, grid, block, 0, st, (const u16*)x, partials, hw, (int)c, chunks, per);
-      hipLaunchKernelGGL((k_ina_apply<CA_F16, false>), grid, block, 0, st, (const u16*)x, (const float*)partials, o, hw, (int)c, chunks, per, eps);
-    }
+    CA_DISPATCH_DT(dtype, {
+      hipLaunchKernelGGL(k_ina_stats<DT>, grid, block, 0, st, (const u16*)x, partials, hw, (int)c, chunks, per);
+      hipLaunchKernelGGL((k_ina_apply<DT, false>), grid, block, 0, st, (const u16*)x, (const float*)partials, o, hw, (int)c, chunks, per, eps);
+    });
   }
   CA_CHECK_LAUNCH("ca_instnorm_act");
   return CA_OK;
@@ -625,8 +589,7 @@ extern "C" int ca_lanime_conv_out(const void* x, const float* wt, const float* b
   const int64_t blocks = (int64_t)images * tx * ty;
   CA_REQUIRE(blocks < ((int64_t)1 << 31), "ca_lanime_conv_out: grid too large");
   const dim3 grid((unsigned)blocks), block(256);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_lanime_conv_out<CA_BF16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, wt, bias, out, (int)h, (int)w, tx, ty);
-  else hipLaunchKernelGGL(k_lanime_conv_out<CA_F16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, wt, bias, out, (int)h, (int)w, tx, ty);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_lanime_conv_out<DT>, grid, block, 0, (hipStream_t)stream, (const u16*)x, wt, bias, out, (int)h, (int)w, tx, ty));
   CA_CHECK_LAUNCH("ca_lanime_conv_out");
   return CA_OK;
 }
@@ -635,18 +598,13 @@ extern "C" int ca_lanime_finish(const float* pre, int32_t images, int32_t h, int
                                 void* stream) {
   CA_REQUIRE(pre, "ca_lanime_finish: the pre-tanh values are required");
   CA_REQUIRE(sizes_ok(images, h, w), "ca_lanime_finish: images=%d h=%d w=%d (each >= 1, images * h * w < 2^31)", images, h, w);
-  CA_REQUIRE(((int64_t)h * w) % 4 == 0, "ca_lanime_finish: h * w = %d x %d must be a multiple of 4", h, w);
-  CA_REQUIRE(map || control, "ca_lanime_finish: map or control is required");
-  CA_REQUIRE(rep == 1 || rep == 2, "ca_lanime_finish: rep=%d (1 or 2)", rep);
-  CA_REQUIRE(control_dtype == CA_F16 || control_dtype == CA_F32, "ca_lanime_finish: control_dtype=%d (CA_F16 or CA_F32)", control_dtype);
-  const int esize = control_dtype == CA_F32 ? 4 : 2;
-  CA_REQUIRE(((uintptr_t)pre & 15) == 0 && ((uintptr_t)map & 3) == 0 && ((uintptr_t)control & (4 * esize - 1)) == 0,
+  if (const int rc = control_out_checks("ca_lanime_finish", true, h, w, "map", map || control, rep, control_dtype)) return rc;
+  CA_REQUIRE(((uintptr_t)pre & 15) == 0 && ((uintptr_t)map & 3) == 0 && ctrl_aligned(control, control_dtype, 4),
              "ca_lanime_finish: pre must be 16-byte aligned, map 4-byte aligned, control aligned to four of its elements");
   const int64_t hw = (int64_t)h * w, total = (int64_t)images * hw;
   const dim3 grid((unsigned)((total / 4 + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (control_dtype == CA_F32) hipLaunchKernelGGL(k_lanime_finish<float>, grid, block, 0, st, pre, map, (float*)control, (int)images, hw, (int)rep);
-  else hipLaunchKernelGGL(k_lanime_finish<u16>, grid, block, 0, st, pre, map, (u16*)control, (int)images, hw, (int)rep);
+  CA_DISPATCH_CTRL(control_dtype, hipLaunchKernelGGL(k_lanime_finish<T>, grid, block, 0, st, pre, map, (T*)control, (int)images, hw, (int)rep));
   CA_CHECK_LAUNCH("ca_lanime_finish");
   return CA_OK;
 }

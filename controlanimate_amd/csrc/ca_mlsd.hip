@@ -3,7 +3,7 @@
 // its decode and OpenCV's line iterator).  The stem, the two 3x3 convolutions of a block B and the second convolution of block C run on
 // ca_conv3x3, every 1x1 convolution on ca_gemm; around them:
 //
-//   prep      k_mlsd_prep     uint8 RGB [n,H,W,3] -> [n,H,W,8]: x / 127.5 - 1 in channels 0..2, the constant 1 / 127.5 - 1 in channel 3
+//   prep      MlsdFill        uint8 RGB [n,H,W,3] -> [n,H,W,8]: x / 127.5 - 1 in channels 0..2, the constant 1 / 127.5 - 1 in channel 3
 //                             (the detector's channel of ones), zeros in 4..7 (the stem's weight is zero-padded to 8 input channels)
 //   dw        k_dwconv3x3     depthwise 3x3, stride 1 (padding 1) or 2 (one row / column of zeros after, none before), fp32 bias,
 //                             optional ReLU6.  A thread owns 8 channels (16 bytes) of one output column and walks down a strip of
@@ -20,35 +20,26 @@
 //                             list; the exact top 200 by (score descending, index ascending) through an 8-pass radix select on the
 //                             64-bit key (score bits, ~index); distance test, float64 endpoints; segments in rank order
 //   draw      k_mlsd_draw     one lane per segment: OpenCV's clipLine and 8-connected line iterator, byte stores of 255
-//             k_mlsd_emit     the map -> the control tensor [rep * n,3,H,W]
+//             k_mlsd_emit     the map -> the control tensor [rep * n,3,H,W] (ca_annot.h)
 //
 // No launch depends on device data on the host side: the chain can be captured in a hipGraph.  The only atomics are integer LDS
 // counters whose arrival order never reaches the output (the candidates are ranked afterwards): two runs give the same bits.
 #include "ca_common.h"
+#include "ca_annot.h"
 
 namespace {
 
-constexpr int64_t kMaxPixels = ((int64_t)1 << 31) - 1;
 constexpr int kTopK = CA_MLSD_TOPK;
 
-inline bool sizes_ok(int32_t images, int32_t h, int32_t w, int64_t scale = 1) {
-  return images >= 1 && h >= 1 && w >= 1 && (int64_t)images * h * w * scale <= kMaxPixels;
-}
-inline bool dtype_ok(int32_t dtype) { return dtype == CA_BF16 || dtype == CA_F16; }
-
 // ---- prep ------------------------------------------------------------------------------------------------------------------------
-template <int DT>
-__global__ __launch_bounds__(256) void k_mlsd_prep(const uint8_t* __restrict__ src, u16* __restrict__ dst, int64_t pixels) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= pixels) return;
-  const uint8_t* s = src + p * 3;
-  float f[8];
+struct MlsdFill {
+  __device__ __forceinline__ void operator()(const uint8_t* s, float f[8]) const {
 #pragma unroll
-  for (int c = 0; c < 3; ++c) f[c] = __fdiv_rn((float)s[c], 127.5f) - 1.0f;
-  f[3] = __fdiv_rn(1.0f, 127.5f) - 1.0f;
-  f[4] = f[5] = f[6] = f[7] = 0.f;
-  st16(dst + p * 8, pack8<DT>(f));
-}
+    for (int c = 0; c < 3; ++c) f[c] = __fdiv_rn((float)s[c], 127.5f) - 1.0f;
+    f[3] = __fdiv_rn(1.0f, 127.5f) - 1.0f;
+    f[4] = f[5] = f[6] = f[7] = 0.f;
+  }
+};
 
 // ---- depthwise 3x3 ---------------------------------------------------------------------------------------------------------------
 constexpr int DW_ROWS = 8;  // output rows per strip
@@ -396,40 +387,22 @@ __global__ __launch_bounds__(256) void k_mlsd_draw(const int32_t* __restrict__ s
 }
 
 template <typename T>
-struct alignas(4 * sizeof(T)) Vec4 {
-  T v[4];
-};
-__device__ __forceinline__ void ctrl_from_level(int level, float& out) { out = __fdiv_rn((float)level, 255.0f); }
-__device__ __forceinline__ void ctrl_from_level(int level, u16& out) { out = Elem<CA_F16>::from_f(__fdiv_rn((float)level, 255.0f)); }
-
-template <typename T>
 __global__ __launch_bounds__(256) void k_mlsd_emit(const uint8_t* __restrict__ map, T* __restrict__ ctrl, int images, int64_t hw, int rep) {
   const int64_t g0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
   if (g0 >= images * hw) return;
   const int img = (int)(g0 / hw);
   const int64_t p = g0 - img * hw;
   const uint32_t four = *(const uint32_t*)(map + g0);
-  Vec4<T> o;
+  int level[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) ctrl_from_level((int)((four >> (8 * i)) & 255u), o.v[i]);
-  for (int r = 0; r < rep; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) *(Vec4<T>*)(ctrl + (((int64_t)r * images + img) * 3 + c) * hw + p) = o;
+  for (int i = 0; i < 4; ++i) level[i] = (int)((four >> (8 * i)) & 255u);
+  emit_control4(ctrl, images, img, hw, p, rep, level);
 }
 
 }  // namespace
 
 extern "C" int ca_mlsd_prep(const uint8_t* src, void* dst, int32_t images, int32_t h, int32_t w, int32_t dtype, void* stream) {
-  CA_REQUIRE(src && dst, "ca_mlsd_prep: src and dst are required");
-  CA_REQUIRE(sizes_ok(images, h, w), "ca_mlsd_prep: images=%d h=%d w=%d (each >= 1, images * h * w < 2^31)", images, h, w);
-  CA_REQUIRE(dtype_ok(dtype), "ca_mlsd_prep: dtype %d", dtype);
-  CA_REQUIRE(((uintptr_t)dst & 15) == 0, "ca_mlsd_prep: dst must be 16-byte aligned");
-  const int64_t pixels = (int64_t)images * h * w;
-  const dim3 grid((unsigned)((pixels + 255) / 256)), block(256);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_mlsd_prep<CA_BF16>, grid, block, 0, (hipStream_t)stream, src, (u16*)dst, pixels);
-  else hipLaunchKernelGGL(k_mlsd_prep<CA_F16>, grid, block, 0, (hipStream_t)stream, src, (u16*)dst, pixels);
-  CA_CHECK_LAUNCH("ca_mlsd_prep");
-  return CA_OK;
+  return launch_rgb8_prep("ca_mlsd_prep", "src and dst", src && dst, src, dst, images, h, w, dtype, true, "dst must be 16-byte aligned", stream, MlsdFill{});
 }
 
 extern "C" int ca_dwconv3x3(const void* x, const void* wt, const float* bias, void* y, int32_t images, int32_t h, int32_t w, int32_t c, int32_t stride,
@@ -453,13 +426,8 @@ extern "C" int ca_dwconv3x3(const void* x, const void* wt, const float* bias, vo
 #define CA_DW_LAUNCH(DT, S)                                                                                                                                   \
   hipLaunchKernelGGL((k_dwconv3x3<DT, S>), grid, block, 0, st, (const u16*)x, (const u16*)wt, bias, (u16*)y, total, (int)h, (int)w, ho, wo, (int)c, strips, \
                      (int)relu6)
-  if (dtype == CA_BF16) {
-    if (stride == 1) CA_DW_LAUNCH(CA_BF16, 1);
-    else CA_DW_LAUNCH(CA_BF16, 2);
-  } else {
-    if (stride == 1) CA_DW_LAUNCH(CA_F16, 1);
-    else CA_DW_LAUNCH(CA_F16, 2);
-  }
+  CA_DISPATCH_DT(dtype, if (stride == 1) CA_DW_LAUNCH(DT, 1);
+    else CA_DW_LAUNCH(DT, 2));
 #undef CA_DW_LAUNCH
   CA_CHECK_LAUNCH("ca_dwconv3x3");
   return CA_OK;
@@ -477,8 +445,7 @@ extern "C" int ca_upsample2x_bilinear_ac(const void* x, void* y, int32_t images,
   const int64_t total = (int64_t)images * 4 * h * w * (c / 8);
   CA_REQUIRE((total + 255) / 256 < ((int64_t)1 << 31), "ca_upsample2x_bilinear_ac: grid too large");
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_up2_ac<CA_BF16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, (u16*)y, total, (int)h, (int)w, (int)c, ld, (int)col0);
-  else hipLaunchKernelGGL(k_up2_ac<CA_F16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, (u16*)y, total, (int)h, (int)w, (int)c, ld, (int)col0);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_up2_ac<DT>, grid, block, 0, (hipStream_t)stream, (const u16*)x, (u16*)y, total, (int)h, (int)w, (int)c, ld, (int)col0));
   CA_CHECK_LAUNCH("ca_upsample2x_bilinear_ac");
   return CA_OK;
 }
@@ -498,9 +465,7 @@ extern "C" int ca_conv3x3_dil(const void* x, const void* wt, const float* bias, 
   const int64_t blocks = (int64_t)images * tx * ty;
   CA_REQUIRE(blocks < ((int64_t)1 << 31), "ca_conv3x3_dil: grid too large");
   const dim3 grid((unsigned)blocks), block(256);
-  if (dtype == CA_BF16)
-    hipLaunchKernelGGL(k_conv3x3_dil<CA_BF16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, (const u16*)wt, bias, (u16*)y, (int)h, (int)w, tx, ty, (int)relu);
-  else hipLaunchKernelGGL(k_conv3x3_dil<CA_F16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, (const u16*)wt, bias, (u16*)y, (int)h, (int)w, tx, ty, (int)relu);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_conv3x3_dil<DT>, grid, block, 0, (hipStream_t)stream, (const u16*)x, (const u16*)wt, bias, (u16*)y, (int)h, (int)w, tx, ty, (int)relu));
   CA_CHECK_LAUNCH("ca_conv3x3_dil");
   return CA_OK;
 }
@@ -531,11 +496,8 @@ extern "C" int ca_mlsd_draw(const int32_t* segments, const int32_t* count, int32
   CA_REQUIRE(segments && count && map, "ca_mlsd_draw: segments, count and map are required");
   CA_REQUIRE(sizes_ok(images, h, w), "ca_mlsd_draw: images=%d h=%d w=%d (each >= 1, images * h * w < 2^31)", images, h, w);
   CA_REQUIRE((int64_t)images * kTopK < kMaxPixels, "ca_mlsd_draw: too many images");
-  CA_REQUIRE(((int64_t)h * w) % 4 == 0, "ca_mlsd_draw: h * w = %d x %d must be a multiple of 4", h, w);
-  CA_REQUIRE(rep == 1 || rep == 2, "ca_mlsd_draw: rep=%d (1 or 2)", rep);
-  CA_REQUIRE(control_dtype == CA_F16 || control_dtype == CA_F32, "ca_mlsd_draw: control_dtype=%d (CA_F16 or CA_F32)", control_dtype);
-  const int esize = control_dtype == CA_F32 ? 4 : 2;
-  CA_REQUIRE((((uintptr_t)segments | (uintptr_t)count | (uintptr_t)map) & 3) == 0 && ((uintptr_t)control & (4 * esize - 1)) == 0,
+  if (const int rc = control_out_checks("ca_mlsd_draw", true, h, w, nullptr, true, rep, control_dtype)) return rc;  // (the map is required above)
+  CA_REQUIRE((((uintptr_t)segments | (uintptr_t)count | (uintptr_t)map) & 3) == 0 && ctrl_aligned(control, control_dtype, 4),
              "ca_mlsd_draw: segments, count and map must be 4-byte aligned, control aligned to four of its elements");
   hipStream_t st = (hipStream_t)stream;
   const int64_t hw = (int64_t)h * w, total = (int64_t)images * hw;
@@ -547,8 +509,7 @@ extern "C" int ca_mlsd_draw(const int32_t* segments, const int32_t* count, int32
   CA_CHECK_LAUNCH("ca_mlsd_draw");
   if (control) {
     const dim3 grid((unsigned)((total / 4 + 255) / 256)), block(256);
-    if (control_dtype == CA_F32) hipLaunchKernelGGL(k_mlsd_emit<float>, grid, block, 0, st, (const uint8_t*)map, (float*)control, (int)images, hw, (int)rep);
-    else hipLaunchKernelGGL(k_mlsd_emit<u16>, grid, block, 0, st, (const uint8_t*)map, (u16*)control, (int)images, hw, (int)rep);
+    CA_DISPATCH_CTRL(control_dtype, hipLaunchKernelGGL(k_mlsd_emit<T>, grid, block, 0, st, (const uint8_t*)map, (T*)control, (int)images, hw, (int)rep));
     CA_CHECK_LAUNCH("ca_mlsd_draw");
   }
   return CA_OK;

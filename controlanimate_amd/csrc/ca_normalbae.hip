@@ -18,21 +18,15 @@
 //   normalize  k_nbae_normalize   norm_normalize: xyz / (|xyz| + 1e-10), kappa = elu(k) + 1 + min_kappa, fp32
 //   refine     k_nbae_refine      one refinement stage in one launch: interpolation into LDS, four layers on the MFMA, norm_normalize
 //   finish     k_nbae_finish      trunc(clip(clip((xyz + 1) * 0.5, 0, 1) * 255, 0, 255)) -> the uint8 map [n,H,W,3] and / or the control tensor
+//                                 (ca_annot.h; one level per channel)
 //
 // Compiled with -ffp-contract=off: the finish and the normalisation round operation by operation, as numpy and torch do; the sums of the
 // convolutions use fmaf explicitly.  No launch reads device data on the host, there are no floating-point atomics: two runs give the
 // same bits, and the chain can be captured in a hipGraph.
 #include "ca_common.h"
+#include "ca_annot.h"
 
 namespace {
-
-constexpr int64_t kMaxPixels = ((int64_t)1 << 31) - 1;
-constexpr int64_t kMaxBytes = 0x7FFFFF00;
-
-inline bool sizes_ok(int32_t images, int32_t h, int32_t w, int64_t scale = 1) {
-  return images >= 1 && h >= 1 && w >= 1 && (int64_t)images * h * w * scale <= kMaxPixels;
-}
-inline bool dtype_ok(int32_t dtype) { return dtype == CA_BF16 || dtype == CA_F16; }
 
 // TensorFlow "SAME": out = ceil(in / stride), total = max((out - 1) * stride + k - in, 0), total / 2 of it in front
 struct SamePad {
@@ -423,13 +417,6 @@ __global__ __launch_bounds__(256) void k_nbae_refine(const u16* __restrict__ fea
 }
 
 // ---- finish ------------------------------------------------------------------------------------------------------------------------------
-template <typename T>
-struct alignas(4 * sizeof(T)) Vec4 {
-  T v[4];
-};
-__device__ __forceinline__ void ctrl_from_level(int level, float& out) { out = __fdiv_rn((float)level, 255.0f); }
-__device__ __forceinline__ void ctrl_from_level(int level, u16& out) { out = Elem<CA_F16>::from_f(__fdiv_rn((float)level, 255.0f)); }
-
 // 4 consecutive pixels per thread (h * w % 4 == 0): 12 bytes of the map, 16 / 8-byte stores to the control tensor
 template <typename T>
 __global__ __launch_bounds__(256) void k_nbae_finish(const float* __restrict__ pred, uint8_t* __restrict__ map, T* __restrict__ ctrl, int images, int64_t hw, int rep) {
@@ -458,14 +445,10 @@ __global__ __launch_bounds__(256) void k_nbae_finish(const float* __restrict__ p
     m[0] = wds[0], m[1] = wds[1], m[2] = wds[2];
   }
   if (ctrl) {
-    for (int r = 0; r < rep; ++r)
+    Vec4<T> o[3];  // one level per channel
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        Vec4<T> o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ctrl_from_level(level[i][ch], o.v[i]);
-        *(Vec4<T>*)(ctrl + (((int64_t)r * images + img) * 3 + ch) * hw + p) = o;
-      }
+    for (int k = 0; k < 12; ++k) ctrl_from_level(level[k & 3][k >> 2], o[k >> 2].v[k & 3]);
+    emit_vec4(ctrl, images, img, hw, p, rep, o);
   }
 }
 
@@ -515,8 +498,7 @@ extern "C" int ca_nbae_stem(const uint8_t* src, const float* wt, const float* bi
   CA_REQUIRE((int64_t)images * (h / 2) * (w / 2) * cout * 2 <= kMaxBytes, "ca_nbae_stem: images=%d h=%d w=%d: y would pass 2^31 bytes", images, h, w);
   const int64_t total = (int64_t)images * (h / 2) * (w / 2) * (cout / 8);
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_nbae_stem<CA_BF16>, grid, block, 0, (hipStream_t)stream, src, wt, bias, (u16*)y, total, (int)h, (int)w, (int)cout);
-  else hipLaunchKernelGGL(k_nbae_stem<CA_F16>, grid, block, 0, (hipStream_t)stream, src, wt, bias, (u16*)y, total, (int)h, (int)w, (int)cout);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_nbae_stem<DT>, grid, block, 0, (hipStream_t)stream, src, wt, bias, (u16*)y, total, (int)h, (int)w, (int)cout));
   CA_CHECK_LAUNCH("ca_nbae_stem");
   return CA_OK;
 }
@@ -542,8 +524,7 @@ extern "C" int ca_dwconv_same(const void* x, const void* wt, const float* bias, 
   CA_REQUIRE(blocks < ((int64_t)1 << 31) && g.chunks < ((int64_t)1 << 30), "ca_dwconv_same: grid too large");
   const dim3 grid((unsigned)blocks);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == CA_BF16) launch_dw_dt<CA_BF16>(ksize, stride, grid, st, x, wt, bias, y, partials, h, w, c, g);
-  else launch_dw_dt<CA_F16>(ksize, stride, grid, st, x, wt, bias, y, partials, h, w, c, g);
+  CA_DISPATCH_DT(dtype, launch_dw_dt<DT>(ksize, stride, grid, st, x, wt, bias, y, partials, h, w, c, g));
   CA_CHECK_LAUNCH("ca_dwconv_same");
   const int cblocks = ceil_div_i(c, 64);
   hipLaunchKernelGGL(k_dw_sum_finish, dim3((unsigned)(images * cblocks)), dim3(256), 0, st, (const float*)partials, sums, (int)g.chunks, (int)c, cblocks);
@@ -574,8 +555,7 @@ extern "C" int ca_scale_channels(const void* x, const float* gate, void* y, int3
   CA_REQUIRE(x == y || (const char*)y + bytes <= (const char*)x || (const char*)x + bytes <= (const char*)y, "ca_scale_channels: y is x or does not overlap it");
   const int64_t total = (int64_t)images * pixels * (c / 8);
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_scale_channels<CA_BF16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, gate, (u16*)y, total, pixels, (int)c);
-  else hipLaunchKernelGGL(k_scale_channels<CA_F16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, gate, (u16*)y, total, pixels, (int)c);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_scale_channels<DT>, grid, block, 0, (hipStream_t)stream, (const u16*)x, gate, (u16*)y, total, pixels, (int)c));
   CA_CHECK_LAUNCH("ca_scale_channels");
   return CA_OK;
 }
@@ -590,8 +570,7 @@ extern "C" int ca_nbae_cat_pred(const float* pred, void* y, int32_t images, int3
   CA_REQUIRE((((uintptr_t)pred | (uintptr_t)y) & 15) == 0, "ca_nbae_cat_pred: pred and y must be 16-byte aligned");
   const int64_t total = (int64_t)images * h * w * 4;
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_nbae_cat_pred<CA_BF16>, grid, block, 0, (hipStream_t)stream, pred, (u16*)y, total, (int)h, (int)w, ld, (int)col0);
-  else hipLaunchKernelGGL(k_nbae_cat_pred<CA_F16>, grid, block, 0, (hipStream_t)stream, pred, (u16*)y, total, (int)h, (int)w, ld, (int)col0);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_nbae_cat_pred<DT>, grid, block, 0, (hipStream_t)stream, pred, (u16*)y, total, (int)h, (int)w, ld, (int)col0));
   CA_CHECK_LAUNCH("ca_nbae_cat_pred");
   return CA_OK;
 }
@@ -623,15 +602,9 @@ extern "C" int ca_nbae_refine(const void* feat, const float* pred, const void* w
 #define CA_RF_LAUNCH(DT, C)                                                                                                                                  \
   hipLaunchKernelGGL((k_nbae_refine<DT, C>), grid, block, 0, st, (const u16*)feat, pred, (const u16*)w0, (const u16*)w1, (const u16*)w2, (const u16*)w3, b0, b1, b2, b3, \
                      out, total, (int)h, (int)w, min_kappa)
-  if (dtype == CA_BF16) {
-    if (c == 128) CA_RF_LAUNCH(CA_BF16, 128);
-    else if (c == 256) CA_RF_LAUNCH(CA_BF16, 256);
-    else CA_RF_LAUNCH(CA_BF16, 512);
-  } else {
-    if (c == 128) CA_RF_LAUNCH(CA_F16, 128);
-    else if (c == 256) CA_RF_LAUNCH(CA_F16, 256);
-    else CA_RF_LAUNCH(CA_F16, 512);
-  }
+  CA_DISPATCH_DT(dtype, if (c == 128) CA_RF_LAUNCH(DT, 128);
+    else if (c == 256) CA_RF_LAUNCH(DT, 256);
+    else CA_RF_LAUNCH(DT, 512));
 #undef CA_RF_LAUNCH
   CA_CHECK_LAUNCH("ca_nbae_refine");
   return CA_OK;
@@ -640,17 +613,13 @@ extern "C" int ca_nbae_refine(const void* feat, const float* pred, const void* w
 extern "C" int ca_nbae_finish(const float* pred, int32_t images, int32_t h, int32_t w, uint8_t* map, void* control, int32_t rep, int32_t control_dtype, void* stream) {
   CA_REQUIRE(pred, "ca_nbae_finish: the prediction is required");
   CA_REQUIRE(sizes_ok(images, h, w, 3), "ca_nbae_finish: images=%d h=%d w=%d (each >= 1, 3 * images * h * w < 2^31)", images, h, w);
-  CA_REQUIRE(((int64_t)h * w) % 4 == 0, "ca_nbae_finish: h * w = %d x %d must be a multiple of 4", h, w);
-  CA_REQUIRE(map || control, "ca_nbae_finish: map or control is required");
-  CA_REQUIRE(rep == 1 || rep == 2, "ca_nbae_finish: rep=%d (1 or 2)", rep);
-  CA_REQUIRE(control_dtype == CA_F16 || control_dtype == CA_F32, "ca_nbae_finish: control_dtype=%d (CA_F16 or CA_F32)", control_dtype);
-  CA_REQUIRE(((uintptr_t)pred & 15) == 0 && ((uintptr_t)map & 3) == 0 && ((uintptr_t)control & (control_dtype == CA_F32 ? 15 : 7)) == 0,
+  if (const int rc = control_out_checks("ca_nbae_finish", true, h, w, "map", map || control, rep, control_dtype)) return rc;
+  CA_REQUIRE(((uintptr_t)pred & 15) == 0 && ((uintptr_t)map & 3) == 0 && ctrl_aligned(control, control_dtype, 4),
              "ca_nbae_finish: pred must be 16-byte aligned, map 4-byte aligned, control aligned to four of its elements");
   const int64_t hw = (int64_t)h * w, quads = (int64_t)images * hw / 4;
   const dim3 grid((unsigned)((quads + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (control_dtype == CA_F32) hipLaunchKernelGGL(k_nbae_finish<float>, grid, block, 0, st, pred, map, (float*)control, (int)images, hw, (int)rep);
-  else hipLaunchKernelGGL(k_nbae_finish<u16>, grid, block, 0, st, pred, map, (u16*)control, (int)images, hw, (int)rep);
+  CA_DISPATCH_CTRL(control_dtype, hipLaunchKernelGGL(k_nbae_finish<T>, grid, block, 0, st, pred, map, (T*)control, (int)images, hw, (int)rep));
   CA_CHECK_LAUNCH("ca_nbae_finish");
   return CA_OK;
 }

@@ -27,11 +27,10 @@
 // Every loop of the decode is bounded by a compile-time constant.  No launch depends on device data on the host side: the chain can be
 // captured in a hipGraph.  atomicMax / atomicOr only where the result does not depend on the order.
 #include "ca_common.h"
+#include "ca_annot.h"
 
 namespace {
 
-constexpr int64_t kMaxPixels = ((int64_t)1 << 31) - 1;
-constexpr int64_t kMaxBytes = 0x7FFFFF00;
 constexpr int kParts = 18, kLimbs = 19, kDrawLimbs = 17, kPrims = kDrawLimbs + kParts;
 constexpr int kFaceParts = CA_FACE_PARTS, kPrimsFace = kPrims + kFaceParts;  // ca_pose_draw_faces: a person's 71 discs follow the body's primitives
 constexpr int kMaxPeaks = CA_POSE_MAX_PEAKS, kMaxPeople = CA_POSE_MAX_PEOPLE;
@@ -49,9 +48,6 @@ __constant__ unsigned char c_color[kParts][3] = {{255, 0, 0},   {255, 85, 0},  {
                                                  {0, 0, 255},   {85, 0, 255},  {170, 0, 255}, {255, 0, 255}, {255, 0, 170}, {255, 0, 85}};
 __constant__ int c_circle_half[5] = {4, 3, 3, 2, 0};  // cv2.circle(radius 4, filled): half width of the row |dy|
 __constant__ int c_disc_half[4] = {3, 2, 2, 0};       // ... of radius 3 (draw_facepose)
-
-inline bool dtype_ok(int32_t dtype) { return dtype == CA_BF16 || dtype == CA_F16; }
-inline bool sizes_ok(int32_t images, int32_t h, int32_t w) { return images >= 1 && h >= 1 && w >= 1 && (int64_t)images * h * w <= kMaxPixels; }
 
 // ---- prep ---------------------------------------------------------------------------------------------------------------------------
 // A thread owns one pixel of the padded input.  ofs / cnt / wgt per destination index of an axis: source index of the first tap, number
@@ -895,13 +891,6 @@ __global__ __launch_bounds__(64) void k_hand_raster(const int32_t* __restrict__ 
 }
 
 template <typename T>
-__device__ __forceinline__ T ctrl_of(int level);
-template <>
-__device__ __forceinline__ float ctrl_of<float>(int level) { return __fdiv_rn((float)level, 255.0f); }
-template <>
-__device__ __forceinline__ u16 ctrl_of<u16>(int level) { return Elem<CA_F16>::from_f(__fdiv_rn((float)level, 255.0f)); }
-
-template <typename T>
 __global__ __launch_bounds__(256) void k_pose_resolve(const unsigned* __restrict__ index, uint8_t* __restrict__ map, T* __restrict__ ctrl, int images, int64_t hw,
                                                       int rep, int prims, int hands) {
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -925,11 +914,7 @@ __global__ __launch_bounds__(256) void k_pose_resolve(const unsigned* __restrict
 #pragma unroll
     for (int c = 0; c < 3; ++c) map[g * 3 + c] = (uint8_t)rgb[c];
   }
-  if (ctrl) {
-    for (int r = 0; r < rep; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) ctrl[(((int64_t)r * images + img) * 3 + c) * hw + p] = ctrl_of<T>(rgb[c]);
-  }
+  if (ctrl) emit_control1(ctrl, images, img, hw, p, rep, rgb);  // (ca_annot.h: one level per channel)
 }
 
 }  // namespace
@@ -946,12 +931,8 @@ extern "C" int ca_pose_prep(const uint8_t* frames, void* out, const int32_t* xof
              "ca_pose_prep: out must be 16-byte aligned, the tables 4-byte aligned");
   const int64_t total = (int64_t)images * hp * wp;
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dtype == CA_BF16)
-    hipLaunchKernelGGL(k_pose_prep<CA_BF16>, grid, block, 0, (hipStream_t)stream, frames, (u16*)out, xofs, xcnt, xw, yofs, ycnt, yw, total, (int)h, (int)w, (int)hs, (int)ws,
-                       (int)hp, (int)wp);
-  else
-    hipLaunchKernelGGL(k_pose_prep<CA_F16>, grid, block, 0, (hipStream_t)stream, frames, (u16*)out, xofs, xcnt, xw, yofs, ycnt, yw, total, (int)h, (int)w, (int)hs, (int)ws,
-                       (int)hp, (int)wp);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_pose_prep<DT>, grid, block, 0, (hipStream_t)stream, frames, (u16*)out, xofs, xcnt, xw, yofs, ycnt, yw, total, (int)h, (int)w, (int)hs, (int)ws,
+                       (int)hp, (int)wp));
   CA_CHECK_LAUNCH("ca_pose_prep");
   return CA_OK;
 }
@@ -1089,10 +1070,9 @@ extern "C" int ca_pose_draw(const int32_t* coords, const int32_t* people, const 
   CA_REQUIRE(map || control, "ca_pose_draw: map or control is required");
   CA_REQUIRE(sizes_ok(images, h, w) && images <= 65535 && h <= kMaxSide && w <= kMaxSide,
              "ca_pose_draw: images=%d h=%d w=%d (each >= 1, images <= 65535, h and w <= %d, images * h * w < 2^31)", images, h, w, kMaxSide);
-  CA_REQUIRE(rep == 1 || rep == 2, "ca_pose_draw: rep=%d (1 or 2)", rep);
-  CA_REQUIRE(control_dtype == CA_F16 || control_dtype == CA_F32, "ca_pose_draw: control_dtype=%d (CA_F16 or CA_F32)", control_dtype);
+  if (const int rc = control_out_checks("ca_pose_draw", false, h, w, nullptr, true, rep, control_dtype)) return rc;
   CA_REQUIRE((((uintptr_t)coords | (uintptr_t)people | (uintptr_t)sin_table | (uintptr_t)index) & 3) == 0 &&
-                 ((uintptr_t)control & (control_dtype == CA_F32 ? 3 : 1)) == 0,
+                 ctrl_aligned(control, control_dtype, 1),
              "ca_pose_draw: coords, people, sin_table and index must be 4-byte aligned, control aligned to its element");
   hipStream_t st = (hipStream_t)stream;
   const int64_t hw = (int64_t)h * w, total = (int64_t)images * hw;
@@ -1100,8 +1080,7 @@ extern "C" int ca_pose_draw(const int32_t* coords, const int32_t* people, const 
   if (e != hipSuccess) CA_FAIL(CA_ERR_LAUNCH, "ca_pose_draw: %s", hipGetErrorString(e));
   hipLaunchKernelGGL(k_pose_raster, dim3(kPrims, kMaxPeople, (unsigned)images), dim3(256), 0, st, coords, people, sin_table, (unsigned*)index, (int)h, (int)w, kPrims);
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (control_dtype == CA_F32) hipLaunchKernelGGL(k_pose_resolve<float>, grid, block, 0, st, (const unsigned*)index, map, (float*)control, (int)images, hw, (int)rep, kPrims, 0);
-  else hipLaunchKernelGGL(k_pose_resolve<u16>, grid, block, 0, st, (const unsigned*)index, map, (u16*)control, (int)images, hw, (int)rep, kPrims, 0);
+  CA_DISPATCH_CTRL(control_dtype, hipLaunchKernelGGL(k_pose_resolve<T>, grid, block, 0, st, (const unsigned*)index, map, (T*)control, (int)images, hw, (int)rep, kPrims, 0));
   CA_CHECK_LAUNCH("ca_pose_draw");
   return CA_OK;
 }
@@ -1114,10 +1093,9 @@ extern "C" int ca_pose_draw_faces(const int32_t* coords, const int32_t* people, 
   CA_REQUIRE(map || control, "ca_pose_draw_faces: map or control is required");
   CA_REQUIRE(sizes_ok(images, h, w) && images <= 65535 && h <= kMaxSide && w <= kMaxSide,
              "ca_pose_draw_faces: images=%d h=%d w=%d (each >= 1, images <= 65535, h and w <= %d, images * h * w < 2^31)", images, h, w, kMaxSide);
-  CA_REQUIRE(rep == 1 || rep == 2, "ca_pose_draw_faces: rep=%d (1 or 2)", rep);
-  CA_REQUIRE(control_dtype == CA_F16 || control_dtype == CA_F32, "ca_pose_draw_faces: control_dtype=%d (CA_F16 or CA_F32)", control_dtype);
+  if (const int rc = control_out_checks("ca_pose_draw_faces", false, h, w, nullptr, true, rep, control_dtype)) return rc;
   CA_REQUIRE((((uintptr_t)coords | (uintptr_t)people | (uintptr_t)sin_table | (uintptr_t)index | (uintptr_t)points | (uintptr_t)xmap | (uintptr_t)ymap) & 3) == 0 &&
-                 ((uintptr_t)control & (control_dtype == CA_F32 ? 3 : 1)) == 0,
+                 ctrl_aligned(control, control_dtype, 1),
              "ca_pose_draw_faces: coords, people, sin_table, points, xmap, ymap and index must be 4-byte aligned, control aligned to its element");
   hipStream_t st = (hipStream_t)stream;
   const int64_t hw = (int64_t)h * w, total = (int64_t)images * hw;
@@ -1126,10 +1104,7 @@ extern "C" int ca_pose_draw_faces(const int32_t* coords, const int32_t* people, 
   hipLaunchKernelGGL(k_pose_raster, dim3(kPrims, kMaxPeople, (unsigned)images), dim3(256), 0, st, coords, people, sin_table, (unsigned*)index, (int)h, (int)w, kPrimsFace);
   if (points) hipLaunchKernelGGL(k_face_raster, dim3(kMaxPeople, (unsigned)images), dim3(256), 0, st, points, people, xmap, ymap, (unsigned*)index, (int)h, (int)w, kPrimsFace, kPrims);
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (control_dtype == CA_F32)
-    hipLaunchKernelGGL(k_pose_resolve<float>, grid, block, 0, st, (const unsigned*)index, map, (float*)control, (int)images, hw, (int)rep, kPrimsFace, 0);
-  else
-    hipLaunchKernelGGL(k_pose_resolve<u16>, grid, block, 0, st, (const unsigned*)index, map, (u16*)control, (int)images, hw, (int)rep, kPrimsFace, 0);
+  CA_DISPATCH_CTRL(control_dtype, hipLaunchKernelGGL(k_pose_resolve<T>, grid, block, 0, st, (const unsigned*)index, map, (T*)control, (int)images, hw, (int)rep, kPrimsFace, 0));
   CA_CHECK_LAUNCH("ca_pose_draw_faces");
   return CA_OK;
 }
@@ -1141,10 +1116,9 @@ extern "C" int ca_pose_draw_hands(const int32_t* coords, const int32_t* people, 
   CA_REQUIRE(map || control, "ca_pose_draw_hands: map or control is required");
   CA_REQUIRE(sizes_ok(images, h, w) && images <= 65535 && h <= kMaxSide && w <= kMaxSide,
              "ca_pose_draw_hands: images=%d h=%d w=%d (each >= 1, images <= 65535, h and w <= %d, images * h * w < 2^31)", images, h, w, kMaxSide);
-  CA_REQUIRE(rep == 1 || rep == 2, "ca_pose_draw_hands: rep=%d (1 or 2)", rep);
-  CA_REQUIRE(control_dtype == CA_F16 || control_dtype == CA_F32, "ca_pose_draw_hands: control_dtype=%d (CA_F16 or CA_F32)", control_dtype);
+  if (const int rc = control_out_checks("ca_pose_draw_hands", false, h, w, nullptr, true, rep, control_dtype)) return rc;
   CA_REQUIRE((((uintptr_t)coords | (uintptr_t)people | (uintptr_t)sin_table | (uintptr_t)index | (uintptr_t)hand_points | (uintptr_t)face_points | (uintptr_t)xmap |
-               (uintptr_t)ymap) & 3) == 0 && ((uintptr_t)control & (control_dtype == CA_F32 ? 3 : 1)) == 0,
+               (uintptr_t)ymap) & 3) == 0 && ctrl_aligned(control, control_dtype, 1),
              "ca_pose_draw_hands: coords, people, sin_table, the points, xmap, ymap and index must be 4-byte aligned, control aligned to its element");
   hipStream_t st = (hipStream_t)stream;
   const int64_t hw = (int64_t)h * w, total = (int64_t)images * hw;
@@ -1156,10 +1130,7 @@ extern "C" int ca_pose_draw_hands(const int32_t* coords, const int32_t* people, 
     hipLaunchKernelGGL(k_face_raster, dim3(kMaxPeople, (unsigned)images), dim3(256), 0, st, face_points, people, xmap, ymap, (unsigned*)index, (int)h, (int)w, kPrimsAll,
                        kPrims + 2 * kHandPrims);
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (control_dtype == CA_F32)
-    hipLaunchKernelGGL(k_pose_resolve<float>, grid, block, 0, st, (const unsigned*)index, map, (float*)control, (int)images, hw, (int)rep, kPrimsAll, 1);
-  else
-    hipLaunchKernelGGL(k_pose_resolve<u16>, grid, block, 0, st, (const unsigned*)index, map, (u16*)control, (int)images, hw, (int)rep, kPrimsAll, 1);
+  CA_DISPATCH_CTRL(control_dtype, hipLaunchKernelGGL(k_pose_resolve<T>, grid, block, 0, st, (const unsigned*)index, map, (T*)control, (int)images, hw, (int)rep, kPrimsAll, 1));
   CA_CHECK_LAUNCH("ca_pose_draw_hands");
   return CA_OK;
 }

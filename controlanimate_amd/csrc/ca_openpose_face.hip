@@ -15,6 +15,7 @@
 // No launch depends on device data on the host side: the stage can be captured in a hipGraph.  The drawing is ca_pose_draw_faces
 // (ca_openpose.hip).
 #include "ca_common.h"
+#include "ca_annot.h"
 
 #include <climits>
 
@@ -273,7 +274,6 @@ __global__ __launch_bounds__(256) void k_face_peaks(const float* __restrict__ he
   }
 }
 
-inline bool dtype_ok(int32_t dtype) { return dtype == CA_BF16 || dtype == CA_F16; }
 inline bool frame_ok(int32_t images, int32_t h, int32_t w) { return images >= 1 && images <= 65535 && h >= 1 && w >= 1 && h <= kMaxSide && w <= kMaxSide; }
 inline bool faces_ok(int32_t images, int32_t max_faces) { return max_faces >= 1 && max_faces <= kMaxPeople && (int64_t)images * max_faces <= 65535; }
 
@@ -308,12 +308,8 @@ extern "C" int ca_face_crop(const uint8_t* frames, const int32_t* slots, void* o
                  ((uintptr_t)lz_coef & 1) == 0,
              "ca_face_crop: out must be 16-byte aligned, slots and the 32-bit tables 4-byte aligned, lz_coef 2-byte aligned");
   const dim3 grid(kSize / kRowsOut, (unsigned)crops), block(256);
-  if (dtype == CA_BF16)
-    hipLaunchKernelGGL(k_face_crop<CA_BF16>, grid, block, 0, (hipStream_t)stream, frames, slots, (u16*)out, lz_ofs, (const short*)lz_coef, ar_ofs, ar_cnt, ar_w, (int)h,
-                       (int)w, (int)max_faces, (int)first, (int)side_max);
-  else
-    hipLaunchKernelGGL(k_face_crop<CA_F16>, grid, block, 0, (hipStream_t)stream, frames, slots, (u16*)out, lz_ofs, (const short*)lz_coef, ar_ofs, ar_cnt, ar_w, (int)h,
-                       (int)w, (int)max_faces, (int)first, (int)side_max);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_face_crop<DT>, grid, block, 0, (hipStream_t)stream, frames, slots, (u16*)out, lz_ofs, (const short*)lz_coef, ar_ofs, ar_cnt, ar_w, (int)h,
+                       (int)w, (int)max_faces, (int)first, (int)side_max));
   CA_CHECK_LAUNCH("ca_face_crop");
   return CA_OK;
 }

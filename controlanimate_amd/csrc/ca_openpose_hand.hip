@@ -524,12 +524,8 @@ extern "C" int ca_hand_crop(const uint8_t* frames, const int32_t* slots, const d
     hipLaunchKernelGGL(k_hand_blur, dim3((unsigned)(((int64_t)wmax * wmax + 255) / 256), (unsigned)crops), dim3(256), 0, st, frames, slots, taps, blurred, (int)h, (int)w,
                        (int)max_hands, (int)first, wmax);
   const dim3 grid((unsigned)((side * side + 255) / 256), (unsigned)crops), block(256);
-  if (dtype == CA_BF16)
-    hipLaunchKernelGGL(k_hand_resize<CA_BF16>, grid, block, 0, st, (const uint8_t*)blurred, slots, (u16*)out, lz_ofs, (const short*)lz_coef, ar_ofs, ar_cnt, ar_w, (int)h,
-                       (int)w, (int)first, (int)side, (int)side_max, wmax);
-  else
-    hipLaunchKernelGGL(k_hand_resize<CA_F16>, grid, block, 0, st, (const uint8_t*)blurred, slots, (u16*)out, lz_ofs, (const short*)lz_coef, ar_ofs, ar_cnt, ar_w, (int)h,
-                       (int)w, (int)first, (int)side, (int)side_max, wmax);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_hand_resize<DT>, grid, block, 0, st, (const uint8_t*)blurred, slots, (u16*)out, lz_ofs, (const short*)lz_coef, ar_ofs, ar_cnt, ar_w, (int)h,
+                       (int)w, (int)first, (int)side, (int)side_max, wmax));
   CA_CHECK_LAUNCH("ca_hand_crop");
   return CA_OK;
 }

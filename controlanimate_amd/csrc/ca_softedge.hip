@@ -3,7 +3,7 @@
 // PidiNetDetector).  The 3 -> 64 init_block runs on ca_conv3x3 (the pixel-difference operator folded into a plain 3x3 weight on the
 // host), every 1x1 convolution on ca_gemm; around them:
 //
-//   prep      k_se_prep        uint8 RGB [n,H,W,3] -> [n,H,W,8]: x / 255 in channels 0..2, zeros in 3..7
+//   prep      SeFill           uint8 RGB [n,H,W,3] -> [n,H,W,8]: x / 255 in channels 0..2, zeros in 3..7
 //   dw        k_dwconv_k       depthwise 3x3 / 5x5 (the folded cd / ad / cv and rd operators), stride 1, no bias, optional ReLU.  As
 //                              k_dwconv3x3 a thread owns 8 (5x5: 4) channels of one output column and walks down a strip of output rows; the KS
 //                              output rows in flight rotate through registers, so an input row of the strip is read once.  The sum of one
@@ -27,31 +27,23 @@
 //                              miss the whole map for a block are skipped
 //   csam      k_csam_a / _b    t = b1 + W1 relu(f) (4 channels) and r = wr . f per pixel, then side = br + sigmoid(conv3x3(t)) * r
 //   fuse      k_se_fuse        the four side maps sampled bilinearly (align_corners = False), the 1x1 classifier, the fp32 sigmoid, the
-//                              optional safe step, x 255, truncation -> uint8 map and / or the control tensor
+//                              optional safe step, x 255, truncation -> uint8 map and / or the control tensor (ca_annot.h)
 //
 // Compiled with -ffp-contract=off: the depthwise sums of k_dwconv_k and k_pdc_block then are the same operations, and the bilinear
 // sample and the classifier round as written.  No atomics; no launch depends on device data on the host side.
 #include "ca_common.h"
+#include "ca_annot.h"
 
 namespace {
 
-constexpr int64_t kMaxPixels = ((int64_t)1 << 31) - 1;
-
-inline bool sizes_ok(int32_t images, int32_t h, int32_t w) { return images >= 1 && h >= 1 && w >= 1 && (int64_t)images * h * w <= kMaxPixels; }
-inline bool dtype_ok(int32_t dtype) { return dtype == CA_BF16 || dtype == CA_F16; }
-
 // ---- prep ------------------------------------------------------------------------------------------------------------------------
-template <int DT>
-__global__ __launch_bounds__(256) void k_se_prep(const uint8_t* __restrict__ src, u16* __restrict__ dst, int64_t pixels) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= pixels) return;
-  const uint8_t* s = src + p * 3;
-  float f[8];
+struct SeFill {
+  __device__ __forceinline__ void operator()(const uint8_t* s, float f[8]) const {
 #pragma unroll
-  for (int c = 0; c < 3; ++c) f[c] = __fdiv_rn((float)s[c], 255.0f);
-  f[3] = f[4] = f[5] = f[6] = f[7] = 0.f;
-  st16(dst + p * 8, pack8<DT>(f));
-}
+    for (int c = 0; c < 3; ++c) f[c] = __fdiv_rn((float)s[c], 255.0f);
+    f[3] = f[4] = f[5] = f[6] = f[7] = 0.f;
+  }
+};
 
 // ---- ReLU ------------------------------------------------------------------------------------------------------------------------
 template <int DT>
@@ -416,13 +408,6 @@ struct SeSides {
   const float* s[4];
 };
 
-template <typename T>
-struct alignas(4 * sizeof(T)) Vec4 {
-  T v[4];
-};
-__device__ __forceinline__ void ctrl_from_level(int level, float& out) { out = __fdiv_rn((float)level, 255.0f); }
-__device__ __forceinline__ void ctrl_from_level(int level, u16& out) { out = Elem<CA_F16>::from_f(__fdiv_rn((float)level, 255.0f)); }
-
 // 4 consecutive pixels of one row per thread (w % 8 == 0)
 template <typename T>
 __global__ __launch_bounds__(256) void k_se_fuse(SeSides sd, const float* __restrict__ cls, float* __restrict__ logit, uint8_t* __restrict__ edges, T* __restrict__ ctrl,
@@ -472,15 +457,8 @@ __global__ __launch_bounds__(256) void k_se_fuse(SeSides sd, const float* __rest
     e = e < 0.f ? 0.f : (e > 255.f ? 255.f : e);
     level[i] = (int)e;  // truncation, as astype(uint8) of a value in [0, 255]
   }
-  if (edges) *(uint32_t*)(edges + g0) = (uint32_t)level[0] | ((uint32_t)level[1] << 8) | ((uint32_t)level[2] << 16) | ((uint32_t)level[3] << 24);
-  if (ctrl) {
-    Vec4<T> v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ctrl_from_level(level[i], v.v[i]);
-    for (int r = 0; r < rep; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) *(Vec4<T>*)(ctrl + (((int64_t)r * images + img) * 3 + c) * hw + p) = v;
-  }
+  if (edges) *(uint32_t*)(edges + g0) = pack_levels4(level);
+  if (ctrl) emit_control4(ctrl, images, img, hw, p, rep, level);
 }
 
 inline bool ranges_overlap(const void* a, int64_t abytes, const void* b, int64_t bbytes) {
@@ -491,16 +469,7 @@ inline bool ranges_overlap(const void* a, int64_t abytes, const void* b, int64_t
 }  // namespace
 
 extern "C" int ca_softedge_prep(const uint8_t* src, void* dst, int32_t images, int32_t h, int32_t w, int32_t dtype, void* stream) {
-  CA_REQUIRE(src && dst, "ca_softedge_prep: src and dst are required");
-  CA_REQUIRE(sizes_ok(images, h, w), "ca_softedge_prep: images=%d h=%d w=%d (each >= 1, images * h * w < 2^31)", images, h, w);
-  CA_REQUIRE(dtype_ok(dtype), "ca_softedge_prep: dtype %d", dtype);
-  CA_REQUIRE(((uintptr_t)dst & 15) == 0, "ca_softedge_prep: dst must be 16-byte aligned");
-  const int64_t pixels = (int64_t)images * h * w;
-  const dim3 grid((unsigned)((pixels + 255) / 256)), block(256);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_se_prep<CA_BF16>, grid, block, 0, (hipStream_t)stream, src, (u16*)dst, pixels);
-  else hipLaunchKernelGGL(k_se_prep<CA_F16>, grid, block, 0, (hipStream_t)stream, src, (u16*)dst, pixels);
-  CA_CHECK_LAUNCH("ca_softedge_prep");
-  return CA_OK;
+  return launch_rgb8_prep("ca_softedge_prep", "src and dst", src && dst, src, dst, images, h, w, dtype, true, "dst must be 16-byte aligned", stream, SeFill{});
 }
 
 extern "C" int ca_relu(const void* x, void* y, int64_t numel, int32_t dtype, void* stream) {
@@ -510,8 +479,7 @@ extern "C" int ca_relu(const void* x, void* y, int64_t numel, int32_t dtype, voi
   CA_REQUIRE((((uintptr_t)x | (uintptr_t)y) & 15) == 0, "ca_relu: x and y must be 16-byte aligned");
   const int64_t groups = numel / 8;
   const dim3 grid((unsigned)((groups + 255) / 256)), block(256);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_se_relu<CA_BF16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, (u16*)y, groups);
-  else hipLaunchKernelGGL(k_se_relu<CA_F16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, (u16*)y, groups);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_se_relu<DT>, grid, block, 0, (hipStream_t)stream, (const u16*)x, (u16*)y, groups));
   CA_CHECK_LAUNCH("ca_relu");
   return CA_OK;
 }
@@ -535,13 +503,8 @@ extern "C" int ca_dwconv_k(const void* x, const void* wt, void* y, int32_t image
   hipStream_t st = (hipStream_t)stream;
 #define CA_DK_LAUNCH(DT, KS) \
   hipLaunchKernelGGL((k_dwconv_k<DT, KS>), grid, block, 0, st, (const u16*)x, (const u16*)wt, (u16*)y, total, (int)h, (int)w, (int)c, strips, (int)relu)
-  if (dtype == CA_BF16) {
-    if (ksize == 3) CA_DK_LAUNCH(CA_BF16, 3);
-    else CA_DK_LAUNCH(CA_BF16, 5);
-  } else {
-    if (ksize == 3) CA_DK_LAUNCH(CA_F16, 3);
-    else CA_DK_LAUNCH(CA_F16, 5);
-  }
+  CA_DISPATCH_DT(dtype, if (ksize == 3) CA_DK_LAUNCH(DT, 3);
+    else CA_DK_LAUNCH(DT, 5));
 #undef CA_DK_LAUNCH
   CA_CHECK_LAUNCH("ca_dwconv_k");
   return CA_OK;
@@ -557,8 +520,7 @@ extern "C" int ca_maxpool2x2(const void* x, void* y, int32_t images, int32_t h, 
   CA_REQUIRE((int64_t)images * h * w * c <= kMaxPixels * 8, "ca_maxpool2x2: tensor too large");
   const int64_t total = (int64_t)images * (h / 2) * (w / 2) * (c / 8);
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_maxpool2x2<CA_BF16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, (u16*)y, total, h / 2, w / 2, (int)c);
-  else hipLaunchKernelGGL(k_maxpool2x2<CA_F16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, (u16*)y, total, h / 2, w / 2, (int)c);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_maxpool2x2<DT>, grid, block, 0, (hipStream_t)stream, (const u16*)x, (u16*)y, total, h / 2, w / 2, (int)c));
   CA_CHECK_LAUNCH("ca_maxpool2x2");
   return CA_OK;
 }
@@ -581,13 +543,8 @@ extern "C" int ca_pdc_block(const void* x, const void* wt_dw, const void* w2, vo
   const dim3 grid((unsigned)blocks), block(256);
   hipStream_t st = (hipStream_t)stream;
 #define CA_PB_LAUNCH(DT, KS) hipLaunchKernelGGL((k_pdc_block<DT, KS>), grid, block, 0, st, (const u16*)x, (const u16*)wt_dw, (const u16*)w2, (u16*)y, (int)h, (int)w, tx, ty)
-  if (dtype == CA_BF16) {
-    if (ksize == 3) CA_PB_LAUNCH(CA_BF16, 3);
-    else CA_PB_LAUNCH(CA_BF16, 5);
-  } else {
-    if (ksize == 3) CA_PB_LAUNCH(CA_F16, 3);
-    else CA_PB_LAUNCH(CA_F16, 5);
-  }
+  CA_DISPATCH_DT(dtype, if (ksize == 3) CA_PB_LAUNCH(DT, 3);
+    else CA_PB_LAUNCH(DT, 5));
 #undef CA_PB_LAUNCH
   CA_CHECK_LAUNCH("ca_pdc_block");
   return CA_OK;
@@ -605,8 +562,7 @@ extern "C" int ca_cdcm_dil4(const void* x, const void* wt, void* y, int32_t imag
   const int64_t blocks = (int64_t)images * tx * ty;
   CA_REQUIRE(blocks < ((int64_t)1 << 31), "ca_cdcm_dil4: grid too large");
   const dim3 grid((unsigned)blocks), block(256);
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_cdcm_dil4<CA_BF16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, (const u16*)wt, (u16*)y, (int)h, (int)w, tx, ty);
-  else hipLaunchKernelGGL(k_cdcm_dil4<CA_F16>, grid, block, 0, (hipStream_t)stream, (const u16*)x, (const u16*)wt, (u16*)y, (int)h, (int)w, tx, ty);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_cdcm_dil4<DT>, grid, block, 0, (hipStream_t)stream, (const u16*)x, (const u16*)wt, (u16*)y, (int)h, (int)w, tx, ty));
   CA_CHECK_LAUNCH("ca_cdcm_dil4");
   return CA_OK;
 }
@@ -624,8 +580,7 @@ extern "C" int ca_csam_reduce(const void* f, const float* w1, const float* b1, c
              "ca_csam_reduce: t, r and side must not overlap");
   const dim3 grid((unsigned)((pixels + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == CA_BF16) hipLaunchKernelGGL(k_csam_a<CA_BF16>, grid, block, 0, st, (const u16*)f, w1, b1, wr, t, r, pixels);
-  else hipLaunchKernelGGL(k_csam_a<CA_F16>, grid, block, 0, st, (const u16*)f, w1, b1, wr, t, r, pixels);
+  CA_DISPATCH_DT(dtype, hipLaunchKernelGGL(k_csam_a<DT>, grid, block, 0, st, (const u16*)f, w1, b1, wr, t, r, pixels));
   CA_CHECK_LAUNCH("ca_csam_reduce");
   hipLaunchKernelGGL(k_csam_b, grid, block, 0, st, (const float*)t, (const float*)r, w2, br, side, pixels, (int)h, (int)w);
   CA_CHECK_LAUNCH("ca_csam_reduce");
@@ -639,21 +594,18 @@ extern "C" int ca_softedge_fuse(const float* side0, const float* side1, const fl
   CA_REQUIRE(h % 8 == 0 && w % 8 == 0, "ca_softedge_fuse: h=%d w=%d must be multiples of 8 (four levels, the k-th of (h >> k, w >> k))", h, w);
   CA_REQUIRE(logit || edges || control, "ca_softedge_fuse: logit, edges or control is required");
   CA_REQUIRE(safe == 0 || safe == 1, "ca_softedge_fuse: safe=%d (0 or 1)", safe);
-  CA_REQUIRE(rep == 1 || rep == 2, "ca_softedge_fuse: rep=%d (1 or 2)", rep);
-  CA_REQUIRE(control_dtype == CA_F16 || control_dtype == CA_F32, "ca_softedge_fuse: control_dtype=%d (CA_F16 or CA_F32)", control_dtype);
-  const int esize = control_dtype == CA_F32 ? 4 : 2;
+  if (const int rc = control_out_checks("ca_softedge_fuse", false, h, w, nullptr, true, rep, control_dtype)) return rc;  // (logit is a third output: above)
   CA_REQUIRE((((uintptr_t)side0 | (uintptr_t)logit) & 15) == 0 && (((uintptr_t)side1 | (uintptr_t)side2 | (uintptr_t)side3 | (uintptr_t)classifier) & 3) == 0,
              "ca_softedge_fuse: side0 and logit must be 16-byte aligned, the other side maps and the classifier 4-byte aligned");
-  CA_REQUIRE(((uintptr_t)edges & 3) == 0 && ((uintptr_t)control & (4 * esize - 1)) == 0,
+  CA_REQUIRE(((uintptr_t)edges & 3) == 0 && ctrl_aligned(control, control_dtype, 4),
              "ca_softedge_fuse: edges must be 4-byte aligned, control aligned to four of its elements");
   SeSides sd;
   sd.s[0] = side0, sd.s[1] = side1, sd.s[2] = side2, sd.s[3] = side3;
   const int64_t total = (int64_t)images * h * w;
   const dim3 grid((unsigned)((total / 4 + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (control_dtype == CA_F32)
-    hipLaunchKernelGGL(k_se_fuse<float>, grid, block, 0, st, sd, classifier, logit, edges, (float*)control, (int)images, (int)h, (int)w, (int)rep, (int)safe);
-  else hipLaunchKernelGGL(k_se_fuse<u16>, grid, block, 0, st, sd, classifier, logit, edges, (u16*)control, (int)images, (int)h, (int)w, (int)rep, (int)safe);
+  CA_DISPATCH_CTRL(control_dtype,
+                   hipLaunchKernelGGL(k_se_fuse<T>, grid, block, 0, st, sd, classifier, logit, edges, (T*)control, (int)images, (int)h, (int)w, (int)rep, (int)safe));
   CA_CHECK_LAUNCH("ca_softedge_fuse");
   return CA_OK;
 }

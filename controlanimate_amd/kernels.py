@@ -804,6 +804,28 @@ def _req_u8_frames(frames: torch.Tensor):
     return frames.shape[0], frames.shape[1]
 
 
+def _req_rgb8(frames: torch.Tensor):
+    """(images, H, W) of contiguous uint8 RGB frames."""
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
+    return tuple(frames.shape[:3])
+
+
+_CONTROL_DT = {torch.float16: CA_F16, torch.float32: _capi.CA_F32}
+
+
+def _control_args(n: int, h: int, w: int, edges: Optional[torch.Tensor], control: Optional[torch.Tensor], rep: int, map_shape=None) -> int:
+    """The outputs of a finish entry (csrc/ca_annot.h): the uint8 map [n, H, W] (or map_shape) and the control tensor [rep * n, 3, H, W];
+    returns control_dtype for the C call."""
+    if edges is not None:
+        assert edges.dtype == torch.uint8 and tuple(edges.shape) == (map_shape or (n, h, w)) and edges.is_contiguous()
+    if control is None:
+        return _capi.CA_F32
+    if control.dtype not in _CONTROL_DT:
+        raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
+    assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
+    return _CONTROL_DT[control.dtype]
+
+
 def _req_f64(*ts):
     _req_cuda(*ts)
     for t in ts:
@@ -881,7 +903,6 @@ def color_finish_u8(o: torch.Tensor, out: torch.Tensor, normalize: bool, ws: tor
 # ---- ABI v16: the canny annotator (controlanimate_amd/annotators.py: CannyAnnotator) ---------------------------------------------
 
 CANNY_TILE_H, CANNY_TILE_W = 16, 64  # kTH / kTW of csrc/ca_canny.hip (ca_canny_tile_h / ca_canny_tile_w; tests/test_canny_cpu.py compares)
-_CANNY_DT = {torch.float16: CA_F16, torch.float32: _capi.CA_F32}
 CANNY_LINK_STAGES = ("label", "merge", "flatten")  # CA_CANNY_LINK_LABEL / _MERGE / _FLATTEN
 
 
@@ -923,14 +944,7 @@ def canny_emit(images: int, h: int, w: int, ws: torch.Tensor, edges: Optional[to
     """Writes the edge map (uint8 [images, H, W], 0 / 255) and / or the control tensor ([rep * images, 3, H, W], 0.0 / 1.0) from
     `ws` as canny_link left it (ca_canny_emit)."""
     _req_cuda(ws, edges, control)
-    if edges is not None:
-        assert edges.dtype == torch.uint8 and tuple(edges.shape) == (images, h, w) and edges.is_contiguous()
-    dt = _capi.CA_F32
-    if control is not None:
-        if control.dtype not in _CANNY_DT:
-            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
-        assert tuple(control.shape) == (rep * images, 3, h, w) and control.is_contiguous()
-        dt = _CANNY_DT[control.dtype]
+    dt = _control_args(images, h, w, edges, control, rep)
     check(lib().ca_canny_emit(images, h, w, _p(ws), _ws_bytes(ws), _p(edges), _p(control), int(rep), dt, _stream()), "ca_canny_emit")
 
 
@@ -940,8 +954,7 @@ def hed_prep(frames: torch.Tensor, norm: torch.Tensor, out: torch.Tensor) -> tor
     """uint8 RGB [images, H, W, 3] -> NHWC `out` [images, H, W, 8] fp16 / bf16: (float)frames - norm in channels 0..2, zeros in 3..7
     (ca_hed_prep).  norm: float32 [3] on the device."""
     _req_cuda(frames, norm, out)
-    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
-    n, h, w, _ = frames.shape
+    n, h, w = _req_rgb8(frames)
     assert norm.dtype == torch.float32 and norm.numel() == 3 and norm.is_contiguous()
     assert tuple(out.shape) == (n, h, w, 8) and out.is_contiguous()
     check(lib().ca_hed_prep(_p(frames), _p(norm), _p(out), n, h, w, dt_code(out.dtype), _stream()), "ca_hed_prep")
@@ -969,14 +982,7 @@ def hed_fuse(sides, edges: Optional[torch.Tensor] = None, control: Optional[torc
     n, h, w = sides[0].shape
     for k, s in enumerate(sides):
         assert s.dtype == torch.float32 and s.is_contiguous() and tuple(s.shape) == (n, h >> k, w >> k), f"side map {k}: {tuple(s.shape)} {s.dtype}"
-    if edges is not None:
-        assert edges.dtype == torch.uint8 and tuple(edges.shape) == (n, h, w) and edges.is_contiguous()
-    dt = _capi.CA_F32
-    if control is not None:
-        if control.dtype not in _CANNY_DT:
-            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
-        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
-        dt = _CANNY_DT[control.dtype]
+    dt = _control_args(n, h, w, edges, control, rep)
     check(lib().ca_hed_fuse(*[_p(s) for s in sides], n, h, w, _p(edges), _p(control), int(rep), dt, _stream()), "ca_hed_fuse")
 
 
@@ -986,8 +992,7 @@ def lineart_conv_in(frames: torch.Tensor, w_packed: torch.Tensor, out: torch.Ten
     """uint8 RGB [images, H, W, 3] -> `out` [images, H, W, 64] fp16 / bf16: the 7x7 convolution behind reflection padding 3 of
     frames / 255, without bias (ca_lineart_conv_in).  w_packed: [64, 160] of out's dtype (lineart.pack_conv_in)."""
     _req_cuda(frames, w_packed, out)
-    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
-    n, h, w, _ = frames.shape
+    n, h, w = _req_rgb8(frames)
     assert tuple(w_packed.shape) == (64, 160) and w_packed.is_contiguous() and w_packed.dtype == out.dtype
     assert tuple(out.shape) == (n, h, w, 64) and out.is_contiguous()
     check(lib().ca_lineart_conv_in(_p(frames), _p(w_packed), _p(out), n, h, w, dt_code(out.dtype), _stream()), "ca_lineart_conv_in")
@@ -1059,14 +1064,7 @@ def lineart_finish(logits: torch.Tensor, edges: Optional[torch.Tensor] = None, c
     _req_cuda(logits, edges, control)
     assert logits.dtype == torch.float32 and logits.dim() == 3 and logits.is_contiguous()
     n, h, w = logits.shape
-    if edges is not None:
-        assert edges.dtype == torch.uint8 and tuple(edges.shape) == (n, h, w) and edges.is_contiguous()
-    dt = _capi.CA_F32
-    if control is not None:
-        if control.dtype not in _CANNY_DT:
-            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
-        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
-        dt = _CANNY_DT[control.dtype]
+    dt = _control_args(n, h, w, edges, control, rep)
     check(lib().ca_lineart_finish(_p(logits), n, h, w, _p(edges), _p(control), int(rep), dt, _stream()), "ca_lineart_finish")
 
 
@@ -1079,8 +1077,7 @@ def lanime_conv_in(frames: torch.Tensor, w_packed: torch.Tensor, bias: torch.Ten
     LeakyReLU(0.2)(d0) and c0[..., :64] = ReLU(d0), c0 [images, H/2, W/2, 128] (ca_lanime_conv_in).  w_packed: [64, 64] of l0's dtype
     (lineart_anime.pack_conv_in); bias: float32 [64]."""
     _req_cuda(frames, w_packed, bias, l0, c0)
-    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
-    n, h, w, _ = frames.shape
+    n, h, w = _req_rgb8(frames)
     assert tuple(w_packed.shape) == (64, 64) and w_packed.is_contiguous() and w_packed.dtype == l0.dtype == c0.dtype
     assert bias.dtype == torch.float32 and bias.numel() == 64 and bias.is_contiguous()
     assert tuple(l0.shape) == (n, h // 2, w // 2, 64) and l0.is_contiguous() and tuple(c0.shape) == (n, h // 2, w // 2, 128) and c0.is_contiguous()
@@ -1180,14 +1177,7 @@ def lanime_finish(pre: torch.Tensor, edges: Optional[torch.Tensor] = None, contr
     _req_cuda(pre, edges, control)
     assert pre.dtype == torch.float32 and pre.dim() == 3 and pre.is_contiguous()
     n, h, w = pre.shape
-    if edges is not None:
-        assert edges.dtype == torch.uint8 and tuple(edges.shape) == (n, h, w) and edges.is_contiguous()
-    dt = _capi.CA_F32
-    if control is not None:
-        if control.dtype not in _CANNY_DT:
-            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
-        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
-        dt = _CANNY_DT[control.dtype]
+    dt = _control_args(n, h, w, edges, control, rep)
     check(lib().ca_lanime_finish(_p(pre), n, h, w, _p(edges), _p(control), int(rep), dt, _stream()), "ca_lanime_finish")
 
 
@@ -1199,8 +1189,7 @@ def mlsd_prep(frames: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """uint8 RGB [images, H, W, 3] -> NHWC `out` [images, H, W, 8] fp16 / bf16: frames / 127.5 - 1 in channels 0..2, 1 / 127.5 - 1 in
     channel 3 (the detector's channel of ones), zeros in 4..7 (ca_mlsd_prep)."""
     _req_cuda(frames, out)
-    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
-    n, h, w, _ = frames.shape
+    n, h, w = _req_rgb8(frames)
     assert tuple(out.shape) == (n, h, w, 8) and out.is_contiguous()
     check(lib().ca_mlsd_prep(_p(frames), _p(out), n, h, w, dt_code(out.dtype), _stream()), "ca_mlsd_prep")
     return out
@@ -1284,13 +1273,7 @@ def mlsd_draw(segments: torch.Tensor, count: torch.Tensor, h: int, w: int, edges
     assert count.dtype == torch.int32 and tuple(count.shape) == (n,) and count.is_contiguous()
     if edges is None:
         edges = torch.empty((n, h, w), dtype=torch.uint8, device=segments.device)
-    assert edges.dtype == torch.uint8 and tuple(edges.shape) == (n, h, w) and edges.is_contiguous()
-    dt = _capi.CA_F32
-    if control is not None:
-        if control.dtype not in _CANNY_DT:
-            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
-        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
-        dt = _CANNY_DT[control.dtype]
+    dt = _control_args(n, h, w, edges, control, rep)
     check(lib().ca_mlsd_draw(_p(segments), _p(count), n, h, w, _p(edges), _p(control), int(rep), dt, _stream()), "ca_mlsd_draw")
     return edges
 
@@ -1301,8 +1284,7 @@ def softedge_prep(frames: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """uint8 RGB [images, H, W, 3] -> NHWC `out` [images, H, W, 8] fp16 / bf16: frames / 255 in channels 0..2, zeros in 3..7
     (ca_softedge_prep)."""
     _req_cuda(frames, out)
-    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
-    n, h, w, _ = frames.shape
+    n, h, w = _req_rgb8(frames)
     assert tuple(out.shape) == (n, h, w, 8) and out.is_contiguous()
     check(lib().ca_softedge_prep(_p(frames), _p(out), n, h, w, dt_code(out.dtype), _stream()), "ca_softedge_prep")
     return out
@@ -1427,14 +1409,7 @@ def softedge_fuse(sides, classifier: torch.Tensor, *, safe: bool = False, logit:
     assert classifier.dtype == torch.float32 and classifier.numel() == 5 and classifier.is_contiguous()
     if logit is not None:
         assert logit.dtype == torch.float32 and tuple(logit.shape) == (n, h, w) and logit.is_contiguous()
-    if edges is not None:
-        assert edges.dtype == torch.uint8 and tuple(edges.shape) == (n, h, w) and edges.is_contiguous()
-    dt = _capi.CA_F32
-    if control is not None:
-        if control.dtype not in _CANNY_DT:
-            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
-        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
-        dt = _CANNY_DT[control.dtype]
+    dt = _control_args(n, h, w, edges, control, rep)
     check(lib().ca_softedge_fuse(*[_p(s) for s in sides], _p(classifier), n, h, w, int(safe), _p(logit), _p(edges), _p(control), int(rep), dt, _stream()),
           "ca_softedge_fuse")
 
@@ -1448,8 +1423,7 @@ def gfp_prep(faces: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, out: tor
     """uint8 [images, H, W, 3] -> `out` [images, H, W, Cout] = LeakyReLU(0.2)(conv1x1((faces / 255 - 0.5) / 0.5)), the channels read in
     reverse order with reverse_channels (ca_gfp_prep).  wt: float32 [Cout, 3]; bias: float32 [Cout]."""
     _req_cuda(faces, wt, bias, out)
-    assert faces.dtype == torch.uint8 and faces.dim() == 4 and faces.shape[3] == 3 and faces.is_contiguous(), "uint8 [images, H, W, 3]"
-    n, h, w, _ = faces.shape
+    n, h, w = _req_rgb8(faces)
     cout = out.shape[3]
     assert tuple(out.shape) == (n, h, w, cout) and out.is_contiguous()
     assert wt.dtype == torch.float32 and tuple(wt.shape) == (cout, 3) and wt.is_contiguous() and bias.dtype == torch.float32 and bias.numel() == cout and bias.is_contiguous()
@@ -1580,8 +1554,7 @@ def resize_pil_u8(frames: torch.Tensor, dh: int, dw: int, xbounds: torch.Tensor,
     """Pillow's Image.resize of uint8 RGB frames [images, H, W, 3] -> [images, dh, dw, 3] (ca_resize_pil_u8): bounds int32 [out, 2] and
     coefficients int32 [out, ksize] per axis, as depth.pil_coeffs builds them; tmp uint8 [images, H, dw, 3]."""
     _req_cuda(frames, xbounds, xcoef, ybounds, ycoef, tmp, out)
-    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
-    n, sh, sw, _ = frames.shape
+    n, sh, sw = _req_rgb8(frames)
     _req_i32(xbounds, xcoef, ybounds, ycoef)
     assert tuple(xbounds.shape) == (dw, 2) and xcoef.dim() == 2 and xcoef.shape[0] == dw and tuple(ybounds.shape) == (dh, 2) and ycoef.dim() == 2 and ycoef.shape[0] == dh
     if tmp is None:
@@ -1599,8 +1572,7 @@ def dpt_patches(frames: torch.Tensor, patch: int, dtype: torch.dtype, out: Optio
     """uint8 RGB [images, S, S, 3] -> (x / 255 - 0.5) / 0.5 as patch rows [images * (S / patch)^2, 3 * patch * patch] in the (c, ky, kx)
     order of the patch-embedding weight (ca_dpt_patches)."""
     _req_cuda(frames, out)
-    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
-    n, s, s2, _ = frames.shape
+    n, s, s2 = _req_rgb8(frames)
     assert s == s2 and patch > 0 and s % patch == 0
     rows = n * (s // patch) ** 2
     if out is None:
@@ -1693,14 +1665,7 @@ def depth_finish(depth: torch.Tensor, keys: torch.Tensor, normalize: str = "max"
     assert keys.dtype == torch.int32 and keys.is_contiguous() and keys.numel() >= 2 * n
     if normalize not in DEPTH_NORMALIZE:
         raise ValueError(f"normalize={normalize!r} ('max' or 'minmax')")
-    if map is not None:
-        assert map.dtype == torch.uint8 and tuple(map.shape) == (n, h, w) and map.is_contiguous()
-    dt = _capi.CA_F32
-    if control is not None:
-        if control.dtype not in _CANNY_DT:
-            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
-        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
-        dt = _CANNY_DT[control.dtype]
+    dt = _control_args(n, h, w, map, control, rep)
     check(lib().ca_depth_finish(_p(depth), _p(keys), n, h, w, DEPTH_NORMALIZE[normalize], _p(map), _p(control), int(rep), dt, _stream()), "ca_depth_finish")
 
 
@@ -1715,8 +1680,7 @@ def pose_prep(frames: torch.Tensor, tables, hs: int, ws: int, out: torch.Tensor)
     """uint8 RGB [images, H, W, 3] -> `out` [images, hp, wp, 8] fp16 / bf16: the INTER_AREA resize to hs x ws through the per-axis tables
     (xofs, xcnt, xw, yofs, ycnt, yw: openpose.area_tables), BGR, x / 256 - 0.5, zeros in the padding and in channels 3 .. 7 (ca_pose_prep)."""
     _req_cuda(frames, out, *tables)
-    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
-    n, h, w, _ = frames.shape
+    n, h, w = _req_rgb8(frames)
     hp, wp = out.shape[1], out.shape[2]
     assert tuple(out.shape) == (n, hp, wp, 8) and out.is_contiguous()
     xofs, xcnt, xw, yofs, ycnt, yw = tables
@@ -1870,14 +1834,7 @@ def pose_draw(coords: torch.Tensor, people: torch.Tensor, sin_table: torch.Tenso
     assert index.dtype == torch.int32 and tuple(index.shape) == (n, h, w) and index.is_contiguous()
     if skeleton is None and control is None:
         skeleton = torch.empty((n, h, w, 3), dtype=torch.uint8, device=coords.device)
-    if skeleton is not None:
-        assert skeleton.dtype == torch.uint8 and tuple(skeleton.shape) == (n, h, w, 3) and skeleton.is_contiguous()
-    dt = _capi.CA_F32
-    if control is not None:
-        if control.dtype not in _CANNY_DT:
-            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
-        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
-        dt = _CANNY_DT[control.dtype]
+    dt = _control_args(n, h, w, skeleton, control, rep, map_shape=(n, h, w, 3))
     check(lib().ca_pose_draw(_p(coords), _p(people), _p(sin_table), _p(index), _p(skeleton), _p(control), n, h, w, int(rep), dt, _stream()), "ca_pose_draw")
     return skeleton
 
@@ -1917,8 +1874,7 @@ def face_crop(frames: torch.Tensor, slots: torch.Tensor, tables: dict, out: torc
     first + crops - 1 resized as cv2.resize does (INTER_LANCZOS4 / INTER_AREA by the slot's mode), BGR, x / 256 - 0.5 (ca_face_crop).
     tables: openpose_face.resize_tables(side_max) on the device (lz_ofs, lz_coef, ar_ofs, ar_cnt, ar_w, side_max)."""
     _req_cuda(frames, slots, out, tables["lz_ofs"], tables["lz_coef"], tables["ar_ofs"], tables["ar_cnt"], tables["ar_w"])
-    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
-    n, h, w, _ = frames.shape
+    n, h, w = _req_rgb8(frames)
     max_faces = slots.shape[1]
     assert slots.dtype == torch.int32 and tuple(slots.shape) == (n, max_faces, FACE_SLOT_INTS) and slots.is_contiguous()
     crops = out.shape[0]
@@ -1966,14 +1922,7 @@ def pose_draw_faces(coords: torch.Tensor, people: torch.Tensor, sin_table: torch
     assert index.dtype == torch.int32 and tuple(index.shape) == (n, h, w) and index.is_contiguous()
     if skeleton is None and control is None:
         skeleton = torch.empty((n, h, w, 3), dtype=torch.uint8, device=coords.device)
-    if skeleton is not None:
-        assert skeleton.dtype == torch.uint8 and tuple(skeleton.shape) == (n, h, w, 3) and skeleton.is_contiguous()
-    dt = _capi.CA_F32
-    if control is not None:
-        if control.dtype not in _CANNY_DT:
-            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
-        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
-        dt = _CANNY_DT[control.dtype]
+    dt = _control_args(n, h, w, skeleton, control, rep, map_shape=(n, h, w, 3))
     check(lib().ca_pose_draw_faces(_p(coords), _p(people), _p(sin_table), _p(points), _p(xmap), _p(ymap), _p(index), _p(skeleton), _p(control), n, h, w, int(rep), dt,
                                    _stream()), "ca_pose_draw_faces")
     return skeleton
@@ -2021,8 +1970,7 @@ def hand_crop(frames: torch.Tensor, slots: torch.Tensor, tables: dict, blurred: 
     max_hands, min(H, W), min(H, W), 3] is written when `blur`, else read.  tables: openpose_hand.resize_tables(side, min(H, W)) on the
     device (taps, lz_ofs, lz_coef, ar_ofs, ar_cnt, ar_w; the AREA ones None when no box can be wider than side)."""
     _req_cuda(frames, slots, blurred, out, *[t for t in tables.values() if isinstance(t, torch.Tensor)])
-    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
-    n, h, w, _ = frames.shape
+    n, h, w = _req_rgb8(frames)
     max_hands, side_max = slots.shape[1], min(h, w)
     assert slots.dtype == torch.int32 and tuple(slots.shape) == (n, max_hands, HAND_SLOT_INTS) and slots.is_contiguous()
     crops, side = out.shape[0], out.shape[1]
@@ -2092,14 +2040,7 @@ def pose_draw_hands(coords: torch.Tensor, people: torch.Tensor, sin_table: torch
     assert index.dtype == torch.int32 and tuple(index.shape) == (n, h, w) and index.is_contiguous()
     if skeleton is None and control is None:
         skeleton = torch.empty((n, h, w, 3), dtype=torch.uint8, device=coords.device)
-    if skeleton is not None:
-        assert skeleton.dtype == torch.uint8 and tuple(skeleton.shape) == (n, h, w, 3) and skeleton.is_contiguous()
-    dt = _capi.CA_F32
-    if control is not None:
-        if control.dtype not in _CANNY_DT:
-            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
-        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
-        dt = _CANNY_DT[control.dtype]
+    dt = _control_args(n, h, w, skeleton, control, rep, map_shape=(n, h, w, 3))
     check(lib().ca_pose_draw_hands(_p(coords), _p(people), _p(sin_table), _p(hand_points), _p(face_points), _p(xmap), _p(ymap), _p(index), _p(skeleton), _p(control),
                                    n, h, w, int(rep), dt, _stream()), "ca_pose_draw_hands")
     return skeleton
@@ -2118,8 +2059,7 @@ def nbae_stem(frames: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, out: t
     """uint8 RGB [images, H, W, 3] -> `out` [images, H/2, W/2, cout]: swish(Conv3x3 stride 2, SAME padding, of the ImageNet-normalised frame +
     bias) (ca_nbae_stem).  wt: float32 [27, cout] (row (ky * 3 + kx) * 3 + channel, BatchNorm folded); bias: float32 [cout]."""
     _req_cuda(frames, wt, bias, out)
-    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), "uint8 [images, H, W, 3]"
-    n, h, w, _ = frames.shape
+    n, h, w = _req_rgb8(frames)
     cout = out.shape[3]
     assert wt.dtype == torch.float32 and tuple(wt.shape) == (27, cout) and wt.is_contiguous() and bias.dtype == torch.float32 and bias.numel() == cout
     assert h % 2 == 0 and w % 2 == 0 and tuple(out.shape) == (n, h // 2, w // 2, cout) and out.is_contiguous()
@@ -2243,12 +2183,5 @@ def nbae_finish(pred: torch.Tensor, map: Optional[torch.Tensor] = None, control:
     _req_cuda(pred, map, control)
     assert pred.dtype == torch.float32 and pred.dim() == 4 and pred.shape[3] == 4 and pred.is_contiguous()
     n, h, w, _ = pred.shape
-    if map is not None:
-        assert map.dtype == torch.uint8 and tuple(map.shape) == (n, h, w, 3) and map.is_contiguous()
-    dt = _capi.CA_F32
-    if control is not None:
-        if control.dtype not in _CANNY_DT:
-            raise TypeError(f"the control tensor must be float32 or float16, got {control.dtype}")
-        assert tuple(control.shape) == (rep * n, 3, h, w) and control.is_contiguous()
-        dt = _CANNY_DT[control.dtype]
+    dt = _control_args(n, h, w, map, control, rep, map_shape=(n, h, w, 3))
     check(lib().ca_nbae_finish(_p(pred), n, h, w, _p(map), _p(control), int(rep), dt, _stream()), "ca_nbae_finish")
