@@ -27,6 +27,8 @@ CA_FACE_MODE_NONE, CA_FACE_MODE_LANCZOS4, CA_FACE_MODE_AREA = 0, 1, 2
 CA_POSE_OVERFLOW_HANDS, CA_POSE_OVERFLOW_HAND_RESIZE = 16, 32  # the hand stage (openpose_hand.py)
 CA_HAND_PARTS, CA_HAND_HEAT_COLS, CA_HAND_MAP, CA_HAND_SCALES, CA_HAND_SLOT_INTS = 21, 24, 128, 4, 8
 CA_HAND_MODE_NONE, CA_HAND_MODE_RESIZE, CA_HAND_MIN_BOX, CA_HAND_AREA_TAPS = 0, 1, 20, 16
+CA_RFACE_MAX_CAND, CA_RFACE_HEAD_COLS, CA_RFACE_DET_COLS, CA_RFACE_MAX_FACES = 1024, 32, 15, 64  # face detection and alignment (face_align.py)
+CA_RFACE_OVERFLOW_CAND, CA_RFACE_OVERFLOW_FACES, CA_RFACE_CENTER, CA_RFACE_LARGEST, CA_FACE_ALIGN_SIZE = 1, 2, 1, 2, 512
 ABI_VERSION = 16
 
 
@@ -360,6 +362,15 @@ SYMBOLS = {
     "ca_nbae_normalize": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "ca_nbae_refine": (C.c_int, [C.c_void_p] * 11 + [C.c_int32] * 4 + [C.c_float, C.c_int32, C.c_void_p]),
     "ca_nbae_finish": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    # added to ABI v16 likewise: face detection and alignment beside ca_gemm / ca_conv3x3 / ca_copy_cols (controlanimate_amd/face_align.py)
+    "ca_rface_stem": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 6 + [C.c_void_p]),
+    "ca_maxpool3x3s2": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.c_void_p]),
+    "ca_subsample2": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.c_void_p]),
+    "ca_add_up2": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p]),
+    "ca_rface_decode_workspace_bytes": (C.c_int64, [C.c_int32] * 3),
+    "ca_rface_decode": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_float] * 3 + [C.c_int32] * 2 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [C.c_void_p]),
+    "ca_face_align": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 2 + [C.c_double] + [C.c_void_p] * 2 + [C.c_void_p]),
+    "ca_face_warp": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p]),
 }
 
 _lib = None

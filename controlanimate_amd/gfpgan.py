@@ -485,3 +485,7 @@ class FaceRestorer:
                                 upscale=upscale)[2]
 
         return face_enhancer
+
+
+# what stands in front of `restore_aligned` for frames that are not aligned yet: detection, fit and warp (face_align.py)
+from .face_align import FaceAligner, FaceHelper  # noqa: E402,F401

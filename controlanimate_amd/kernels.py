@@ -2185,3 +2185,103 @@ def nbae_finish(pred: torch.Tensor, map: Optional[torch.Tensor] = None, control:
     n, h, w, _ = pred.shape
     dt = _control_args(n, h, w, map, control, rep, map_shape=(n, h, w, 3))
     check(lib().ca_nbae_finish(_p(pred), n, h, w, _p(map), _p(control), int(rep), dt, _stream()), "ca_nbae_finish")
+
+
+# ---- face detection and alignment (controlanimate_amd/face_align.py; csrc/ca_retinaface.hip) -------------------------------------------------
+RFACE_MAX_CAND, RFACE_HEAD_COLS, RFACE_DET_COLS, FACE_ALIGN_SIZE = _capi.CA_RFACE_MAX_CAND, _capi.CA_RFACE_HEAD_COLS, _capi.CA_RFACE_DET_COLS, _capi.CA_FACE_ALIGN_SIZE
+
+
+def rface_stem(frames: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, bgr: bool = False) -> torch.Tensor:
+    """uint8 [images, H, W, 3] -> `out` [images, H/2, W/2, cout]: relu(conv 7x7 stride 2 padding 3 of (byte - (104, 117, 123)) + bias), the zero
+    padding in the mean-subtracted image (ca_rface_stem).  w_packed: face_align.pack_stem's, out's dtype [ceil(cout / 16) * 16, 160]."""
+    _req_cuda(frames, w_packed, bias, out)
+    n, h, w = _req_rgb8(frames)
+    cout = out.shape[3]
+    assert w_packed.dtype == out.dtype and tuple(w_packed.shape) == (-(-cout // 16) * 16, 160) and w_packed.is_contiguous()
+    assert bias.dtype == torch.float32 and bias.numel() == cout
+    assert h % 2 == 0 and w % 2 == 0 and tuple(out.shape) == (n, h // 2, w // 2, cout) and out.is_contiguous()
+    check(lib().ca_rface_stem(_p(frames), _p(w_packed), _p(bias), _p(out), n, h, w, cout, int(bool(bgr)), dt_code(out.dtype), _stream()), "ca_rface_stem")
+    return out
+
+
+def _nhwc_out(x: torch.Tensor, out: Optional[torch.Tensor], ho: int, wo: int) -> torch.Tensor:
+    assert x.dim() == 4 and x.is_contiguous()
+    shape = (x.shape[0], ho, wo, x.shape[3])
+    if out is None:
+        return torch.empty(shape, dtype=x.dtype, device=x.device)
+    assert tuple(out.shape) == shape and out.dtype == x.dtype and out.is_contiguous()
+    return out
+
+
+def maxpool3x3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """F.max_pool2d(x, 3, 2, 1) of NHWC x (ca_maxpool3x3s2): the padding never wins."""
+    _req_cuda(x, out)
+    n, h, w, c = x.shape
+    out = _nhwc_out(x, out, (h - 1) // 2 + 1, (w - 1) // 2 + 1)
+    check(lib().ca_maxpool3x3s2(_p(x), _p(out), n, h, w, c, dt_code(x.dtype), _stream()), "ca_maxpool3x3s2")
+    return out
+
+
+def subsample2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x[:, ::2, ::2, :] of NHWC x (ca_subsample2)."""
+    _req_cuda(x, out)
+    n, h, w, c = x.shape
+    out = _nhwc_out(x, out, (h + 1) // 2, (w + 1) // 2)
+    check(lib().ca_subsample2(_p(x), _p(out), n, h, w, c, dt_code(x.dtype), _stream()), "ca_subsample2")
+    return out
+
+
+def add_up2(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a [n, h, w, c] + nearest x2 of b [n, h/2, w/2, c], rounded once (ca_add_up2); out may be a."""
+    _req_cuda(a, b, out)
+    n, h, w, c = a.shape
+    assert b.is_contiguous() and b.dtype == a.dtype and tuple(b.shape) == (n, h // 2, w // 2, c) and h % 2 == 0 and w % 2 == 0
+    out = _nhwc_out(a, out, h, w)
+    check(lib().ca_add_up2(_p(a), _p(b), _p(out), n, h, w, c, dt_code(a.dtype), _stream()), "ca_add_up2")
+    return out
+
+
+def rface_decode_workspace_bytes(images: int, h: int, w: int) -> int:
+    n = int(lib().ca_rface_decode_workspace_bytes(images, h, w))
+    if n <= 0:
+        raise _capi.CAHipError(f"ca_rface_decode_workspace_bytes: images={images} h={h} w={w} is out of range")
+    return n
+
+
+def rface_decode(heads, h: int, w: int, conf: float, nms: float, eye_dist: float, flags: int, ws: torch.Tensor, dets: torch.Tensor, count: torch.Tensor,
+                 overflow: torch.Tensor) -> None:
+    """The three levels' fp32 head tensors [images, ceil(h / step), ceil(w / step), 32] -> dets fp32 [images, max_faces, 15], count and overflow
+    int32 [images] in one launch (ca_rface_decode)."""
+    _req_cuda(*heads, ws, dets, count, overflow)
+    n, max_faces = dets.shape[0], dets.shape[1]
+    assert len(heads) == 3
+    for t, step in zip(heads, (8, 16, 32)):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n, -(-h // step), -(-w // step), RFACE_HEAD_COLS), (tuple(t.shape), step)
+    assert dets.dtype == torch.float32 and dets.is_contiguous() and dets.shape[2] == RFACE_DET_COLS
+    _req_i32(count, overflow)
+    assert count.numel() == n and overflow.numel() == n and count.is_contiguous() and overflow.is_contiguous()
+    check(lib().ca_rface_decode(_p(heads[0]), _p(heads[1]), _p(heads[2]), n, h, w, float(conf), float(nms), float(eye_dist), int(flags), max_faces, _p(ws),
+                                _ws_bytes(ws), _p(dets), _p(count), _p(overflow), _stream()), "ca_rface_decode")
+
+
+def face_align(dets: torch.Tensor, count: torch.Tensor, upscale: float, affine: torch.Tensor, inverse: torch.Tensor) -> None:
+    """dets, count -> the float64 similarity [images, max_faces, 2, 3] onto the 512 x 512 template and its inverse times upscale (ca_face_align)."""
+    _req_cuda(dets, count, affine, inverse)
+    _req_f64(affine, inverse)
+    n, max_faces = dets.shape[0], dets.shape[1]
+    assert dets.dtype == torch.float32 and dets.is_contiguous() and dets.shape[2] == RFACE_DET_COLS and count.dtype == torch.int32 and count.numel() == n
+    assert tuple(affine.shape) == (n, max_faces, 2, 3) == tuple(inverse.shape) and affine.is_contiguous() and inverse.is_contiguous()
+    check(lib().ca_face_align(_p(dets), _p(count), n, max_faces, float(upscale), _p(affine), _p(inverse), _stream()), "ca_face_align")
+
+
+def face_warp(frames: torch.Tensor, affine: torch.Tensor, count: torch.Tensor, faces: torch.Tensor, bgr: bool = False) -> torch.Tensor:
+    """cv2.warpAffine(frame, affine, (512, 512)) of every slot in OpenCV's fixed point -> faces uint8 [images * max_faces, 512, 512, 3]; a slot
+    behind the count is filled with the border value (ca_face_warp)."""
+    _req_cuda(frames, affine, count, faces)
+    _req_f64(affine)
+    n, h, w = _req_rgb8(frames)
+    max_faces = affine.shape[1]
+    assert tuple(affine.shape) == (n, max_faces, 2, 3) and affine.is_contiguous() and count.dtype == torch.int32 and count.numel() == n
+    assert faces.dtype == torch.uint8 and faces.is_contiguous() and tuple(faces.shape) == (n * max_faces, FACE_ALIGN_SIZE, FACE_ALIGN_SIZE, 3)
+    check(lib().ca_face_warp(_p(frames), _p(affine), _p(count), _p(faces), n, h, w, max_faces, int(bool(bgr)), _stream()), "ca_face_warp")
+    return faces

@@ -1374,6 +1374,64 @@ int ca_nbae_refine(const void* feat, const float* pred, const void* w0, const vo
  * (CA_F32 or CA_F16; rep = 2 writes the frames twice).  h * w a multiple of 4. */
 int ca_nbae_finish(const float* pred, int32_t images, int32_t h, int32_t w, uint8_t* map, void* control, int32_t rep, int32_t control_dtype, void* stream);
 
+/* ---- added to ABI v16 likewise: face detection and alignment in front of the GFPGAN face restorer -- RetinaFace-ResNet50, its decode and
+ * NMS, get_face_landmarks_5's filters, the 5-point similarity and the warp to 512 x 512 (controlanimate_amd/face_align.py;
+ * csrc/ca_retinaface.hip; the specification is tests/retinaface_ref.py).  The bottlenecks' 1x1 convolutions, the FPN's and the heads' run
+ * on ca_gemm (the block's identity as its residual: the epilogue adds it before the activation), every 3x3 convolution on ca_conv3x3
+ * (CA_ACT_RELU), the SSH concatenation through ca_copy_cols.  No entry reads device data on the host, none uses floating-point atomics:
+ * two runs give the same bits and the chain can be captured in a hipGraph. ---- */
+#define CA_RFACE_MAX_CAND 1024        /* candidates above the threshold that enter the NMS, per frame */
+#define CA_RFACE_HEAD_COLS 32         /* a level's head row: 4 class | 8 box | 20 landmark columns (two priors per cell) */
+#define CA_RFACE_DET_COLS 15          /* x1, y1, x2, y2, score, five landmarks (x, y) */
+#define CA_RFACE_MAX_FACES 64
+#define CA_RFACE_OVERFLOW_CAND 1      /* more than CA_RFACE_MAX_CAND candidates: the best by (score, lower prior index) were taken */
+#define CA_RFACE_OVERFLOW_FACES 2     /* more faces than max_faces: the first max_faces in NMS order were taken */
+#define CA_RFACE_CENTER 1             /* flags: only_center_face */
+#define CA_RFACE_LARGEST 2            /* flags: only_keep_largest (wins over CA_RFACE_CENTER) */
+#define CA_FACE_ALIGN_SIZE 512
+
+/* uint8 frames src [images, h, w, 3] -> y [images, h / 2, w / 2, cout] of dtype = relu(conv 7x7 stride 2 padding 3 of (byte - mean) + bias):
+ * mean (104, 117, 123) by the network's channel, which is the array's channel c (bgr = 0) or 2 - c (bgr = 1); the zero padding lies in the
+ * mean-subtracted image.  w_packed of dtype [ceil(cout / 16) * 16][160]: column ky * 21 + kx * 3 + network channel, columns 147 .. 159 and
+ * the rows from cout on zero (BatchNorm folded); bias fp32 [cout].  h and w even, cout a multiple of 8 in 8 .. 64; on the MFMA, fp32 sums. */
+int ca_rface_stem(const uint8_t* src, const void* w_packed, const float* bias, void* y, int32_t images, int32_t h, int32_t w, int32_t cout, int32_t bgr, int32_t dtype,
+                  void* stream);
+
+/* The 3x3 / stride-2 / padding-1 maximum of x [images, h, w, c] -> y [images, (h - 1) / 2 + 1, (w - 1) / 2 + 1, c]; only the taps inside the
+ * image take part.  c a multiple of 8. */
+int ca_maxpool3x3s2(const void* x, void* y, int32_t images, int32_t h, int32_t w, int32_t c, int32_t dtype, void* stream);
+
+/* y [images, (h + 1) / 2, (w + 1) / 2, c] = x[:, ::2, ::2, :]: the gather in front of a stride-2 1x1 convolution on ca_gemm. */
+int ca_subsample2(const void* x, void* y, int32_t images, int32_t h, int32_t w, int32_t c, int32_t dtype, void* stream);
+
+/* y [images, h, w, c] = a [images, h, w, c] + b [images, h / 2, w / 2, c] at (y / 2, x / 2) (F.interpolate(mode='nearest') to twice the size),
+ * the sum in fp32, rounded once; h and w even; y may be a. */
+int ca_add_up2(const void* a, const void* b, void* y, int32_t images, int32_t h, int32_t w, int32_t c, int32_t dtype, void* stream);
+
+int64_t ca_rface_decode_workspace_bytes(int32_t images, int32_t h, int32_t w);
+
+/* One launch per window, one block per frame.  heads0 .. 2: fp32 [images, ceil(h / 8 | 16 | 32), ceil(w / ..), 32] (CA_RFACE_HEAD_COLS: per
+ * prior a of a cell, class logits at 2a, box at 4 + 4a, landmarks at 12 + 10a).  Prior k of a frame: levels in order, cells row-major, two
+ * priors per cell, (cx, cy, s / w, s / h) computed from the indices in float64.  score = 1 / (1 + exp(c0 - c1)) in float64, rounded to fp32,
+ * kept when > conf; the CA_RFACE_MAX_CAND best by (score descending, prior index ascending); boxes and landmarks decoded in float64
+ * (variances 0.1, 0.2) and rounded once to fp32; the greedy NMS in float64 with areas (x2 - x1 + 1)(y2 - y1 + 1), a box stays while its
+ * overlap with every kept box is <= nms; faces whose landmarks 0 and 1 are closer than eye_dist are dropped; flags choose one face.
+ * -> dets fp32 [images, max_faces, 15] (zero rows behind the count), count int32 [images], overflow int32 [images] (CA_RFACE_OVERFLOW_*).
+ * workspace: at least ca_rface_decode_workspace_bytes(images, h, w) bytes, 8-byte aligned. */
+int ca_rface_decode(const float* heads0, const float* heads1, const float* heads2, int32_t images, int32_t h, int32_t w, float conf, float nms, float eye_dist,
+                    int32_t flags, int32_t max_faces, void* workspace, int64_t workspace_bytes, float* dets, int32_t* count, int32_t* overflow, void* stream);
+
+/* dets, count -> affine float64 [images, max_faces, 2, 3]: the least-squares similarity (scale, rotation, translation) of the five landmarks
+ * onto the 512 x 512 template, closed form in float64; inverse float64 likewise: invertAffineTransform(affine) * upscale.  Slots behind the
+ * count are zero.  One thread per slot. */
+int ca_face_align(const float* dets, const int32_t* count, int32_t images, int32_t max_faces, double upscale, double* affine, double* inverse, void* stream);
+
+/* cv2.warpAffine(frame, affine, (512, 512)) of every slot -> faces uint8 [images * max_faces, 512, 512, 3]: INTER_LINEAR in OpenCV's fixed
+ * point (coordinates at 10 fractional bits rounded to 5, 15-bit weights, (sum + 2^14) >> 15), BORDER_CONSTANT (135, 133, 132) by channel
+ * position (bgr = 1: (132, 133, 135)); a slot behind the count is filled with the border value.  h and w below 32768. */
+int ca_face_warp(const uint8_t* frames, const double* affine, const int32_t* count, uint8_t* faces, int32_t images, int32_t h, int32_t w, int32_t max_faces,
+                 int32_t bgr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
