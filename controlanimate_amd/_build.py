@@ -18,7 +18,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libcontrolanimate_hip.so")
-SOURCES = ["ca_gemm.hip", "ca_gemm_pp.hip", "ca_gemm_ar.hip", "ca_norm.hip", "ca_attention.hip", "ca_elementwise.hip", "ca_upscale.hip", "ca_color.hip", "ca_canny.hip", "ca_perceiver.hip", "ca_hed.hip", "ca_lineart.hip", "ca_mlsd.hip", "ca_softedge.hip", "ca_lineart_anime.hip", "ca_gfpgan.hip", "ca_depth.hip", "ca_openpose.hip", "ca_openpose_face.hip", "ca_openpose_hand.hip", "ca_normalbae.hip", "ca_retinaface.hip"]
+SOURCES = ["ca_gemm.hip", "ca_gemm_pp.hip", "ca_gemm_ar.hip", "ca_norm.hip", "ca_attention.hip", "ca_elementwise.hip", "ca_upscale.hip", "ca_color.hip", "ca_canny.hip", "ca_perceiver.hip", "ca_hed.hip", "ca_lineart.hip", "ca_mlsd.hip", "ca_softedge.hip", "ca_lineart_anime.hip", "ca_gfpgan.hip", "ca_depth.hip", "ca_openpose.hip", "ca_openpose_face.hip", "ca_openpose_hand.hip", "ca_normalbae.hip", "ca_retinaface.hip", "ca_facepaste.hip"]
 HEADERS = ["ca_common.h", "ca_annot.h", "ca_gemm_core.h", "ca_gemm_plan.h", "ca_gemm_pp2.h", "ca_gemm_wres.h", "ca_gemm_ps.h", "ca_gemm_pq.h", "ca_gemm_ar.h", "ca_ff_fused.h", "ca_attn_out.h", "ca_tattn_fused.h", "ca_xattn_fused.h", "ca_gemm_seq.h", "ca_conv_wino.h", os.path.join("..", "..", "include", "controlanimate_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          # keep MFMA accumulators in the (unified) VGPR file: without it hipcc parks them in AGPRs and the
@@ -39,6 +39,7 @@ EXTRA["ca_openpose_face.hip"] = ["-ffp-contract=off"]  # the crop's INTER_AREA s
 EXTRA["ca_openpose_hand.hip"] = ["-ffp-contract=off"]  # util.handDetect's double arithmetic and the decode's double sums round operation by operation (tests/hand_ref.py)
 EXTRA["ca_normalbae.hip"] = ["-ffp-contract=off"]      # norm_normalize and the uint8 finish round operation by operation, as torch's / numpy's (tests/normalbae_ref.py)
 EXTRA["ca_retinaface.hip"] = ["-ffp-contract=off"]     # the decode's, the fit's and the warp's float64 arithmetic rounds operation by operation, as numpy's (tests/retinaface_ref.py)
+EXTRA["ca_facepaste.hip"] = ["-ffp-contract=off"]      # the paste's inverse affine and blend round operation by operation, as numpy's; the blur uses __dmul_rn / __dadd_rn (tests/facepaste_ref.py)
 
 
 def _extra_env_flags() -> list:

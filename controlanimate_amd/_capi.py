@@ -29,6 +29,8 @@ CA_HAND_PARTS, CA_HAND_HEAT_COLS, CA_HAND_MAP, CA_HAND_SCALES, CA_HAND_SLOT_INTS
 CA_HAND_MODE_NONE, CA_HAND_MODE_RESIZE, CA_HAND_MIN_BOX, CA_HAND_AREA_TAPS = 0, 1, 20, 16
 CA_RFACE_MAX_CAND, CA_RFACE_HEAD_COLS, CA_RFACE_DET_COLS, CA_RFACE_MAX_FACES = 1024, 32, 15, 64  # face detection and alignment (face_align.py)
 CA_RFACE_OVERFLOW_CAND, CA_RFACE_OVERFLOW_FACES, CA_RFACE_CENTER, CA_RFACE_LARGEST, CA_FACE_ALIGN_SIZE = 1, 2, 1, 2, 512
+CA_PARSE_CLASSES, CA_PARSE_CPAD, CA_BLUR_TAPS = 19, 32, 51  # the paste-back behind the face restorer (face_paste.py)
+CA_RING_IN, CA_RING_OUT, CA_RING_RES, CA_RING_REFLECT, CA_RING_REPLICATE = 1, 2, 4, 0, 1
 ABI_VERSION = 16
 
 
@@ -371,6 +373,14 @@ SYMBOLS = {
     "ca_rface_decode": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_float] * 3 + [C.c_int32] * 2 + [C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [C.c_void_p]),
     "ca_face_align": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 2 + [C.c_double] + [C.c_void_p] * 2 + [C.c_void_p]),
     "ca_face_warp": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p]),
+    # added to ABI v16 likewise: the paste-back behind the face restorer -- ParseNet, the mask blur, the inverse warp and the blend (controlanimate_amd/face_paste.py)
+    "ca_parse_prep": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.c_void_p]),
+    "ca_conv3x3_reflect": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 11 + [C.c_void_p]),
+    "ca_parse_mask": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 7 + [C.c_void_p]),
+    "ca_parse_labels": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "ca_ring_fill": (C.c_int, [C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p]),
+    "ca_mask_blur": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p]),
+    "ca_face_paste": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_double, C.c_void_p]),
 }
 
 _lib = None

@@ -50,6 +50,7 @@ class Dispatch:
     dpt_head_fused = False  # ca_dpt_head (one launch, the upsampled plane never written) for the tail of the depth annotator's head; off: the composed form (ca_upsample2x_bilinear_ac + ca_conv3x3 + ca_dpt_logit) is 2.5x faster at 192^2 -> 384^2 x 128 channels (tools/bench_depth.py, profiles/depth_bench.json)
     pose_conv7_direct = True  # ca_conv7x7 (the implicit GEMM from an LDS halo tile) for the 7x7 convolutions of the OpenPose annotator's refinement stages; off: ca_im2col7x7 + ca_gemm (tools/bench_openpose.py)
     nbae_refine_fused = True  # ca_nbae_refine (one launch per refinement stage of the NormalBae annotator, hidden activations in LDS) where C is 128, 256 or 512; off: the composed form (ca_upsample2x_bilinear_ac + ca_nbae_cat_pred + 4 ca_gemm + ca_nbae_normalize) (tools/bench_normalbae.py, profiles/normalbae_bench.json)
+    parse_conv_reflect = False  # ParseNet's stride-1 convolutions (face_paste.py).  False: the ring route at every level -- the activations are ringed tensors [n, P + 2, P + 2, C], ca_ring_fill + the zero-padded ca_conv3x3 over them; True: ca_conv3x3_reflect (the reflection as an index map at the LDS tile load) everywhere; a collection of plane sizes (e.g. {64, 128}): the ring route at those levels only.  The stride-2 and x2 layers, the first (3-channel) layer and the mask launch take ca_conv3x3_reflect on every setting.  The ring route measured faster at every level from 64 x 64 up and the same at 32 x 32 (tools/bench_facepaste.py, profiles/facepaste_bench.json)
     controlnet_streams = 2  # HIP streams the bodies of a stack of >= 3 ControlNets are spread over (independent up to the summed residuals)
 
 

@@ -1,7 +1,8 @@
 """Face detection and alignment in front of gfpgan.FaceRestorer: the front half of facexlib's FaceRestoreHelper as GFPGANer.enhance(img,
 has_aligned=False) drives it (modules/upscaler.py:53-70 of the reference) -- detect, filter, fit, warp -- for a whole window, ending in the
 `[faces, 512, 512, 3]` uint8 tensor that `FaceRestorer.restore_aligned` takes and the affine matrices a paste-back needs.  The paste-back
-itself (ParseNet, the mask blur, the inverse warp, the blend) is NOT built: `FaceHelper.paste_faces_to_input_image` raises.
+itself (ParseNet, the mask blur, the inverse warp, the blend) is built, opt-in and UNPINNED, in face_paste.py: `FaceHelper(aligner,
+paster=FacePaster(...))`; without a paster `FaceHelper.paste_faces_to_input_image` raises as before.
 
     network  RetinaFace(network_name='resnet50', phase='test'): torchvision's ResNet-50 v1.5 (taps behind layer2 / 3 / 4), an FPN to 256
              channels, three SSH modules, a class / box / landmark head per level; (byte - (104, 117, 123)) in, no resize
@@ -463,10 +464,10 @@ class FaceAligner(HipStages):
 class FaceHelper:
     """The adapter with facexlib.FaceRestoreHelper's method names that `FaceRestorer.enhance(img, has_aligned=False, face_helper=...)` drives,
     one frame at a time.  Detection, fit and warp run in `get_face_landmarks_5` (one `FaceAligner.align`); the count is read from the device
-    once, there.  The paste-back is not built."""
+    once, there.  The paste-back runs on `paster` (a face_paste.FacePaster) when one is given; without one it raises."""
 
-    def __init__(self, aligner: FaceAligner, bgr: bool = False):
-        self.aligner, self.bgr = aligner, bool(bgr)
+    def __init__(self, aligner: FaceAligner, bgr: bool = False, paster=None):
+        self.aligner, self.bgr, self.paster = aligner, bool(bgr), paster
         self.face_size = (FACE_SIZE, FACE_SIZE)
         self.upscale_factor = aligner.upscale_factor
         self.clean_all()
@@ -515,4 +516,26 @@ class FaceHelper:
         self.inverse_affine_matrices = list(self._out["inverse_affine"].cpu().numpy())
 
     def paste_faces_to_input_image(self, save_path=None, upsample_img=None):
-        raise NotImplementedError("paste-back (ParseNet mask, inverse warp, blend) is not built yet")
+        """-> the pasted uint8 array [h_up, w_up, 3] of the one frame (with a paster): the restored faces blended into `upsample_img`, or
+        into the frame, at the aligner's upscale_factor."""
+        if self.paster is None:
+            raise NotImplementedError("paste-back (ParseNet mask, inverse warp, blend) is not built yet")
+        if save_path is not None:
+            raise NotImplementedError("paste_faces_to_input_image(save_path=...) is not built")
+        if self._out is None or self.input_img is None:
+            raise ValueError("read_image and get_face_landmarks_5 first")
+        if len(self.restored_faces) != self._count:
+            raise ValueError(f"{len(self.restored_faces)} restored faces for {self._count} detected ones")
+        import torch
+        h, w = self.input_img.shape[:2]
+        bg = torch.from_numpy(np.ascontiguousarray(self.input_img if upsample_img is None else np.asarray(upsample_img)))[None]
+        dev = self._out["inverse_affine"].device
+        slots = max(self._count, 1)
+        restored = torch.zeros((slots, FACE_SIZE, FACE_SIZE, 3), dtype=torch.uint8)
+        for r, face in enumerate(self.restored_faces):
+            restored[r] = torch.from_numpy(np.ascontiguousarray(face))
+        inv = torch.zeros((1, slots, 2, 3), dtype=torch.float64, device=dev)
+        inv[0, :self._count] = self._out["inverse_affine"]
+        count = torch.tensor([self._count], dtype=torch.int32, device=dev)
+        out = self.paster.paste(bg.to(dev), restored.to(dev), inv, count, self.upscale_factor, self.bgr, frame_size=(h, w))
+        return out[0].cpu().numpy()

@@ -23,8 +23,9 @@ same bits.  There is no CPU fallback: without the library or a GPU a call raises
 
 Scope.  `restore_aligned` is `GFPGANer.enhance(..., has_aligned=True)` for faces that already are 512 x 512 (enhance would cv2.resize
 any other size, which is not restated: NotImplementedError).  Face detection (RetinaFace), the 5-point warp and the parsing-mask
-paste-back are facexlib.FaceRestoreHelper's upstream and stay the caller's here: `enhance(has_aligned=False)` and `as_face_enhancer`
-drive a caller-supplied object with that class's methods.
+paste-back are facexlib.FaceRestoreHelper's and live beside this module (face_align.py and face_paste.py: built, opt-in, UNPINNED):
+`enhance(has_aligned=False)` and `as_face_enhancer` drive an object with that class's methods, `face_align.FaceHelper(aligner,
+paster=face_paste.FacePaster(...))` or the caller's own; `face_paste.FaceEnhancer` runs the three stages for a whole window.
 
 The specification is tests/gfpgan_ref.py.  gfpgan, basicsr, facexlib and OpenCV are third-party packages that are absent here and
 no GFPGANv1.3.pth is available: key names and parity with them are UNPINNED, and the real-weight path of `as_face_enhancer` is
@@ -442,8 +443,8 @@ class FaceRestorer:
     def enhance(self, img, has_aligned: bool = False, only_center_face: bool = False, paste_back: bool = True, weight: float = 0.5, face_helper=None,
                 bg_upsampler=None, upscale: float = 2):
         """GFPGANer.enhance's control flow and return triple (cropped_faces, restored_faces, restored_img).  has_aligned=True needs no
-        helper.  Otherwise `face_helper` is an object with facexlib.FaceRestoreHelper's methods (detection, warp and paste-back are not
-        built here); all cropped faces of the frame go through the net in ONE pass.  `weight` is accepted as GFPGANer accepts it (the clean
+        helper.  Otherwise `face_helper` is an object with facexlib.FaceRestoreHelper's methods (detection, warp and paste-back are
+        face_align.FaceHelper's, the paste-back with a face_paste.FacePaster); all cropped faces of the frame go through the net in ONE pass.  `weight` is accepted as GFPGANer accepts it (the clean
         architecture ignores it)."""
         if has_aligned:
             arr = np.asarray(img)
@@ -489,3 +490,5 @@ class FaceRestorer:
 
 # what stands in front of `restore_aligned` for frames that are not aligned yet: detection, fit and warp (face_align.py)
 from .face_align import FaceAligner, FaceHelper  # noqa: E402,F401
+# ... and what stands behind it: ParseNet, the mask blur and the blend back into the frame (face_paste.py; opt-in)
+from .face_paste import FaceEnhancer, FacePaster  # noqa: E402,F401

@@ -775,14 +775,17 @@ def rgb8_to_nhwc(frames: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
 
 
 def resize_lanczos4_u8(frames: torch.Tensor, dh: int, dw: int, xofs: torch.Tensor, alpha: torch.Tensor, yofs: torch.Tensor,
-                       beta: torch.Tensor) -> torch.Tensor:
-    """uint8 [n, sh, sw, 3] -> [n, dh, dw, 3] with the INTER_LANCZOS4 tables of upscaler.lanczos4_tables (ca_resize_lanczos4_u8)."""
+                       beta: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [n, sh, sw, 3] -> [n, dh, dw, 3] with the INTER_LANCZOS4 tables of upscaler.lanczos4_tables (ca_resize_lanczos4_u8); written
+    into `out` when given."""
     _req_cuda(frames, xofs, alpha, yofs, beta)
     assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous()
     assert xofs.dtype == yofs.dtype == torch.int32 and alpha.dtype == beta.dtype == torch.int16
     assert xofs.numel() == dw and alpha.numel() == 8 * dw and yofs.numel() == dh and beta.numel() == 8 * dh
     n, sh, sw, _ = frames.shape
-    out = torch.empty((n, dh, dw, 3), device=frames.device, dtype=torch.uint8)
+    if out is None:
+        out = torch.empty((n, dh, dw, 3), device=frames.device, dtype=torch.uint8)
+    assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, dh, dw, 3)
     check(lib().ca_resize_lanczos4_u8(_p(frames), _p(out), n, sh, sw, dh, dw, _p(xofs), _p(alpha), _p(yofs), _p(beta), _stream()),
           "ca_resize_lanczos4_u8")
     return out
@@ -2285,3 +2288,115 @@ def face_warp(frames: torch.Tensor, affine: torch.Tensor, count: torch.Tensor, f
     assert faces.dtype == torch.uint8 and faces.is_contiguous() and tuple(faces.shape) == (n * max_faces, FACE_ALIGN_SIZE, FACE_ALIGN_SIZE, 3)
     check(lib().ca_face_warp(_p(frames), _p(affine), _p(count), _p(faces), n, h, w, max_faces, int(bool(bgr)), _stream()), "ca_face_warp")
     return faces
+
+
+# ---- the paste-back behind the face restorer (controlanimate_amd/face_paste.py; csrc/ca_facepaste.hip) ---------------------------------------
+PARSE_CLASSES, PARSE_CPAD, BLUR_TAPS = _capi.CA_PARSE_CLASSES, _capi.CA_PARSE_CPAD, _capi.CA_BLUR_TAPS
+RING_IN, RING_OUT, RING_RES = _capi.CA_RING_IN, _capi.CA_RING_OUT, _capi.CA_RING_RES
+
+
+def _ringed(shape, ring: bool) -> tuple:
+    n, h, w, c = shape
+    return (n, h + 2, w + 2, c) if ring else (n, h, w, c)
+
+
+def parse_prep(faces: torch.Tensor, out: torch.Tensor, reverse: bool = True, ring: bool = False) -> torch.Tensor:
+    """uint8 faces [n, S, S, 3] -> `out` [n, S, S, 32] (ringed: [n, S + 2, S + 2, 32], the interior written): ((byte / 255) - 0.5) / 0.5, the
+    channels reversed by flag, channels 3 .. 31 zero (ca_parse_prep)."""
+    _req_cuda(faces, out)
+    n, s, s2 = _req_rgb8(faces)
+    assert s == s2 and out.is_contiguous() and tuple(out.shape) == _ringed((n, s, s, PARSE_CPAD), ring)
+    check(lib().ca_parse_prep(_p(faces), _p(out), n, s, int(bool(reverse)), int(bool(ring)), dt_code(out.dtype), _stream()), "ca_parse_prep")
+    return out
+
+
+def conv3x3_reflect(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, stride: int = 1, up2: bool = False, leaky: bool = False,
+                    residual: Optional[torch.Tensor] = None, out_f32: bool = False, out: Optional[torch.Tensor] = None, in_ring: bool = False,
+                    out_ring: bool = False, res_ring: bool = False) -> torch.Tensor:
+    """act(Conv2d(k 3, stride)(ReflectionPad2d(1)(u)) + bias + residual) of NHWC x [n, H, W, Cin], u = x or (up2) its nearest x2; w
+    [Cout, 3, 3, Cin]; act = LeakyReLU(0.2) when leaky (ca_conv3x3_reflect).  in_ring / out_ring / res_ring: that operand is a ringed
+    tensor [n, H + 2, W + 2, C] whose interior is read / written."""
+    _req_cuda(x, w, bias, residual, out)
+    assert x.dim() == 4 and x.is_contiguous() and w.dim() == 4 and w.is_contiguous() and w.dtype == x.dtype
+    n, h, wd, cin = x.shape
+    if in_ring:
+        h, wd = h - 2, wd - 2
+    cout = w.shape[0]
+    assert tuple(w.shape[1:]) == (3, 3, cin) and bias.dtype == torch.float32 and bias.numel() == cout
+    lh, lw = (2 * h, 2 * wd) if up2 else (h, wd)
+    gh, gw = (lh - 1) // stride + 1, (lw - 1) // stride + 1
+    odt = torch.float32 if out_f32 else x.dtype
+    oshape = _ringed((n, gh, gw, cout), out_ring)
+    if out is None:
+        out = torch.empty(oshape, dtype=odt, device=x.device)
+    assert tuple(out.shape) == oshape and out.dtype == odt and out.is_contiguous()
+    if residual is not None:
+        assert residual.dtype == x.dtype and residual.is_contiguous() and tuple(residual.shape) == _ringed((n, gh, gw, cout), res_ring)
+    rings = (RING_IN if in_ring else 0) | (RING_OUT if out_ring else 0) | (RING_RES if res_ring and residual is not None else 0)
+    check(lib().ca_conv3x3_reflect(_p(x), _p(w), _p(bias), _p(residual), _p(out), n, h, wd, cin, cout, int(stride), int(bool(up2)), int(bool(leaky)),
+                                   int(bool(out_f32)), rings, dt_code(x.dtype), _stream()), "ca_conv3x3_reflect")
+    return out
+
+
+def ring_fill(x: torch.Tensor, mode: str = "reflect") -> torch.Tensor:
+    """Writes the one-pixel ring of x [n, H + 2, W + 2, C] from its interior, in place: 'reflect' (ReflectionPad2d(1)) or 'replicate'
+    (ca_ring_fill)."""
+    _req_cuda(x)
+    assert x.dim() == 4 and x.is_contiguous() and mode in ("reflect", "replicate")
+    n, h, w, c = x.shape
+    check(lib().ca_ring_fill(_p(x), n, h - 2, w - 2, c, _capi.CA_RING_REFLECT if mode == "reflect" else _capi.CA_RING_REPLICATE, dt_code(x.dtype), _stream()),
+          "ca_ring_fill")
+    return x
+
+
+def parse_mask(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, mask: torch.Tensor, in_ring: bool = False) -> torch.Tensor:
+    """ParseNet's last layer in one launch: the reflected convolution of x [n, H, W, Cin] with w [32, 3, 3, Cin] (19 rows used), the
+    first-maximum argmax and the colour map -> mask uint8 [n, H, W] of 0 / 255 (ca_parse_mask)."""
+    _req_cuda(x, w, bias, mask)
+    assert x.dim() == 4 and x.is_contiguous() and w.is_contiguous() and w.dtype == x.dtype
+    n, h, wd, cin = x.shape
+    if in_ring:
+        h, wd = h - 2, wd - 2
+    assert tuple(w.shape) == (PARSE_CPAD, 3, 3, cin) and bias.dtype == torch.float32 and bias.numel() == PARSE_CPAD
+    assert mask.dtype == torch.uint8 and mask.is_contiguous() and tuple(mask.shape) == (n, h, wd)
+    check(lib().ca_parse_mask(_p(x), _p(w), _p(bias), _p(mask), n, h, wd, cin, PARSE_CLASSES, int(bool(in_ring)), dt_code(x.dtype), _stream()), "ca_parse_mask")
+    return mask
+
+
+def parse_labels(logits: torch.Tensor, labels: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> None:
+    """fp32 logits [.., cols] -> labels uint8 [..] (the first maximum over the 19 classes) and / or the 0 / 255 mask uint8 [..] (ca_parse_labels)."""
+    _req_cuda(logits, labels, mask)
+    assert logits.dtype == torch.float32 and logits.is_contiguous()
+    pixels = logits.numel() // logits.shape[-1]
+    for t in (labels, mask):
+        assert t is None or (t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == pixels)
+    check(lib().ca_parse_labels(_p(logits), _p(labels), _p(mask), pixels, logits.shape[-1], PARSE_CLASSES, _stream()), "ca_parse_labels")
+
+
+def mask_blur(mask: torch.Tensor, taps: torch.Tensor, ws: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """uint8 mask [n, 512, 512] -> `out` float64 [n, 512, 512]: two Gaussian blurs (101 taps, sigma 11, reflect-101) in float64, the outer 10
+    rows and columns zeroed, / 255 (ca_mask_blur).  taps: float64 [51], the centre tap and the 50 behind it; ws: float64 like out."""
+    _req_cuda(mask, taps, ws, out)
+    _req_f64(taps, ws, out)
+    n, s, _ = mask.shape
+    assert mask.dtype == torch.uint8 and mask.is_contiguous() and tuple(mask.shape) == (n, s, s) == tuple(out.shape) == tuple(ws.shape)
+    check(lib().ca_mask_blur(_p(mask), _p(taps), _p(ws), _p(out), n, s, taps.numel(), _stream()), "ca_mask_blur")
+    return out
+
+
+def face_paste(background: torch.Tensor, restored: torch.Tensor, masks: torch.Tensor, inverse_affine: torch.Tensor, count: torch.Tensor, out: torch.Tensor,
+               upscale: float = 1.0) -> torch.Tensor:
+    """The blend of every frame's faces r < count into its background, one launch per window (ca_face_paste): background and out uint8
+    [n, H, W, 3], restored uint8 [n * max_faces, 512, 512, 3], masks float64 [n * max_faces, 512, 512], inverse_affine float64
+    [n, max_faces, 2, 3] (read only: the 0.5 upscale offset is applied inside), count int32 [n]."""
+    _req_cuda(background, restored, masks, inverse_affine, count, out)
+    _req_f64(masks, inverse_affine)
+    n, h, w = _req_rgb8(background)
+    max_faces = inverse_affine.shape[1]
+    assert tuple(inverse_affine.shape) == (n, max_faces, 2, 3) and count.dtype == torch.int32 and count.numel() == n and count.is_contiguous()
+    assert restored.dtype == torch.uint8 and restored.is_contiguous() and tuple(restored.shape) == (n * max_faces, FACE_ALIGN_SIZE, FACE_ALIGN_SIZE, 3)
+    assert tuple(masks.shape) == (n * max_faces, FACE_ALIGN_SIZE, FACE_ALIGN_SIZE)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n, h, w, 3)
+    check(lib().ca_face_paste(_p(background), _p(restored), _p(masks), _p(inverse_affine), _p(count), _p(out), n, h, w, max_faces, float(upscale), _stream()),
+          "ca_face_paste")
+    return out

@@ -17,10 +17,11 @@ x2 upsamplings are folded into the gather of conv_up1 / conv_up2.  There is no C
 
 GFPGAN face restoration (use_face_enhancer) is a detector + aligner + restoration network + paste-back of its own.  The network is
 built for ALIGNED 512 x 512 faces in gfpgan.py (GFPGANv1Clean on the HIP kernels, no CPU fallback, UNPINNED against gfpgan and real
-weights); face detection, the 5-point warp and the parsing-mask paste-back are facexlib's and stay the caller's.  The call that gives
-the reference's behaviour is `Upscaler(scale, face_enhancer=FaceRestorer(weights).as_face_enhancer(face_helper))` with a caller-supplied
-helper that has facexlib.FaceRestoreHelper's methods; any other `face_enhancer` callable works as before.  Nothing here changes:
-without a callable, use_face_enhancer=True still raises.
+weights); face detection and the 5-point warp (face_align.py) and the parsing-mask paste-back (face_paste.py) are built, opt-in and
+UNPINNED against facexlib.  The call that gives the reference's behaviour is `Upscaler(scale, face_enhancer=FaceEnhancer(aligner,
+restorer, paster).as_face_enhancer())` with the aligner built at upscale_factor = scale, or `FaceRestorer(weights).as_face_enhancer(
+face_helper)` with `FaceHelper(aligner, paster=paster)` or a caller-supplied helper that has facexlib.FaceRestoreHelper's methods; any
+other `face_enhancer` callable works as before.  Nothing here changes: without a callable, use_face_enhancer=True still raises.
 """
 from __future__ import annotations
 

@@ -1432,6 +1432,61 @@ int ca_face_align(const float* dets, const int32_t* count, int32_t images, int32
 int ca_face_warp(const uint8_t* frames, const double* affine, const int32_t* count, uint8_t* faces, int32_t images, int32_t h, int32_t w, int32_t max_faces,
                  int32_t bgr, void* stream);
 
+/* ---- added to ABI v16 likewise: the paste-back behind the face restorer -- facexlib's ParseNet, the parsing mask's two Gaussian blurs, the
+ * inverse warp and the blend of FaceRestoreHelper.paste_faces_to_input_image (controlanimate_amd/face_paste.py; csrc/ca_facepaste.hip; the
+ * specification is tests/facepaste_ref.py).  ParseNet pads by REFLECTION: its convolutions run on ca_conv3x3_reflect, or -- the stride-1
+ * ones, by a host-side switch -- on the zero-padded ca_conv3x3 over a ringed tensor that ca_ring_fill completes.  `rings` / `ring` say which
+ * operands are ringed tensors [n, H + 2, W + 2, C] of which the interior is addressed.  No entry reads device data on the host, none uses
+ * atomics: two runs give the same bits and the chain can be captured in a hipGraph. ---- */
+#define CA_PARSE_CLASSES 19           /* ParseNet's parsing maps; MASK_COLORMAP is 0 for classes 0, 14, 16, 17, 18 and 255 for the rest */
+#define CA_PARSE_CPAD 32              /* channels of ca_parse_prep's output, and rows of the last layer's padded weight */
+#define CA_BLUR_TAPS 51               /* the centre tap and the 50 behind it of the symmetric 101-tap kernel */
+#define CA_RING_IN 1                  /* rings: x is ringed */
+#define CA_RING_OUT 2                 /*        y is ringed (its interior is written, its ring is left alone) */
+#define CA_RING_RES 4                 /*        the residual is ringed */
+#define CA_RING_REFLECT 0             /* ca_ring_fill's mode: ring row 0 = interior row 1 (ReflectionPad2d(1)) */
+#define CA_RING_REPLICATE 1           /*                      ring row 0 = interior row 0 */
+
+/* uint8 faces [images, size, size, 3] -> out [images, size, size, 32] of dtype (ringed when ring = 1): channel c = ((byte / 255) - 0.5) / 0.5
+ * of channel c (reverse = 0) or 2 - c (reverse = 1), each operation in fp32, rounded once to dtype; channels 3 .. 31 are zero. */
+int ca_parse_prep(const uint8_t* faces, void* out, int32_t images, int32_t size, int32_t reverse, int32_t ring, int32_t dtype, void* stream);
+
+/* y [images, gh, gw, cout] = act(Conv2d(k 3, stride, padding 0)(ReflectionPad2d(1)(u)) + bias + residual), u = x [images, h, w, cin] or, with
+ * up2 = 1, its nearest x2 (the x2 plane is never written: reflection on it is replication of x's border).  gh = (lh - 1) / stride + 1 with
+ * lh = h or 2 h.  wt of dtype [cout][3][3][cin]; bias fp32 [cout]; residual of dtype [images, gh, gw, cout] or NULL; act = LeakyReLU(0.2) when
+ * leaky; y of dtype, or fp32 when out_f32.  cin and cout each 32, 64, 128 or 256; stride 1 or 2, up2 only at stride 1.  An implicit GEMM on
+ * the MFMA from an LDS halo tile whose load applies the reflection as an index map; fp32 sums. */
+int ca_conv3x3_reflect(const void* x, const void* wt, const float* bias, const void* residual, void* y, int32_t images, int32_t h, int32_t w, int32_t cin,
+                       int32_t cout, int32_t stride, int32_t up2, int32_t leaky, int32_t out_f32, int32_t rings, int32_t dtype, void* stream);
+
+/* ParseNet's last layer in one launch: the reflected stride-1 convolution of x [images, h, w, cin] (ringed when ring = 1) with wt of dtype
+ * [32][3][3][cin] (rows classes .. 31 zero) and bias fp32 [32], the first maximum over the `classes` logits (the lowest index wins a tie) and
+ * the colour map -> mask uint8 [images, h, w] of 0 / 255.  The logits never reach memory.  classes = CA_PARSE_CLASSES. */
+int ca_parse_mask(const void* x, const void* wt, const float* bias, uint8_t* mask, int32_t images, int32_t h, int32_t w, int32_t cin, int32_t classes,
+                  int32_t ring, int32_t dtype, void* stream);
+
+/* The composed form's tail: logits fp32 [pixels, cols] -> labels uint8 [pixels] (the first maximum over columns 0 .. classes - 1) and / or
+ * mask uint8 [pixels] (the colour map of the label). */
+int ca_parse_labels(const float* logits, uint8_t* labels, uint8_t* mask, int64_t pixels, int32_t cols, int32_t classes, void* stream);
+
+/* Writes the one-pixel ring of x [images, h + 2, w + 2, c] of dtype from its interior (corners included), by CA_RING_REFLECT or
+ * CA_RING_REPLICATE.  c a multiple of 8. */
+int ca_ring_fill(void* x, int32_t images, int32_t h, int32_t w, int32_t c, int32_t mode, int32_t dtype, void* stream);
+
+/* mask uint8 [images, 512, 512] -> out float64 [images, 512, 512]: cv2.GaussianBlur(., (101, 101), 11) twice (each a row pass, then a column
+ * pass, BORDER_REFLECT_101), the outer 10 rows and columns zeroed, divided by 255.  taps float64 [ntaps = CA_BLUR_TAPS]: the normalised
+ * kernel's centre tap k0 and k1 .. k50.  A pass computes k0 x0 + sum over i = 1 .. 50, in that order, of k_i (x_-i + x_+i), every product and
+ * sum rounded by itself.  workspace float64 [images, 512, 512], not out.  size must be 512. */
+int ca_mask_blur(const uint8_t* mask, const double* taps, double* workspace, double* out, int32_t images, int32_t size, int32_t ntaps, void* stream);
+
+/* out uint8 [images, h, w, 3]: every pixel starts from background [images, h, w, 3] and walks the faces r < count[image] in order:
+ * v = cv2.warpAffine(restored[image * max_faces + r], M, (w, h)) in OpenCV's fixed point with border 0, m = the bilinear sample of
+ * masks[image * max_faces + r] (float64 [., 512, 512]) at the same coordinates (5 fractional bits, four products summed in double, border 0),
+ * pixel = m v + (1 - m) pixel in float64; one truncation to uint8 at the end.  M = inverse_affine float64 [images, max_faces, 2, 3] with
+ * 0.5 upscale added to its translation column when upscale > 1 (inside the kernel; the matrices are only read).  out may be background. */
+int ca_face_paste(const uint8_t* background, const uint8_t* restored, const double* masks, const double* inverse_affine, const int32_t* count, uint8_t* out,
+                  int32_t images, int32_t h, int32_t w, int32_t max_faces, double upscale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
