@@ -47,7 +47,8 @@ from typing import NamedTuple
 
 import numpy as np
 
-from .annotator_base import AnnotatorBase, BufferPlan, HipStages, check_state_dict as _check_state_dict, device_weights, load_state_dict
+from . import annotator_base as _base
+from .annotator_base import FrameIntake, PackedNetwork, bn_key_shapes as _bn, check_state_dict as _check_state_dict, pack_conv, pack_pointwise
 
 WEIGHTS_NAME = "detection_Resnet50_Final.pth"
 STAGES = ("stem", "body", "fpn_ssh", "heads", "decode", "warp")
@@ -82,10 +83,6 @@ def check_geometry(geo) -> None:
           and geo.out_channels % 32 == 0)
     if not ok:
         raise ValueError(f"geometry out of the kernels' range (stem a multiple of 8 in 8 .. 64, four layer widths and out_channels multiples of 32): {geo}")
-
-
-def _bn(prefix: str, c: int) -> dict:
-    return {f"{prefix}.weight": (c,), f"{prefix}.bias": (c,), f"{prefix}.running_mean": (c,), f"{prefix}.running_var": (c,)}
 
 
 def blocks_of(geo):
@@ -153,10 +150,7 @@ def check_state_dict(sd, geo=RESNET50) -> None:
 
 def fold_bn(sd, conv: str, bn: str):
     """(weight, bias) in fp32 of the bias-free convolution `conv` followed by the eval-mode BatchNorm `bn`."""
-    import torch
-    w = sd[conv + ".weight"].detach().float()
-    scale = sd[bn + ".weight"].detach().float() / torch.sqrt(sd[bn + ".running_var"].detach().float() + BN_EPS)
-    return w * scale.view(-1, 1, 1, 1), sd[bn + ".bias"].detach().float() - sd[bn + ".running_mean"].detach().float() * scale
+    return _base.fold_bn(sd, conv, bn, BN_EPS)
 
 
 def pack_stem(w, dtype):
@@ -175,28 +169,26 @@ def pack_network(sd, geo, dtype) -> dict:
     """The packed weights of the chain as a tree of host tensors: BatchNorm folded in fp32, rounded once to dtype where a kernel reads dtype."""
     import torch
 
-    def lin(wb):    # [Cout, Cin, 1, 1] -> [Cout, Cin]
-        return wb[0].reshape(wb[0].shape[0], -1).contiguous().to(dtype), wb[1].contiguous()
+    def lin(name, bn):
+        return pack_pointwise(fold_bn(sd, name, bn), dtype)
 
-    def conv(wb):   # [Cout, Cin, 3, 3] -> [Cout, 3, 3, Cin]
-        return wb[0].permute(0, 2, 3, 1).contiguous().to(dtype), wb[1].contiguous()
+    def conv(name, bn):
+        return pack_conv(fold_bn(sd, name, bn), dtype)
 
     stem = fold_bn(sd, "body.conv1", "body.bn1")
     out = {"stem": (pack_stem(stem[0], dtype), stem[1].contiguous()), "blocks": [], "ssh": [], "heads": []}
     for li, b, _, _, _, _ in blocks_of(geo):
         p = f"body.layer{li}.{b}"
-        blk = {"conv1": lin(fold_bn(sd, p + ".conv1", p + ".bn1")), "conv2": conv(fold_bn(sd, p + ".conv2", p + ".bn2")),
-               "conv3": lin(fold_bn(sd, p + ".conv3", p + ".bn3"))}
+        blk = {"conv1": lin(p + ".conv1", p + ".bn1"), "conv2": conv(p + ".conv2", p + ".bn2"), "conv3": lin(p + ".conv3", p + ".bn3")}
         if b == 0:
-            blk["down"] = lin(fold_bn(sd, p + ".downsample.0", p + ".downsample.1"))
+            blk["down"] = lin(p + ".downsample.0", p + ".downsample.1")
         out["blocks"].append(blk)
-    out["output"] = [lin(fold_bn(sd, f"fpn.output{k}.0", f"fpn.output{k}.1")) for k in (1, 2, 3)]
-    out["merge"] = [conv(fold_bn(sd, f"fpn.merge{k}.0", f"fpn.merge{k}.1")) for k in (1, 2)]
+    out["output"] = [lin(f"fpn.output{k}.0", f"fpn.output{k}.1") for k in (1, 2, 3)]
+    out["merge"] = [conv(f"fpn.merge{k}.0", f"fpn.merge{k}.1") for k in (1, 2)]
     for k in (1, 2, 3):
-        out["ssh"].append({name: conv(fold_bn(sd, f"ssh{k}.{name}.0", f"ssh{k}.{name}.1")) for name in SSH_CONVS})
-        w = torch.cat([sd[f"{name}.{k - 1}.conv1x1.weight"].detach().float().reshape(2 * width, -1) for name, width in HEADS])
-        b = torch.cat([sd[f"{name}.{k - 1}.conv1x1.bias"].detach().float() for name, _ in HEADS])
-        out["heads"].append((w.contiguous().to(dtype), b.contiguous()))
+        out["ssh"].append({name: conv(f"ssh{k}.{name}.0", f"ssh{k}.{name}.1") for name in SSH_CONVS})
+        out["heads"].append(pack_pointwise((torch.cat([sd[f"{name}.{k - 1}.conv1x1.weight"] for name, _ in HEADS]),
+                                            torch.cat([sd[f"{name}.{k - 1}.conv1x1.bias"] for name, _ in HEADS])), dtype))
     return out
 
 
@@ -232,20 +224,13 @@ def unpack_heads(levels) -> tuple:
     return np.concatenate(cls, 1), np.concatenate(box, 1), np.concatenate(ldm, 1)
 
 
-class FaceAligner(HipStages):
+class FaceAligner(FrameIntake, PackedNetwork):
     """`FaceAligner.from_pretrained(path).align(frames)`: detection and alignment of the faces of a window on the HIP kernels.  Non-uint8
     input raises TypeError, frames of different sizes ValueError, sizes out of scope NotImplementedError -- all before the device is
     touched; without the library or a GPU a call raises CAHipUnavailable (there is no CPU fallback)."""
 
     WEIGHTS_NAME = WEIGHTS_NAME
     STAGES = STAGES
-    max_activation_bytes = AnnotatorBase.max_activation_bytes
-    _addressed_by = AnnotatorBase._addressed_by
-    _grey_to_rgb = True
-    _dev = None
-    _weights = device_weights
-    _frames = AnnotatorBase._frames
-    chunk_frames = AnnotatorBase.chunk_frames
 
     def __init__(self, state_dict_or_path, max_faces: int = 4, conf_threshold: float = 0.97, nms_threshold: float = 0.4, eye_dist_threshold: float = 5,
                  upscale_factor: float = 1, dtype=None, device=None, geometry=RESNET50):
@@ -259,7 +244,7 @@ class FaceAligner(HipStages):
             raise ValueError(f"conf_threshold={conf_threshold} (0 <= . < 1), nms_threshold={nms_threshold} (0 .. 1), eye_dist_threshold={eye_dist_threshold} "
                              f"(>= 0), upscale_factor={upscale_factor} (> 0)")
         check_geometry(geometry)
-        sd = load_state_dict(state_dict_or_path, WEIGHTS_NAME) if isinstance(state_dict_or_path, (str, os.PathLike)) else state_dict_or_path
+        sd = self._load(state_dict_or_path) if isinstance(state_dict_or_path, (str, os.PathLike)) else state_dict_or_path
         sd = strip_module_prefix(sd)
         check_state_dict(sd, geometry)
         self.device, self.dtype, self.geometry, self.max_faces = device, dtype, geometry, int(max_faces)
@@ -274,7 +259,7 @@ class FaceAligner(HipStages):
     def from_pretrained(cls, path, max_faces: int = 4, conf_threshold: float = 0.97, nms_threshold: float = 0.4, eye_dist_threshold: float = 5,
                         upscale_factor: float = 1, dtype=None, device=None, **kwargs):
         """path: a local detection_Resnet50_Final.pth or a directory that holds it (no network access, ever)."""
-        return cls(load_state_dict(path, WEIGHTS_NAME), max_faces=max_faces, conf_threshold=conf_threshold, nms_threshold=nms_threshold,
+        return cls(cls._load(path), max_faces=max_faces, conf_threshold=conf_threshold, nms_threshold=nms_threshold,
                    eye_dist_threshold=eye_dist_threshold, upscale_factor=upscale_factor, dtype=dtype, device=device, **kwargs)
 
     # ---- input checks ----------------------------------------------------------------------------------------------------------
@@ -290,20 +275,19 @@ class FaceAligner(HipStages):
         layers of a pass take and give back in a fixed order (the first pass allocates them, every later pass reuses the same ones)."""
         import torch
         from . import kernels as K
-        key = (n, h, w)
-        if key not in self._ws:
-            dev = self._device()
-            mf = self.max_faces
+        mf = self.max_faces
 
+        def make(dev):
             def new(shape, dtype):
                 return torch.empty(shape, dtype=dtype, device=dev)
 
-            self._ws[key] = {"heads": [new((n, fh, fw, HEAD_COLS), torch.float32) for fh, fw in level_shapes(h, w)],
-                             "decode": new((K.rface_decode_workspace_bytes(n, h, w),), torch.uint8),
-                             "dets": new((n, mf, DET_COLS), torch.float32), "count": new((n,), torch.int32), "overflow": new((n,), torch.int32),
-                             "affine": new((n, mf, 2, 3), torch.float64), "inverse_affine": new((n, mf, 2, 3), torch.float64),
-                             "faces": new((n * mf, FACE_SIZE, FACE_SIZE, 3), torch.uint8), "pool": [], "plan": [], "planned": False}
-        return self._ws[key]
+            return {"heads": [new((n, fh, fw, HEAD_COLS), torch.float32) for fh, fw in level_shapes(h, w)],
+                    "decode": new((K.rface_decode_workspace_bytes(n, h, w),), torch.uint8),
+                    "dets": new((n, mf, DET_COLS), torch.float32), "count": new((n,), torch.int32), "overflow": new((n,), torch.int32),
+                    "affine": new((n, mf, 2, 3), torch.float64), "inverse_affine": new((n, mf, 2, 3), torch.float64),
+                    "faces": new((n * mf, FACE_SIZE, FACE_SIZE, 3), torch.uint8)}
+
+        return self._workspace((n, h, w), make)
 
     # ---- the chain -------------------------------------------------------------------------------------------------------------
     def _network(self, src, ws, i0: int, bgr: bool, taps_out=None) -> None:
@@ -313,88 +297,72 @@ class FaceAligner(HipStages):
         wts = self._weights(src.device)
         geo = self.geometry
         n, h, w, _ = src.shape
-        plan = BufferPlan(ws, self.dtype, src.device)   # the same buffers in the same order on every pass
-        take, give, timed = plan.take, plan.give, self._timed
-
-        def pw(name, x, wb, act, residual=None):
-            """1x1 convolution of NHWC x as a GEMM over its pixels; the residual is added before the activation."""
-            nn, hh, ww, cc = x.shape
-            m, co = nn * hh * ww, wb[0].shape[0]
-            y = take(nn, hh, ww, co)
-            timed(name, K.gemm, x.view(m, cc), wb[0], bias=wb[1], act=act, residual=None if residual is None else residual.view(m, co), out=y.view(m, co))
-            return y
-
-        def c3(name, x, wb, stride=1):
-            nn, hh, ww, _ = x.shape
-            return timed(name, K.conv3x3, x, wb[0], bias=wb[1], stride=stride, act=K.ACT_RELU,
-                         out=take(nn, (hh - 1) // stride + 1, (ww - 1) // stride + 1, wb[0].shape[0]))
-
-        s = timed("stem", K.rface_stem, src, wts["stem"][0], wts["stem"][1], take(n, h // 2, w // 2, geo.stem), bgr)
-        if taps_out is not None:
-            taps_out.append(s.clone())
-        x = timed("body", K.maxpool3x3s2, s, take(n, h // 4, w // 4, geo.stem))
-        give(s)
-        taps = []
-        for (li, b, _, _, _, stride), blk in zip(blocks_of(geo), wts["blocks"]):
-            t = pw("body", x, blk["conv1"], K.ACT_RELU)
-            t2 = c3("body", t, blk["conv2"], stride)
-            give(t)
-            idn = x
-            if b == 0:
-                if stride == 2:
-                    sub = timed("body", K.subsample2, x, take(x.shape[0], x.shape[1] // 2, x.shape[2] // 2, x.shape[3]))
-                    idn = pw("body", sub, blk["down"], K.ACT_NONE)
-                    give(sub)
-                else:
-                    idn = pw("body", x, blk["down"], K.ACT_NONE)
-            y = pw("body", t2, blk["conv3"], K.ACT_RELU, residual=idn)
-            give(t2)
-            if idn is not x:
-                give(idn)
-            if not any(x is tp for tp in taps):   # a tap stays until the FPN has read it
-                give(x)
-            x = y
-            if li > 1 and b == LAYERS[li - 1] - 1:
-                taps.append(x)
-        if taps_out is not None:
-            taps_out.extend(tp.clone() for tp in taps)
-        # ---- FPN
-        o = [pw("fpn_ssh", tp, wb, K.ACT_RELU) for tp, wb in zip(taps, wts["output"])]
-        for tp in taps:
-            give(tp)
-        timed("fpn_ssh", K.add_up2, o[1], o[2], o[1])
-        m2 = c3("fpn_ssh", o[1], wts["merge"][1])
-        give(o[1])
-        timed("fpn_ssh", K.add_up2, o[0], m2, o[0])
-        m1 = c3("fpn_ssh", o[0], wts["merge"][0])
-        give(o[0])
-        # ---- SSH and heads
-        for k, (f, ssh, head) in enumerate(zip((m1, m2, o[2]), wts["ssh"], wts["heads"])):
-            nn, hh, ww, c = f.shape
-            m = nn * hh * ww
-            b3 = c3("fpn_ssh", f, ssh["conv3X3"])
-            b51 = c3("fpn_ssh", f, ssh["conv5X5_1"])
-            give(f)
-            cat = take(m, c // 2)                      # [5X5_2 | 7x7_3]
-            b5 = c3("fpn_ssh", b51, ssh["conv5X5_2"])
-            timed("fpn_ssh", K.copy_cols, b5.view(m, c // 4), cat, 0)
-            give(b5)
-            b72 = c3("fpn_ssh", b51, ssh["conv7X7_2"])
-            give(b51)
-            b7 = c3("fpn_ssh", b72, ssh["conv7x7_3"])
-            give(b72)
-            timed("fpn_ssh", K.copy_cols, b7.view(m, c // 4), cat, c // 4)
-            give(b7)
-            timed("heads", K.gemm, b3.view(m, c // 2), head[0], a2=cat, bias=head[1], out_f32=True, out=ws["heads"][k][i0:i0 + nn].view(m, HEAD_COLS))
-            give(b3)
-            give(cat)
-        ws["planned"] = True
+        with self._pass(ws, src.device) as p:   # the same buffers in the same order on every pass
+            take, give, launch, pw, c3 = p.take, p.give, p.launch, p.pointwise, p.conv3x3
+            s = launch("stem", K.rface_stem, src, wts["stem"][0], wts["stem"][1], take(n, h // 2, w // 2, geo.stem), bgr)
+            if taps_out is not None:
+                taps_out.append(s.clone())
+            x = launch("body", K.maxpool3x3s2, s, take(n, h // 4, w // 4, geo.stem))
+            give(s)
+            taps = []
+            for (li, b, _, _, _, stride), blk in zip(blocks_of(geo), wts["blocks"]):
+                t = pw("body", x, blk["conv1"], K.ACT_RELU)
+                t2 = c3("body", t, blk["conv2"], stride, K.ACT_RELU)
+                give(t)
+                idn = x
+                if b == 0:
+                    if stride == 2:
+                        sub = launch("body", K.subsample2, x, take(x.shape[0], x.shape[1] // 2, x.shape[2] // 2, x.shape[3]))
+                        idn = pw("body", sub, blk["down"])
+                        give(sub)
+                    else:
+                        idn = pw("body", x, blk["down"])
+                y = pw("body", t2, blk["conv3"], K.ACT_RELU, residual=idn)   # the residual is added before the activation
+                give(t2)
+                if idn is not x:
+                    give(idn)
+                if not any(x is tp for tp in taps):   # a tap stays until the FPN has read it
+                    give(x)
+                x = y
+                if li > 1 and b == LAYERS[li - 1] - 1:
+                    taps.append(x)
+            if taps_out is not None:
+                taps_out.extend(tp.clone() for tp in taps)
+            # ---- FPN
+            o = [pw("fpn_ssh", tp, wb, K.ACT_RELU) for tp, wb in zip(taps, wts["output"])]
+            for tp in taps:
+                give(tp)
+            launch("fpn_ssh", K.add_up2, o[1], o[2], o[1])
+            m2 = c3("fpn_ssh", o[1], wts["merge"][1], act=K.ACT_RELU)
+            give(o[1])
+            launch("fpn_ssh", K.add_up2, o[0], m2, o[0])
+            m1 = c3("fpn_ssh", o[0], wts["merge"][0], act=K.ACT_RELU)
+            give(o[0])
+            # ---- SSH and heads
+            for k, (f, ssh, head) in enumerate(zip((m1, m2, o[2]), wts["ssh"], wts["heads"])):
+                nn, hh, ww, c = f.shape
+                m = nn * hh * ww
+                b3 = c3("fpn_ssh", f, ssh["conv3X3"], act=K.ACT_RELU)
+                b51 = c3("fpn_ssh", f, ssh["conv5X5_1"], act=K.ACT_RELU)
+                give(f)
+                cat = take(m, c // 2)                      # [5X5_2 | 7x7_3]
+                b5 = c3("fpn_ssh", b51, ssh["conv5X5_2"], act=K.ACT_RELU)
+                launch("fpn_ssh", K.copy_cols, b5.view(m, c // 4), cat, 0)
+                give(b5)
+                b72 = c3("fpn_ssh", b51, ssh["conv7X7_2"], act=K.ACT_RELU)
+                give(b51)
+                b7 = c3("fpn_ssh", b72, ssh["conv7x7_3"], act=K.ACT_RELU)
+                give(b72)
+                launch("fpn_ssh", K.copy_cols, b7.view(m, c // 4), cat, c // 4)
+                give(b7)
+                pw("heads", b3, head, a2=cat, out2d=ws["heads"][k][i0:i0 + nn].view(m, HEAD_COLS), out_f32=True)
+                give(b3)
+                give(cat)
 
     def _heads(self, src, ws, bgr: bool) -> list:
         n, h, w, _ = src.shape
-        step = self.chunk_frames(h, w)
-        for i0 in range(0, n, step):
-            self._network(src[i0:i0 + step], ws, i0, bgr)
+        for i0, sl in self._chunks(n, self.chunk_frames(h, w)):
+            self._network(src[sl], ws, i0, bgr)
         return ws["heads"]
 
     def decode(self, heads, h: int, w: int, ws=None, only_center_face: bool = False, only_keep_largest: bool = False, conf_threshold=None,

@@ -51,7 +51,8 @@ from typing import NamedTuple
 
 import numpy as np
 
-from .annotator_base import AnnotatorBase, BufferPlan, HipStages, check_state_dict as _check_state_dict, device_weights, load_state_dict
+from . import annotator_base as _base
+from .annotator_base import PackedNetwork, bn_key_shapes as _bn, check_state_dict as _check_state_dict, pack_conv
 
 WEIGHTS_NAME = "parsing_parsenet.pth"
 STAGES = ("prep", "encoder", "body", "decoder", "mask", "blur", "paste")
@@ -103,10 +104,6 @@ def has_shortcut(cin: int, cout: int, scale: str) -> bool:
     return not (scale == "none" and cin == cout)
 
 
-def _bn(prefix: str, c: int) -> dict:
-    return {f"{prefix}.weight": (c,), f"{prefix}.bias": (c,), f"{prefix}.running_mean": (c,), f"{prefix}.running_var": (c,)}
-
-
 def parsenet_key_shapes(geo=PARSENET) -> dict:
     """Every tensor of parsing_parsenet.pth that the chain uses (facexlib's names, from memory): name -> shape."""
     out = {"encoder.0.conv2d.weight": (geo.base_ch, 3, 3, 3), "encoder.0.conv2d.bias": (geo.base_ch,)}
@@ -135,35 +132,19 @@ def check_state_dict(sd, geo=PARSENET) -> None:
 def fold_bn(sd, conv: str):
     """(weight, bias) in fp32 of the ConvLayer `conv`: its bias-free convolution followed by its eval-mode BatchNorm when it has one, else
     the convolution's own weight and bias."""
-    import torch
-    w = sd[conv + ".conv2d.weight"].detach().float()
-    bn = conv + ".norm.norm"
-    if bn + ".weight" not in sd:
-        return w, sd[conv + ".conv2d.bias"].detach().float()
-    scale = sd[bn + ".weight"].detach().float() / torch.sqrt(sd[bn + ".running_var"].detach().float() + BN_EPS)
-    return w * scale.view(-1, 1, 1, 1), sd[bn + ".bias"].detach().float() - sd[bn + ".running_mean"].detach().float() * scale
-
-
-def pack_conv(w, b, dtype, cin_pad: int = 0, cout_pad: int = 0):
-    """Conv2d weight [Cout, Cin, 3, 3] and bias (fp32) -> ([Cout', 3, 3, Cin'] of dtype, fp32 [Cout']), zero-padded to cin_pad / cout_pad."""
-    import torch
-    cout, cin = w.shape[:2]
-    co, ci = max(cout, cout_pad), max(cin, cin_pad)
-    wp = torch.zeros((co, 3, 3, ci), dtype=torch.float32)
-    wp[:cout, :, :, :cin] = w.detach().float().permute(0, 2, 3, 1)
-    bp = torch.zeros((co,), dtype=torch.float32)
-    bp[:cout] = b.detach().float()
-    return wp.to(dtype).contiguous(), bp.contiguous()
+    if conv + ".norm.norm.weight" not in sd:
+        return sd[conv + ".conv2d.weight"].detach().float(), sd[conv + ".conv2d.bias"].detach().float()
+    return _base.fold_bn(sd, conv + ".conv2d", conv + ".norm.norm", BN_EPS)
 
 
 def pack_network(sd, geo, dtype) -> dict:
     """The packed weights of the chain as a tree of host tensors: BatchNorm folded in fp32, rounded once to dtype."""
-    out = {"in": pack_conv(*fold_bn(sd, "encoder.0"), dtype, cin_pad=CPAD), "blocks": [],
-           "mask": pack_conv(*fold_bn(sd, "out_mask_conv"), dtype, cout_pad=CPAD)}
+    out = {"in": pack_conv(fold_bn(sd, "encoder.0"), dtype, cin_pad=CPAD), "blocks": [],
+           "mask": pack_conv(fold_bn(sd, "out_mask_conv"), dtype, cout_pad=CPAD)}
     for name, cin, cout, scale in blocks_of(geo):
-        blk = {"conv1": pack_conv(*fold_bn(sd, name + ".conv1"), dtype), "conv2": pack_conv(*fold_bn(sd, name + ".conv2"), dtype)}
+        blk = {"conv1": pack_conv(fold_bn(sd, name + ".conv1"), dtype), "conv2": pack_conv(fold_bn(sd, name + ".conv2"), dtype)}
         if has_shortcut(cin, cout, scale):
-            blk["shortcut"] = pack_conv(*fold_bn(sd, name + ".shortcut_func"), dtype)
+            blk["shortcut"] = pack_conv(fold_bn(sd, name + ".shortcut_func"), dtype)
         out["blocks"].append(blk)
     return out
 
@@ -192,18 +173,13 @@ def _bytes_per_face_pixel(geo) -> int:
     return int(math.ceil(2 * worst))
 
 
-class FacePaster(HipStages):
+class FacePaster(PackedNetwork):
     """`FacePaster.from_pretrained(path).paste(background, restored, inverse_affine, count)`: ParseNet, the mask blur and the blend on the HIP
     kernels.  Non-uint8 input raises TypeError, wrong shapes ValueError -- before the device is touched; without the library or a GPU a call
     raises CAHipUnavailable (there is no CPU fallback)."""
 
     WEIGHTS_NAME = WEIGHTS_NAME
     STAGES = STAGES
-    max_activation_bytes = AnnotatorBase.max_activation_bytes
-    _addressed_by = AnnotatorBase._addressed_by
-    _dev = None
-    _weights = device_weights
-    chunk_frames = AnnotatorBase.chunk_frames
 
     def __init__(self, state_dict_or_path, dtype=None, device=None, geometry=PARSENET):
         import torch
@@ -212,7 +188,7 @@ class FacePaster(HipStages):
             raise TypeError(f"dtype must be torch.float16 or torch.bfloat16, got {dtype}")
         geometry = Geometry(*geometry)
         check_geometry(geometry)
-        sd = load_state_dict(state_dict_or_path, WEIGHTS_NAME) if isinstance(state_dict_or_path, (str, os.PathLike)) else state_dict_or_path
+        sd = self._load(state_dict_or_path) if isinstance(state_dict_or_path, (str, os.PathLike)) else state_dict_or_path
         sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
         check_state_dict(sd, geometry)
         self.device, self.dtype, self.geometry = device, dtype, geometry
@@ -224,7 +200,7 @@ class FacePaster(HipStages):
     @classmethod
     def from_pretrained(cls, path, dtype=None, device=None, **kwargs):
         """path: a local parsing_parsenet.pth or a directory that holds it (no network access, ever)."""
-        return cls(load_state_dict(path, WEIGHTS_NAME), dtype=dtype, device=device, **kwargs)
+        return cls(cls._load(path), dtype=dtype, device=device, **kwargs)
 
     # ---- input checks ----------------------------------------------------------------------------------------------------------
     def _faces(self, faces):
@@ -260,51 +236,47 @@ class FacePaster(HipStages):
         """The buffers of a call with m faces, cached per (m, ring levels): the masks, the blur's scratch and output, and a pool of activation
         buffers that the layers of a pass take and give back in a fixed order (the first pass allocates them, every later pass reuses them)."""
         import torch
-        key = (m, self.ring_levels())
-        if key not in self._ws:
-            dev, s = self._device(), self.geometry.in_size
-            self._ws[key] = {"mask": torch.empty((m, s, s), dtype=torch.uint8, device=dev), "labels": None, "logits": None,
-                             "blur": torch.empty((m, s, s), dtype=torch.float64, device=dev), "soft": torch.empty((m, s, s), dtype=torch.float64, device=dev),
-                             "pool": [], "plan": [], "planned": False}
-        return self._ws[key]
+        s = self.geometry.in_size
+        return self._workspace((m, self.ring_levels()), lambda dev: {
+            "mask": torch.empty((m, s, s), dtype=torch.uint8, device=dev), "labels": None, "logits": None,
+            "blur": torch.empty((m, s, s), dtype=torch.float64, device=dev), "soft": torch.empty((m, s, s), dtype=torch.float64, device=dev)})
 
     # ---- the chain -------------------------------------------------------------------------------------------------------------
-    def _trunk(self, src, ws, bgr: bool):
-        """ParseNet up to the decoder's output for the faces `src` (a chunk) -> (x [m, S, S, head channels] or ringed, its plan).  The caller
-        gives x back."""
+    def _trunk(self, p, src, bgr: bool):
+        """ParseNet up to the decoder's output for the faces `src` (a chunk) on the pass `p` -> x [m, S, S, head channels] or ringed.  The
+        caller gives x back."""
         from . import kernels as K
         wts = self._weights(src.device)
         rings = self.ring_levels()
         m, s = src.shape[0], src.shape[1]
-        plan = BufferPlan(ws, self.dtype, src.device)
-        timed = self._timed
+        launch = p.launch
         filled = set()      # the ringed buffers whose ring holds the reflection of their present interior
 
-        def take(p, c):
-            return plan.take(m, p + 2, p + 2, c) if p in rings else plan.take(m, p, p, c)
+        def take(side, c):
+            return p.take(m, side + 2, side + 2, c) if side in rings else p.take(m, side, side, c)
 
-        def conv(stage, x, p, wb, stride=1, up2=False, leaky=False, residual=None, reflect=False):
-            """One ConvLayer on the plane of side p -> (y, its side).  reflect: ca_conv3x3_reflect whatever the level's route."""
-            po = 2 * p if up2 else (p - 1) // stride + 1
+        def conv(stage, x, side, wb, stride=1, up2=False, leaky=False, residual=None, reflect=False):
+            """One ConvLayer on the plane of side `side` -> (y, its side).  reflect: ca_conv3x3_reflect whatever the level's route."""
+            po = 2 * side if up2 else (side - 1) // stride + 1
             y = take(po, wb[0].shape[0])
-            if p in rings and stride == 1 and not up2 and not reflect:
+            if side in rings and stride == 1 and not up2 and not reflect:
                 if x.data_ptr() not in filled:
-                    timed(stage, K.ring_fill, x)
+                    launch(stage, K.ring_fill, x)
                     filled.add(x.data_ptr())
-                timed(stage, K.conv3x3, x, wb[0], bias=wb[1], residual=residual, act=K.ACT_LEAKY02 if leaky else K.ACT_NONE, out=y, split_k=False)
+                launch(stage, K.conv3x3, x, wb[0], bias=wb[1], residual=residual, act=K.ACT_LEAKY02 if leaky else K.ACT_NONE, out=y, split_k=False)
             else:
-                timed(stage, K.conv3x3_reflect, x, wb[0], wb[1], stride=stride, up2=up2, leaky=leaky, residual=residual, out=y, in_ring=p in rings,
-                      out_ring=po in rings, res_ring=po in rings)
+                launch(stage, K.conv3x3_reflect, x, wb[0], wb[1], stride=stride, up2=up2, leaky=leaky, residual=residual, out=y, in_ring=side in rings,
+                       out_ring=po in rings, res_ring=po in rings)
             filled.discard(y.data_ptr())
             return y, po
 
         def give(t):
             filled.discard(t.data_ptr())
-            plan.give(t)
+            p.give(t)
 
         x0 = take(s, CPAD)
-        timed("prep", K.parse_prep, src, x0, not bgr, s in rings)
-        x, p = conv("encoder", x0, s, wts["in"], reflect=True)   # K = 32 of which 3 channels are live: ca_conv3x3 measured 2.2x slower on it
+        launch("prep", K.parse_prep, src, x0, not bgr, s in rings)
+        x, side = conv("encoder", x0, s, wts["in"], reflect=True)   # K = 32 of which 3 channels are live: ca_conv3x3 measured 2.2x slower on it
         give(x0)
         feat = None
         for (name, cin, cout, scale), blk in zip(blocks_of(self.geometry), wts["blocks"]):
@@ -313,20 +285,19 @@ class FacePaster(HipStages):
                 feat = x
             idn = x
             if "shortcut" in blk:
-                idn, _ = conv(stage, x, p, blk["shortcut"], stride=2 if scale == "down" else 1, up2=scale == "up")
-            y, py = conv(stage, x, p, blk["conv1"], up2=scale == "up", leaky=True)
+                idn, _ = conv(stage, x, side, blk["shortcut"], stride=2 if scale == "down" else 1, up2=scale == "up")
+            y, py = conv(stage, x, side, blk["conv1"], up2=scale == "up", leaky=True)
             z, pz = conv(stage, y, py, blk["conv2"], stride=2 if scale == "down" else 1, residual=idn)
             give(y)
             if idn is not x:
                 give(idn)
             if x is not feat:
                 give(x)
-            x, p = z, pz
+            x, side = z, pz
             if name == f"body.{self.geometry.res_depth - 1}":
-                timed("body", K.add_bcast, feat, x, x)      # feat + body(feat), in place (ringed buffers: the rings are rewritten before they are read)
+                launch("body", K.add_bcast, feat, x, x)      # feat + body(feat), in place (ringed buffers: the rings are rewritten before they are read)
                 give(feat)
-        ws["planned"] = True
-        return x, plan
+        return x
 
     def _masks_u8(self, src, ws, bgr: bool, composed: bool = False):
         """The 0 / 255 masks of all faces into ws["mask"], in chunks; composed: through fp32 logits (kept in ws["logits"]) and ws["labels"]."""
@@ -334,21 +305,20 @@ class FacePaster(HipStages):
         from . import kernels as K
         m, s = src.shape[0], src.shape[1]
         passes = -(-m // self.chunk_frames(s + 2, s + 2))
-        step = -(-m // passes)      # an even split
         wts = self._weights(src.device)
         if composed and ws["logits"] is None:
             ws["logits"] = torch.empty((m, s, s, CPAD), dtype=torch.float32, device=src.device)
             ws["labels"] = torch.empty((m, s, s), dtype=torch.uint8, device=src.device)
-        for i0 in range(0, m, step):
-            x, plan = self._trunk(src[i0:i0 + step], ws, bgr)
-            ring = s in self.ring_levels()
-            if composed:
-                lg = ws["logits"][i0:i0 + step]
-                self._timed("mask", K.conv3x3_reflect, x, wts["mask"][0], wts["mask"][1], out_f32=True, out=lg, in_ring=ring)
-                self._timed("mask", K.parse_labels, lg, ws["labels"][i0:i0 + step], ws["mask"][i0:i0 + step])
-            else:
-                self._timed("mask", K.parse_mask, x, wts["mask"][0], wts["mask"][1], ws["mask"][i0:i0 + step], ring)
-            plan.give(x)
+        ring = s in self.ring_levels()
+        for _, sl in self._chunks(m, -(-m // passes)):      # an even split
+            with self._pass(ws, src.device) as p:
+                x = self._trunk(p, src[sl], bgr)
+                if composed:
+                    p.launch("mask", K.conv3x3_reflect, x, wts["mask"][0], wts["mask"][1], out_f32=True, out=ws["logits"][sl], in_ring=ring)
+                    p.launch("mask", K.parse_labels, ws["logits"][sl], ws["labels"][sl], ws["mask"][sl])
+                else:
+                    p.launch("mask", K.parse_mask, x, wts["mask"][0], wts["mask"][1], ws["mask"][sl], ring)
+                p.give(x)
         return ws["mask"]
 
     # ---- the public surface ------------------------------------------------------------------------------------------------------

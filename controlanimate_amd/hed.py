@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import os
 
-from .annotator_base import AnnotatorBase, check_state_dict as _check_state_dict
+from .annotator_base import AnnotatorBase, check_state_dict as _check_state_dict, pack_conv
 
 HED_BLOCKS = ((3, 64, 2), (64, 128, 2), (128, 256, 3), (256, 512, 3), (512, 512, 3))  # (in, out, layers) of block1 .. block5
 WEIGHTS_NAME = "ControlNetHED.pth"
@@ -72,12 +72,7 @@ class HedAnnotator(AnnotatorBase):
         # packed once, on the host: [cout][3][3][cin] in `dtype` (cin zero-padded to 8 for the first), fp32 biases, projections as fp32 rows
         self._host = {"norm": sd["norm"].detach().float().reshape(3).contiguous(), "blocks": []}
         for b, (cin, cout, layers) in enumerate(HED_BLOCKS, start=1):
-            convs = []
-            for i in range(layers):
-                w = sd[f"block{b}.convs.{i}.weight"].detach().float().permute(0, 2, 3, 1)
-                if w.shape[3] % _CIN_PAD:
-                    w = torch.nn.functional.pad(w, (0, _CIN_PAD - w.shape[3] % _CIN_PAD))
-                convs.append((w.contiguous().to(dtype), sd[f"block{b}.convs.{i}.bias"].detach().float().contiguous()))
+            convs = [pack_conv((sd[f"block{b}.convs.{i}.weight"], sd[f"block{b}.convs.{i}.bias"]), dtype, cin_pad=_CIN_PAD) for i in range(layers)]
             self._host["blocks"].append((convs, sd[f"block{b}.projection.weight"].detach().float().reshape(cout).contiguous(),
                                          sd[f"block{b}.projection.bias"].detach().float().reshape(1).contiguous()))
         self._ws = {}   # (`timings` receives events under "prep", "conv", "pool_side", "fuse" -- tools/bench_hed.py)
@@ -87,13 +82,9 @@ class HedAnnotator(AnnotatorBase):
         """(two ping-pong activation buffers for a chunk of frames, the five float32 side maps [n, h >> k, w >> k]) of a call with n frames
         of h x w pixels, cached per (n, h, w); contents are never assumed."""
         import torch
-        key = (n, h, w)
-        if key not in self._ws:
-            dev = self._device()
-            elems = min(n, self.chunk_frames(h, w)) * h * w * 64
-            self._ws[key] = ([torch.empty(elems, dtype=self.dtype, device=dev) for _ in range(2)],
-                             [torch.empty((n, h >> k, w >> k), dtype=torch.float32, device=dev) for k in range(5)])
-        return self._ws[key]
+        return self._workspace((n, h, w), lambda dev: (
+            [torch.empty(min(n, self.chunk_frames(h, w)) * h * w * 64, dtype=self.dtype, device=dev) for _ in range(2)],
+            [torch.empty((n, h >> k, w >> k), dtype=torch.float32, device=dev) for k in range(5)]))
 
     # ---- input checks ----------------------------------------------------------------------------------------------------------
     def _check_size(self, h: int, w: int) -> None:
@@ -131,9 +122,8 @@ class HedAnnotator(AnnotatorBase):
         from . import kernels as K
         n, h, w, _ = src.shape
         bufs, sides = self.workspace(n, h, w)
-        step = self.chunk_frames(h, w)
-        for i0 in range(0, n, step):
-            self._network(src[i0:i0 + step], bufs, sides, i0)
+        for i0, sl in self._chunks(n, self.chunk_frames(h, w)):
+            self._network(src[sl], bufs, sides, i0)
         if edges is not None or control is not None:
             self._timed("fuse", K.hed_fuse, sides, edges=edges, control=control, rep=rep)
         return sides

@@ -37,7 +37,7 @@ from __future__ import annotations
 
 import os
 
-from .annotator_base import AnnotatorBase, check_state_dict as _check_state_dict, load_state_dict
+from .annotator_base import AnnotatorBase, check_state_dict as _check_state_dict, load_state_dict, pack_conv
 
 WEIGHTS_NAME,WEIGHTS_NAME_COARSE = "sk_model.pth", "sk_model2.pth"
 N_RES_BLOCKS = 3
@@ -111,8 +111,8 @@ class LineartAnnotator(AnnotatorBase):
         check_state_dict(sd)
         self.device, self.dtype = device, dtype
 
-        def conv(key):  # [Cout, Cin, 3, 3] -> [Cout, 3, 3, Cin]
-            return sd[key + ".weight"].detach().float().permute(0, 2, 3, 1).contiguous().to(dtype)
+        def conv(key):
+            return pack_conv((sd[key + ".weight"], None), dtype)[0]
 
         # packed once, on the host; every bias but the last cancels in the InstanceNorm behind it
         self._host = {
@@ -140,17 +140,17 @@ class LineartAnnotator(AnnotatorBase):
         sums, the float32 logits [n, h, w]) of a call with n frames of h x w pixels, cached per (n, h, w); contents are never assumed."""
         import torch
         from . import _capi
-        key = (n, h, w)
-        if key not in self._ws:
-            dev = self._device()
+
+        def make(dev):
             m = min(n, self.chunk_frames(h, w))
             lib = _capi.lib()
             floats = max(int(lib.ca_instnorm_partials_floats(m, h >> s, w >> s, c)) for s, c in ((0, 64), (1, 128), (2, 256)))
-            self._ws[key] = ([torch.empty(m * h * w * 64, dtype=self.dtype, device=dev) for _ in range(3)],
-                             torch.empty(m * h * w * 144, dtype=self.dtype, device=dev),
-                             torch.empty(floats, dtype=torch.float32, device=dev),
-                             torch.empty((n, h, w), dtype=torch.float32, device=dev))
-        return self._ws[key]
+            return ([torch.empty(m * h * w * 64, dtype=self.dtype, device=dev) for _ in range(3)],
+                    torch.empty(m * h * w * 144, dtype=self.dtype, device=dev),
+                    torch.empty(floats, dtype=torch.float32, device=dev),
+                    torch.empty((n, h, w), dtype=torch.float32, device=dev))
+
+        return self._workspace((n, h, w), make)
 
     # ---- input checks ----------------------------------------------------------------------------------------------------------
     def _check_size(self, h: int, w: int) -> None:
@@ -206,9 +206,8 @@ class LineartAnnotator(AnnotatorBase):
         from . import kernels as K
         n, h, w, _ = src.shape
         ws = self.workspace(n, h, w)
-        step = self.chunk_frames(h, w)
-        for i0 in range(0, n, step):
-            self._network(src[i0:i0 + step], ws, i0)
+        for i0, sl in self._chunks(n, self.chunk_frames(h, w)):
+            self._network(src[sl], ws, i0)
         if edges is not None or control is not None:
             self._timed("finish", K.lineart_finish, ws[3], edges=edges, control=control, rep=rep)
         return ws[3]

@@ -191,9 +191,8 @@ class LineartAnimeAnnotator(LineartAnnotator):
         (ReLU(d_7 + bias)), "partials" (the InstanceNorm sums) and "pre" (float32 [n, h, w])."""
         import torch
         from . import _capi
-        key = (n, h, w)
-        if key not in self._ws:
-            dev = self._device()
+
+        def make(dev):
             m = min(n, self.chunk_frames(h, w))
             lib = _capi.lib()
             px = [(h >> (i + 1)) * (w >> (i + 1)) for i in range(NUM_DOWNS)]
@@ -203,14 +202,15 @@ class LineartAnimeAnnotator(LineartAnnotator):
                 return torch.empty(elems, dtype=self.dtype, device=dev)
 
             cols = cols_elems(m, h, w)
-            self._ws[key] = {"cols": buf(cols) if cols else None,
-                             "L": [buf(m * px[i] * CHANNELS[i]) for i in range(NUM_DOWNS - 1)],
-                             "C": [buf(m * px[i] * 2 * CHANNELS[i]) for i in range(NUM_DOWNS - 1)],
-                             "raw": buf(m * px[0] * CHANNELS[0]),
-                             "inner": buf(m * px[-1] * CHANNELS[-1]),
-                             "partials": torch.empty(floats, dtype=torch.float32, device=dev),
-                             "pre": torch.empty((n, h, w), dtype=torch.float32, device=dev)}
-        return self._ws[key]
+            return {"cols": buf(cols) if cols else None,
+                    "L": [buf(m * px[i] * CHANNELS[i]) for i in range(NUM_DOWNS - 1)],
+                    "C": [buf(m * px[i] * 2 * CHANNELS[i]) for i in range(NUM_DOWNS - 1)],
+                    "raw": buf(m * px[0] * CHANNELS[0]),
+                    "inner": buf(m * px[-1] * CHANNELS[-1]),
+                    "partials": torch.empty(floats, dtype=torch.float32, device=dev),
+                    "pre": torch.empty((n, h, w), dtype=torch.float32, device=dev)}
+
+        return self._workspace((n, h, w), make)
 
     # ---- input checks ----------------------------------------------------------------------------------------------------------
     def _check_size(self, h: int, w: int) -> None:
@@ -250,9 +250,8 @@ class LineartAnimeAnnotator(LineartAnnotator):
         from . import kernels as K
         n, h, w, _ = src.shape
         ws = self.workspace(n, h, w)
-        step = self.chunk_frames(h, w)
-        for i0 in range(0, n, step):
-            self._network(src[i0:i0 + step], ws, i0)
+        for i0, sl in self._chunks(n, self.chunk_frames(h, w)):
+            self._network(src[sl], ws, i0)
         if edges is not None or control is not None:
             self._timed("finish", K.lanime_finish, ws["pre"], edges=edges, control=control, rep=rep)
         return ws["pre"]

@@ -46,7 +46,8 @@ from __future__ import annotations
 
 import os
 
-from .annotator_base import AnnotatorBase, BufferPlan, check_state_dict as _check_state_dict
+from . import annotator_base as _base
+from .annotator_base import AnnotatorBase, bn_key_shapes as _bn, check_state_dict as _check_state_dict, pack_conv, pack_pointwise
 
 WEIGHTS_NAME = "mlsd_large_512_fp32.pth"
 EPS = 1e-5
@@ -66,10 +67,6 @@ def backbone_blocks():
             out.append((idx, cin, cin * t, c, stride, t != 1, stride == 1 and cin == c))
             cin, idx = c, idx + 1
     return out
-
-
-def _bn(prefix: str, c: int) -> dict:
-    return {f"{prefix}.weight": (c,), f"{prefix}.bias": (c,), f"{prefix}.running_mean": (c,), f"{prefix}.running_var": (c,)}
 
 
 def mlsd_key_shapes() -> dict:
@@ -111,11 +108,7 @@ def check_state_dict(sd) -> None:
 def fold_bn(sd, conv: str, bn: str):
     """(weight, bias) in fp32 of the convolution `conv` followed by the eval-mode BatchNorm `bn`: w * g / sqrt(var + eps) per output
     channel, (b - mean) * g / sqrt(var + eps) + beta."""
-    import torch
-    w = sd[conv + ".weight"].detach().float()
-    b = sd[conv + ".bias"].detach().float() if conv + ".bias" in sd else torch.zeros(w.shape[0])
-    scale = sd[bn + ".weight"].detach().float() / torch.sqrt(sd[bn + ".running_var"].detach().float() + EPS)
-    return w * scale.view(-1, 1, 1, 1), (b - sd[bn + ".running_mean"].detach().float()) * scale + sd[bn + ".bias"].detach().float()
+    return _base.fold_bn(sd, conv, bn, EPS)
 
 
 def folded_layers(sd) -> dict:
@@ -141,9 +134,7 @@ def folded_layers(sd) -> dict:
 
 def pack_depthwise(w):
     """Depthwise weight [C, 1, 3, 3] -> [9, C]: tap ky * 3 + kx of every channel (ca_dwconv3x3)."""
-    if w.dim() != 4 or tuple(w.shape[1:]) != (1, 3, 3):
-        raise ValueError(f"a depthwise weight [C, 1, 3, 3] is expected, got {tuple(w.shape)}")
-    return w.detach().reshape(w.shape[0], 9).t().contiguous()
+    return _base.pack_depthwise(w, (3,))
 
 
 class MlsdAnnotator(AnnotatorBase):
@@ -174,23 +165,15 @@ class MlsdAnnotator(AnnotatorBase):
         self.device, self.dtype = device, dtype
         self.resolution, self.thr_v, self.thr_d = int(detect_resolution), float(thr_v), float(thr_d)
         f = folded_layers(sd)
-
-        def conv(wb):  # [Cout, Cin, 3, 3] -> [Cout, 3, 3, Cin]
-            return wb[0].permute(0, 2, 3, 1).contiguous().to(dtype), wb[1].contiguous()
-
-        def lin(wb):   # [Cout, Cin, 1, 1] -> [Cout, Cin]
-            return wb[0].reshape(wb[0].shape[0], -1).contiguous().to(dtype), wb[1].contiguous()
-
-        stem_w = torch.nn.functional.pad(f["stem"][0], (0, 0, 0, 0, 0, 4))  # 4 -> 8 input channels, the new ones zero
-        head_w, head_b = f["C"][2][0].reshape(16, 64)[7:12], f["C"][2][1][7:12]
         # packed once, on the host
         self._host = {
-            "stem": conv((stem_w, f["stem"][1])),
-            "features": [{k: ((pack_depthwise(v[0]).to(dtype), v[1].contiguous()) if k == "dw" else lin(v)) for k, v in blk.items()} for blk in f["features"]],
-            "A": [(lin(a), lin(b)) for a, b in f["A"]],
-            "B": [(conv(a), conv(b)) for a, b in f["B"]],
-            "C": (conv(f["C"][0]), conv(f["C"][1])),
-            "head": (torch.nn.functional.pad(head_w, (0, 0, 0, 3)).contiguous().to(dtype), torch.nn.functional.pad(head_b, (0, 3)).contiguous()),
+            "stem": pack_conv(f["stem"], dtype, cin_pad=8),   # 4 -> 8 input channels, the new ones zero
+            "features": [{k: ((pack_depthwise(v[0]).to(dtype), v[1].contiguous()) if k == "dw" else pack_pointwise(v, dtype)) for k, v in blk.items()}
+                         for blk in f["features"]],
+            "A": [(pack_pointwise(a, dtype), pack_pointwise(b, dtype)) for a, b in f["A"]],
+            "B": [(pack_conv(a, dtype), pack_conv(b, dtype)) for a, b in f["B"]],
+            "C": (pack_conv(f["C"][0], dtype), pack_conv(f["C"][1], dtype)),
+            "head": pack_pointwise((f["C"][2][0][7:12], f["C"][2][1][7:12]), dtype, cout_pad=8),   # rows 7 .. 11 of conv3, 5 -> 8 rows
         }
         self._ws = {}   # (`timings` receives events under the keys of STAGES -- tools/bench_mlsd.py)
 
@@ -202,16 +185,12 @@ class MlsdAnnotator(AnnotatorBase):
         allocates them -- the largest chunk comes first -- and every later pass reuses the same ones)."""
         import torch
         from . import kernels as K
-        key = (n, h, w)
-        if key not in self._ws:
-            dev = self._device()
-            self._ws[key] = {"tp": torch.empty((n, h // 2, w // 2, 8), dtype=torch.float32, device=dev),
-                             "segments": torch.empty((n, TOPK, 4), dtype=torch.int32, device=dev),
-                             "count": torch.empty((n,), dtype=torch.int32, device=dev),
-                             "decode": torch.empty(K.mlsd_decode_workspace_bytes(n, h // 2, w // 2), dtype=torch.uint8, device=dev),
-                             "map": torch.empty((n, h, w), dtype=torch.uint8, device=dev),
-                             "pool": [], "plan": [], "planned": False}
-        return self._ws[key]
+        return self._workspace((n, h, w), lambda dev: {
+            "tp": torch.empty((n, h // 2, w // 2, 8), dtype=torch.float32, device=dev),
+            "segments": torch.empty((n, TOPK, 4), dtype=torch.int32, device=dev),
+            "count": torch.empty((n,), dtype=torch.int32, device=dev),
+            "decode": torch.empty(K.mlsd_decode_workspace_bytes(n, h // 2, w // 2), dtype=torch.uint8, device=dev),
+            "map": torch.empty((n, h, w), dtype=torch.uint8, device=dev)})
 
     # ---- input checks ----------------------------------------------------------------------------------------------------------
     def _check_size(self, h: int, w: int) -> None:
@@ -227,78 +206,62 @@ class MlsdAnnotator(AnnotatorBase):
         from . import kernels as K
         wts = self._weights(src.device)
         n, h, w, _ = src.shape
-        plan = BufferPlan(ws, self.dtype, src.device)   # the same buffers in the same order on every pass
-        take, give, timed = plan.take, plan.give, self._timed
-
-        def pw(x, wb, act, out2d=None, residual=None, name="pointwise", out_f32=False):
-            """1x1 convolution of NHWC x as a GEMM over its pixels; out2d: a [pixels, N] view (possibly of a wider tensor)."""
-            nn, hh, ww, cc = x.shape
-            m = nn * hh * ww
-            ret = None
-            if out2d is None:
-                ret = take(nn, hh, ww, wb[0].shape[0])
-                out2d = ret.view(m, wb[0].shape[0])
-            timed(name, K.gemm, x.view(m, cc), wb[0], bias=wb[1], act=act, residual=None if residual is None else residual.view(m, -1), out=out2d,
-                  out_f32=out_f32)
-            return ret
-
-        x = timed("prep", K.mlsd_prep, src, take(n, h, w, 8))
-        y = timed("stem", K.conv3x3, x, wts["stem"][0], bias=wts["stem"][1], stride=2, pad_asym=True, act=K.ACT_RELU6, out=take(n, h // 2, w // 2, 32))
-        give(x)
-        x, taps = y, {}
-        for (idx, _, hid, c, stride, expands, skips), blk in zip(backbone_blocks(), wts["features"]):
-            t = pw(x, blk["expand"], K.ACT_RELU6) if expands else x
-            hh, ww = t.shape[1] // stride, t.shape[2] // stride
-            d = timed("depthwise", K.dwconv3x3, t, blk["dw"][0], blk["dw"][1], stride=stride, relu6=True, out=take(n, hh, ww, hid))
-            if expands:
-                give(t)
-            y = pw(d, blk["project"], K.ACT_NONE, residual=x if skips else None)
-            give(d)
-            if idx - 1 in TAPS:   # x is the output of features[idx - 1]: a tap stays until its block A has read it
-                taps[idx - 1] = x
-            else:
-                give(x)
-            x = y
-            if idx == TAPS[-1]:
-                taps[idx] = x
-        c1, c2, c3, c4, c5 = (taps[i] for i in TAPS)
-        x = c5
-        for level, (a, up) in enumerate(((c4, False), (c3, True), (c2, True), (c1, True))):
-            (w1, w2), (b1, b2) = wts["A"][level], wts["B"][level]
-            nn, hh, ww, _ = a.shape
-            cat = take(nn, hh, ww, 128)
-            cat2d = cat.view(nn * hh * ww, 128)
-            pw(a, w2, K.ACT_RELU, out2d=cat2d[:, :64])
-            if up:
-                t = pw(x, w1, K.ACT_RELU)
-                timed("upsample", K.upsample2x_bilinear_ac, t, cat, 64)
-                give(t)
-            else:
-                pw(x, w1, K.ACT_RELU, out2d=cat2d[:, 64:])
-            give(a)
+        with self._pass(ws, src.device) as p:   # the same buffers in the same order on every pass
+            take, give, launch, pw = p.take, p.give, p.launch, p.pointwise
+            x = launch("prep", K.mlsd_prep, src, take(n, h, w, 8))
+            y = p.conv3x3("stem", x, wts["stem"], stride=2, act=K.ACT_RELU6, pad_asym=True)
             give(x)
-            t = timed("conv", K.conv3x3, cat, b1[0], bias=b1[1], act=K.ACT_RELU, out=take(nn, hh, ww, 128))
-            timed("add", K.add_bcast, t, cat, out=t)   # ReLU, then the skip
-            give(cat)
-            x = timed("conv", K.conv3x3, t, b2[0], bias=b2[1], act=K.ACT_RELU, out=take(nn, hh, ww, 64))
+            x, taps = y, {}
+            for (idx, _, hid, c, stride, expands, skips), blk in zip(backbone_blocks(), wts["features"]):
+                t = pw("pointwise", x, blk["expand"], K.ACT_RELU6) if expands else x
+                hh, ww = t.shape[1] // stride, t.shape[2] // stride
+                d = launch("depthwise", K.dwconv3x3, t, blk["dw"][0], blk["dw"][1], stride=stride, relu6=True, out=take(n, hh, ww, hid))
+                if expands:
+                    give(t)
+                y = pw("pointwise", d, blk["project"], residual=x if skips else None)
+                give(d)
+                if idx - 1 in TAPS:   # x is the output of features[idx - 1]: a tap stays until its block A has read it
+                    taps[idx - 1] = x
+                else:
+                    give(x)
+                x = y
+                if idx == TAPS[-1]:
+                    taps[idx] = x
+            c1, c2, c3, c4, c5 = (taps[i] for i in TAPS)
+            x = c5
+            for level, (a, up) in enumerate(((c4, False), (c3, True), (c2, True), (c1, True))):
+                (w1, w2), (b1, b2) = wts["A"][level], wts["B"][level]
+                nn, hh, ww, _ = a.shape
+                cat = take(nn, hh, ww, 128)
+                cat2d = cat.view(nn * hh * ww, 128)
+                pw("pointwise", a, w2, K.ACT_RELU, out2d=cat2d[:, :64])
+                if up:
+                    t = pw("pointwise", x, w1, K.ACT_RELU)
+                    launch("upsample", K.upsample2x_bilinear_ac, t, cat, 64)
+                    give(t)
+                else:
+                    pw("pointwise", x, w1, K.ACT_RELU, out2d=cat2d[:, 64:])
+                give(a)
+                give(x)
+                t = p.conv3x3("conv", cat, b1, act=K.ACT_RELU)
+                launch("add", K.add_bcast, t, cat, out=t)   # ReLU, then the skip
+                give(cat)
+                x = p.conv3x3("conv", t, b2, act=K.ACT_RELU)
+                give(t)
+            (d1, d2) = wts["C"]
+            t = launch("dilated", K.conv3x3_dil, x, d1[0], d1[1], dilation=5, relu=True, out=take(*x.shape))
+            give(x)
+            x = p.conv3x3("conv", t, d2, act=K.ACT_RELU)
             give(t)
-        (d1, d2) = wts["C"]
-        t = timed("dilated", K.conv3x3_dil, x, d1[0], d1[1], dilation=5, relu=True, out=take(*x.shape))
-        give(x)
-        x = timed("conv", K.conv3x3, t, d2[0], bias=d2[1], act=K.ACT_RELU, out=take(*t.shape))
-        give(t)
-        tp = ws["tp"][i0:i0 + n]
-        pw(x, wts["head"], K.ACT_NONE, out2d=tp.view(-1, 8), name="head", out_f32=True)
-        give(x)
-        ws["planned"] = True
+            pw("head", x, wts["head"], out2d=ws["tp"][i0:i0 + n].view(-1, 8), out_f32=True)
+            give(x)
 
     def _run(self, src, edges, control, rep):
         from . import kernels as K
         n, h, w, _ = src.shape
         ws = self.workspace(n, h, w)
-        step = self.chunk_frames(h, w)
-        for i0 in range(0, n, step):
-            self._network(src[i0:i0 + step], ws, i0)
+        for i0, sl in self._chunks(n, self.chunk_frames(h, w)):
+            self._network(src[sl], ws, i0)
         if edges is not None or control is not None:
             self._timed("decode", K.mlsd_decode, ws["tp"], self.thr_v, self.thr_d, segments=ws["segments"], count=ws["count"], ws=ws["decode"])
             self._timed("draw", K.mlsd_draw, ws["segments"], ws["count"], h, w, edges=edges if edges is not None else ws["map"], control=control, rep=rep)

@@ -48,7 +48,8 @@ from typing import NamedTuple
 
 import numpy as np
 
-from .annotator_base import AnnotatorBase, BufferPlan, check_state_dict as _check_state_dict
+from . import annotator_base as _base
+from .annotator_base import AnnotatorBase, bn_key_shapes as _bn, check_state_dict as _check_state_dict, fold_bn, pack_conv, pack_pointwise
 
 WEIGHTS_NAME = "scannet.pt"
 ENCODER_BN_EPS, DECODER_BN_EPS = 1e-3, 1e-5
@@ -85,10 +86,6 @@ def blocks_of(geo):
             out.append((s, b, cin, width, kernel, stride if b == 0 else 1, expand, max(1, cin // 4)))
             cin = width
     return out
-
-
-def _bn(prefix: str, c: int) -> dict:
-    return {f"{prefix}.weight": (c,), f"{prefix}.bias": (c,), f"{prefix}.running_mean": (c,), f"{prefix}.running_var": (c,)}
 
 
 def decoder_widths(geo):
@@ -154,20 +151,9 @@ def check_state_dict(sd, geo=B5) -> None:
                       "decoder.{conv2, up1 .. up4, out_conv_res8, out_conv_res4 / 2 / 1}", ignore=_ignored)
 
 
-def fold_bn(sd, conv: str, bn: str, eps: float):
-    """(weight, bias) in fp32 of the convolution `conv` followed by the eval-mode BatchNorm `bn`."""
-    import torch
-    w = sd[conv + ".weight"].detach().float()
-    b = sd[conv + ".bias"].detach().float() if conv + ".bias" in sd else torch.zeros(w.shape[0])
-    scale = sd[bn + ".weight"].detach().float() / torch.sqrt(sd[bn + ".running_var"].detach().float() + eps)
-    return w * scale.view(-1, *([1] * (w.dim() - 1))), (b - sd[bn + ".running_mean"].detach().float()) * scale + sd[bn + ".bias"].detach().float()
-
-
 def pack_depthwise(w):
     """Depthwise weight [C, 1, k, k] -> [k * k, C]: tap ky * k + kx of every channel (ca_dwconv_same)."""
-    if w.dim() != 4 or w.shape[1] != 1 or w.shape[2] != w.shape[3] or w.shape[2] not in (3, 5):
-        raise ValueError(f"a depthwise weight [C, 1, k, k] with k = 3 or 5 is expected, got {tuple(w.shape)}")
-    return w.detach().reshape(w.shape[0], -1).t().contiguous()
+    return _base.pack_depthwise(w, (3, 5), "[C, 1, k, k] with k = 3 or 5")
 
 
 def pack_stem(w):
@@ -179,15 +165,7 @@ def pack_stem(w):
 
 def pack_network(sd, geo, dtype) -> dict:
     """The packed weights of the chain as a tree of host tensors (BatchNorm folded in fp32, rounded once to dtype where a kernel reads dtype)."""
-    import torch
-    F = torch.nn.functional
     e = "encoder.original_model"
-
-    def lin(wb):    # [Cout, Cin, 1(, 1)] -> [Cout, Cin]
-        return wb[0].reshape(wb[0].shape[0], -1).contiguous().to(dtype), wb[1].contiguous()
-
-    def conv(wb):   # [Cout, Cin, 3, 3] -> [Cout, 3, 3, Cin]
-        return wb[0].permute(0, 2, 3, 1).contiguous().to(dtype), wb[1].contiguous()
 
     def plain(name):
         return sd[name + ".weight"].detach().float(), sd[name + ".bias"].detach().float()
@@ -199,24 +177,23 @@ def pack_network(sd, geo, dtype) -> dict:
         if expand == 1:
             dw, proj = fold_bn(sd, f"{p}.conv_dw", f"{p}.bn1", ENCODER_BN_EPS), fold_bn(sd, f"{p}.conv_pw", f"{p}.bn2", ENCODER_BN_EPS)
         else:
-            blk["expand"] = lin(fold_bn(sd, f"{p}.conv_pw", f"{p}.bn1", ENCODER_BN_EPS))
+            blk["expand"] = pack_pointwise(fold_bn(sd, f"{p}.conv_pw", f"{p}.bn1", ENCODER_BN_EPS), dtype)
             dw, proj = fold_bn(sd, f"{p}.conv_dw", f"{p}.bn2", ENCODER_BN_EPS), fold_bn(sd, f"{p}.conv_pwl", f"{p}.bn3", ENCODER_BN_EPS)
         blk["dw"] = (pack_depthwise(dw[0]).to(dtype), dw[1].contiguous())
         wr, br = plain(f"{p}.se.conv_reduce")
         we, be = plain(f"{p}.se.conv_expand")
         blk["se"] = (wr.reshape(r, -1).contiguous(), br.contiguous(), we.reshape(-1, r).t().contiguous(), be.contiguous())
-        blk["project"] = lin(proj)
+        blk["project"] = pack_pointwise(proj, dtype)
         out["blocks"].append(blk)
-    out["head"] = (sd[f"{e}.conv_head.weight"].detach().float().reshape(geo.head, -1).contiguous().to(dtype), None)
+    out["head"] = pack_pointwise((sd[f"{e}.conv_head.weight"], None), dtype)
     w2, b2 = plain("decoder.conv2")
     w2 = w2.reshape(geo.decoder, geo.head)
     out["conv2"] = [(w2[i:i + UP_MAX_C].contiguous().to(dtype), b2[i:i + UP_MAX_C].contiguous()) for i in range(0, geo.decoder, UP_MAX_C)]
     out["up"] = []
     for i in range(4):
         p = f"decoder.up{i + 1}._net"
-        out["up"].append((conv(fold_bn(sd, f"{p}.0", f"{p}.1", DECODER_BN_EPS)), conv(fold_bn(sd, f"{p}.3", f"{p}.4", DECODER_BN_EPS))))
-    w8, b8 = plain("decoder.out_conv_res8")
-    out["res8"] = conv((F.pad(w8, (0, 0, 0, 0, 0, 0, 0, 4)), F.pad(b8, (0, 4))))     # Cout 4 -> 8, the new ones zero
+        out["up"].append(tuple(pack_conv(fold_bn(sd, f"{p}.{j}", f"{p}.{j + 1}", DECODER_BN_EPS), dtype) for j in (0, 3)))
+    out["res8"] = pack_conv(plain("decoder.out_conv_res8"), dtype, cout_pad=8)   # Cout 4 -> 8, the new ones zero
     mlps = [[plain(f"decoder.out_conv_{name}.{j}") for j in (0, 2, 4, 6)] for name in ("res4", "res2", "res1")]
     out["mlp"] = [pack_mlp(m, dtype) for m in mlps]
     out["mlp_frag"] = [pack_mlp_frag(m, dtype) for m in mlps]   # (None per stage whose widths ca_nbae_refine is not built for)
@@ -341,9 +318,8 @@ class NormalBaeAnnotator(AnnotatorBase):
         import torch
         from . import kernels as K
         from .context import dispatch
-        key = (n, h, w, bool(dispatch.nbae_refine_fused))   # (the two forms of the refinement stages take different buffers: a plan each)
-        if key not in self._ws:
-            dev = self._device()
+
+        def make(dev):
             m = min(n, self.chunk_frames(h, w))
             geo = self.geometry
             cmax, partials, hh, ww = 8, 1, h // 2, w // 2
@@ -355,10 +331,11 @@ class NormalBaeAnnotator(AnnotatorBase):
             def f32(*shape):
                 return torch.empty(shape, dtype=torch.float32, device=dev)
 
-            self._ws[key] = {"pred": f32(n, h, w, 4), "pred8": f32(m, h // 8, w // 8, 4), "pred4": f32(m, h // 4, w // 4, 4), "pred2": f32(m, h // 2, w // 2, 4),
-                             "raw": f32(m * h * w * 8), "sums": f32(m * cmax), "gate": f32(m * cmax), "partials": f32(partials),
-                             "pool": [], "plan": [], "planned": False}
-        return self._ws[key]
+            return {"pred": f32(n, h, w, 4), "pred8": f32(m, h // 8, w // 8, 4), "pred4": f32(m, h // 4, w // 4, 4), "pred2": f32(m, h // 2, w // 2, 4),
+                    "raw": f32(m * h * w * 8), "sums": f32(m * cmax), "gate": f32(m * cmax), "partials": f32(partials)}
+
+        # (the two forms of the refinement stages take different buffers: a plan each)
+        return self._workspace((n, h, w, bool(dispatch.nbae_refine_fused)), make)
 
     # ---- input checks ----------------------------------------------------------------------------------------------------------
     def _check_size(self, h: int, w: int) -> None:
@@ -376,84 +353,69 @@ class NormalBaeAnnotator(AnnotatorBase):
         wts = self._weights(src.device)
         geo = self.geometry
         n, h, w, _ = src.shape
-        plan = BufferPlan(ws, self.dtype, src.device)   # the same buffers in the same order on every pass
-        take, give, timed = plan.take, plan.give, self._timed
-
-        def pw(name, x, wb, act, residual=None, a2=None, out=None, out_f32=False):
-            """1x1 convolution of NHWC x as a GEMM over its pixels (a2: a second source of the same pixels)."""
-            nn, hh, ww, cc = x.shape
-            m, co = nn * hh * ww, wb[0].shape[0]
-            ret = out
-            if out is None:
-                ret = take(nn, hh, ww, co)
-                out = ret.view(m, co)
-            timed(name, K.gemm, x.view(m, cc), wb[0], a2=None if a2 is None else a2.view(m, -1), bias=wb[1], act=act,
-                  residual=None if residual is None else residual.view(m, co), out=out, out_f32=out_f32)
-            return ret
-
-        x = timed("stem", K.nbae_stem, src, wts["stem"][0], wts["stem"][1], take(n, h // 2, w // 2, geo.stem))
-        taps = []
-        for (s, b, cin, cout, _, stride, expand, _), blk in zip(blocks_of(geo), wts["blocks"]):
-            t = pw("encoder", x, blk["expand"], K.ACT_SILU) if expand != 1 else x
-            _, hh, ww, mid = t.shape
-            ho, wo = K.same_out(hh, stride), K.same_out(ww, stride)
-            sums, gate = ws["sums"][:n * mid].view(n, mid), ws["gate"][:n * mid].view(n, mid)
-            d, _ = timed("encoder", K.dwconv_same, t, blk["dw"][0], blk["dw"][1], stride=stride, out=take(n, ho, wo, mid), sums=sums, partials=ws["partials"])
-            if expand != 1:
+        with self._pass(ws, src.device) as p:   # the same buffers in the same order on every pass
+            take, give, launch, pw = p.take, p.give, p.launch, p.pointwise
+            x = launch("stem", K.nbae_stem, src, wts["stem"][0], wts["stem"][1], take(n, h // 2, w // 2, geo.stem))
+            taps = []
+            for (s, b, cin, cout, _, stride, expand, _), blk in zip(blocks_of(geo), wts["blocks"]):
+                t = pw("encoder", x, blk["expand"], K.ACT_SILU) if expand != 1 else x
+                _, hh, ww, mid = t.shape
+                ho, wo = K.same_out(hh, stride), K.same_out(ww, stride)
+                sums, gate = ws["sums"][:n * mid].view(n, mid), ws["gate"][:n * mid].view(n, mid)
+                d, _ = launch("encoder", K.dwconv_same, t, blk["dw"][0], blk["dw"][1], stride=stride, out=take(n, ho, wo, mid), sums=sums, partials=ws["partials"])
+                if expand != 1:
+                    give(t)
+                launch("encoder", K.se_gate, sums, *blk["se"], ho * wo, out=gate)
+                launch("encoder", K.scale_channels, d, gate, out=d)
+                y = pw("encoder", d, blk["project"], residual=x if (stride == 1 and cin == cout) else None)
+                give(d)
+                if not any(x is tp for tp in taps):   # a tap stays until the decoder has read it
+                    give(x)
+                x = y
+                if b == geo.stages[s][1] - 1 and s in TAP_STAGES:
+                    taps.append(x)
+            head = pw("encoder", x, wts["head"])
+            give(x)
+            if taps_out is not None:
+                taps_out.extend(tp.clone() for tp in taps + [head])
+            # ---- decoder
+            parts = [pw("decoder", head, wb) for wb in wts["conv2"]]
+            give(head)
+            xd = []
+            for i, (c1, c2) in enumerate(wts["up"]):
+                skip = taps[3 - i]
+                nn, hh, ww, _ = skip.shape
+                up = take(nn, hh, ww, sum(pt.shape[3] for pt in parts))
+                col = 0
+                for pt in parts:
+                    launch("decoder", K.upsample2x_bilinear_ac, pt, up, col)
+                    col += pt.shape[3]
+                t = p.conv3x3("decoder", up, c1, act=K.ACT_LEAKY001, x2=skip)
+                give(up)
+                give(skip)
+                if i < 2:   # conv2's output and x_d1 are done; x_d2 and x_d3 stay for their refinement stages
+                    for pt in parts:
+                        give(pt)
+                y = p.conv3x3("decoder", t, c2, act=K.ACT_LEAKY001)
                 give(t)
-            timed("encoder", K.se_gate, sums, *blk["se"], ho * wo, out=gate)
-            timed("encoder", K.scale_channels, d, gate, out=d)
-            y = pw("encoder", d, blk["project"], K.ACT_NONE, residual=x if (stride == 1 and cin == cout) else None)
-            give(d)
-            if not any(x is tp for tp in taps):   # a tap stays until the decoder has read it
-                give(x)
-            x = y
-            if b == geo.stages[s][1] - 1 and s in TAP_STAGES:
-                taps.append(x)
-        head = pw("encoder", x, wts["head"], K.ACT_NONE)
-        give(x)
-        if taps_out is not None:
-            taps_out.extend(tp.clone() for tp in taps + [head])
-        # ---- decoder
-        parts = [pw("decoder", head, wb, K.ACT_NONE) for wb in wts["conv2"]]
-        give(head)
-        xd = []
-        for i, (c1, c2) in enumerate(wts["up"]):
-            skip = taps[3 - i]
-            nn, hh, ww, _ = skip.shape
-            up = take(nn, hh, ww, sum(p.shape[3] for p in parts))
-            col = 0
-            for p in parts:
-                timed("decoder", K.upsample2x_bilinear_ac, p, up, col)
-                col += p.shape[3]
-            t = timed("decoder", K.conv3x3, up, c1[0], x2=skip, bias=c1[1], act=K.ACT_LEAKY001, out=take(nn, hh, ww, c1[0].shape[0]))
-            give(up)
-            give(skip)
-            if i < 2:   # conv2's output and x_d1 are done; x_d2 and x_d3 stay for their refinement stages
-                for p in parts:
-                    give(p)
-            y = timed("decoder", K.conv3x3, t, c2[0], bias=c2[1], act=K.ACT_LEAKY001, out=take(nn, hh, ww, c2[0].shape[0]))
-            give(t)
-            xd.append(y)
-            parts = [y]
-        nn, h8, w8, _ = xd[1].shape
-        raw8 = ws["raw"][:nn * h8 * w8 * 8].view(nn, h8, w8, 8)
-        timed("decoder", K.conv3x3, xd[1], wts["res8"][0], bias=wts["res8"][1], out_f32=True, out=raw8)
-        pred = timed("decoder", K.nbae_normalize, raw8.view(-1, 8), ws["pred8"][:nn])
-        # ---- the three refinement stages
-        outs = (ws["pred4"][:nn], ws["pred2"][:nn], ws["pred"][i0:i0 + nn])
-        for feat, layers, frag, out in zip(xd[1:], wts["mlp"], wts["mlp_frag"], outs):
-            pred = refine_stage(feat, pred, layers, out=out, raw=ws["raw"], take=take, give=give, timed=timed, frag=frag)
-            give(feat)
-        ws["planned"] = True
+                xd.append(y)
+                parts = [y]
+            nn, h8, w8, _ = xd[1].shape
+            raw8 = ws["raw"][:nn * h8 * w8 * 8].view(nn, h8, w8, 8)
+            launch("decoder", K.conv3x3, xd[1], wts["res8"][0], bias=wts["res8"][1], out_f32=True, out=raw8)
+            pred = launch("decoder", K.nbae_normalize, raw8.view(-1, 8), ws["pred8"][:nn])
+            # ---- the three refinement stages
+            outs = (ws["pred4"][:nn], ws["pred2"][:nn], ws["pred"][i0:i0 + nn])
+            for feat, layers, frag, out in zip(xd[1:], wts["mlp"], wts["mlp_frag"], outs):
+                pred = refine_stage(feat, pred, layers, out=out, raw=ws["raw"], take=take, give=give, timed=launch, frag=frag)
+                give(feat)
 
     def _run(self, src, map, control, rep):
         from . import kernels as K
         n, h, w, _ = src.shape
         ws = self.workspace(n, h, w)
-        step = self.chunk_frames(h, w)
-        for i0 in range(0, n, step):
-            self._network(src[i0:i0 + step], ws, i0)
+        for i0, sl in self._chunks(n, self.chunk_frames(h, w)):
+            self._network(src[sl], ws, i0)
         if map is not None or control is not None:
             self._timed("finish", K.nbae_finish, ws["pred"], map=map, control=control, rep=rep)
         return ws["pred"]

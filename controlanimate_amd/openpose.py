@@ -68,7 +68,7 @@ import re
 
 import numpy as np
 
-from .annotator_base import AnnotatorBase, BufferPlan, check_state_dict as _check_state_dict
+from .annotator_base import AnnotatorBase, PackedNetwork, check_state_dict as _check_state_dict, pack_conv, pack_pointwise
 
 WEIGHTS_NAME = "body_pose_model.pth"
 MAX_PEAKS, MAX_PEOPLE, AREA_TAPS = 64, 64, 8
@@ -141,19 +141,16 @@ def pack_mconv1(w, heads):
 def cpm_packers(sd, dtype, heads):
     """(conv, lin, mconv1): the layers of a CPM network out of the state dict `sd` (bare names) as (weight in `dtype`, fp32 bias) in the
     kernels' layouts; heads: the concatenation's layout behind the features, as pack_mconv1 takes it."""
-    import torch
-    F = torch.nn.functional
-
     def wb(name):
         return sd[name + ".weight"].detach().float(), sd[name + ".bias"].detach().float().contiguous()
 
     def conv(name, pad_in=0):  # [Cout, Cin, k, k] -> [Cout, k, k, Cin (+ pad_in zero channels)]
         w, b = wb(name)
-        return F.pad(w, (0, 0, 0, 0, 0, pad_in)).permute(0, 2, 3, 1).contiguous().to(dtype), b
+        return pack_conv((w, b), dtype, cin_pad=w.shape[1] + pad_in)
 
     def lin(name, pad_out=0):  # [Cout, Cin, 1, 1] -> [Cout + pad_out zero rows, Cin]
         w, b = wb(name)
-        return F.pad(w.reshape(w.shape[0], -1), (0, 0, 0, pad_out)).contiguous().to(dtype), F.pad(b, (0, pad_out)).contiguous()
+        return pack_pointwise((w, b), dtype, cout_pad=w.shape[0] + pad_out)
 
     def mconv1(name):
         w, b = wb(name)
@@ -173,61 +170,69 @@ def pack_crop_cpm_weights(sd, dtype, front, maps: int, rows: int, columns: int) 
                         "fc": lin(f"Mconv6_stage{t}"), "out": lin(f"Mconv7_stage{t}", pad)} for t in range(2, 7)]}
 
 
-def crop_cpm_network(owner, ws, wts, prefix: str, front, crop, nc: int, side: int, hl: int, cat_cols: int, out2d, direct: bool) -> None:
-    """The CPM network of the face and hand stages for `nc` crops of side x side pixels, from the crop launch onward: the front end, the
-    feature copy into the concatenation [features 128 | heat | zeros] of `cat_cols` columns at hl x hl, stage 1 and the five 7x7 stages,
-    the last of which writes the fp32 view out2d [nc * hl * hl, heat columns].  crop(out): the stage's crop launch into out
-    [nc, side, side, 8]; prefix: "face" / "hand", in front of the stage names; ws: the dict that holds the pool and its plan (the buffer
-    plan and the per-stage launch counts depend on the order of the takes, gives and launches below)."""
-    from . import kernels as K
-    timed = owner._timed
-    plan = BufferPlan(ws, owner.dtype, out2d.device)   # the body's buffer plan: the same buffers in the same order on every pass
-    take, give = plan.take, plan.give
+class CropStage(PackedNetwork):
+    """A stage of one OpenposeAnnotator (`owner`) that runs a one-branch CPM network on crops around its keypoints: it runs in the
+    owner's dtype, on its device, within its max_activation_bytes, and its launches are stages of the owner's `timings`.  The four are
+    read through to the owner and cannot be set on the stage: set them on the annotator."""
 
-    def pw(x2d, wb, act, out2d, out_f32=False):
-        timed(prefix + "_pointwise", K.gemm, x2d, wb[0], bias=wb[1], act=act, out=out2d, out_f32=out_f32)
+    dtype = property(lambda self: self.owner.dtype)
+    device = property(lambda self: self.owner.device)
+    timings = property(lambda self: self.owner.timings)
+    max_activation_bytes = property(lambda self: self.owner.max_activation_bytes)
 
-    x = timed(prefix + "_crop", crop, take(nc, side, side, 8))
-    for layer, wb in zip(front, wts["front"]):
-        if layer == "pool":
-            y = timed(prefix + "_pool", K.maxpool2x2, x, take(nc, x.shape[1] // 2, x.shape[2] // 2, x.shape[3]))
-        else:   # split_k=False: the order of an output's sum is then the same whatever the number of crops
-            y = timed(prefix + "_conv", K.conv3x3, x, wb[0], bias=wb[1], act=K.ACT_RELU, out=take(*x.shape[:3], wb[0].shape[0]), split_k=False)
-        give(x)
-        x = y
-    feat = x
-    rows = nc * hl * hl
-    cat = take(nc, hl, hl, cat_cols)
-    cat2d = cat.view(rows, cat_cols)
-    cat2d.zero_()   # the columns behind the heat maps are read (against zero weights) and never written
-    timed(prefix + "_copy", K.copy_cols, feat.view(rows, 128), cat2d, 0)
-    heat_cols = cat2d[:, 128:128 + out2d.shape[1]]
-    fc = take(rows, 512)
-    pw(feat.view(rows, 128), wts["stage1"]["fc"], K.ACT_RELU, fc)
-    give(feat)
-    pw(fc, wts["stage1"]["out"], K.ACT_NONE, heat_cols)
-    give(fc)
-    cols = None if direct else take(rows, 49 * cat_cols)
-    for t, stage in enumerate(wts["stages"]):
-        a = cat
-        for i in range(5):
-            y = take(nc, hl, hl, 128)
-            timed(prefix + "_conv7", K.conv7x7, [a], [stage["conv7"][i][0]], biases=[stage["conv7"][i][1]], relu=True, outs=[y], direct=direct, cols=cols)
-            if i:
+    def _cpm_network(self, ws, wts, prefix: str, front, crop, nc: int, side: int, hl: int, cat_cols: int, out2d, direct: bool) -> None:
+        """The CPM network for `nc` crops of side x side pixels, from the crop launch onward: the front end, the feature copy into the
+        concatenation [features 128 | heat | zeros] of `cat_cols` columns at hl x hl, stage 1 and the five 7x7 stages, the last of which
+        writes the fp32 view out2d [nc * hl * hl, heat columns].  crop(out): the stage's crop launch into out [nc, side, side, 8];
+        prefix: "face" / "hand", in front of the stage names; ws: the dict that holds the pool and its plan (the buffer plan and the
+        per-stage launch counts depend on the order of the takes, gives and launches below)."""
+        from . import kernels as K
+        with self._pass(ws, out2d.device) as p:   # the body's buffer plan: the same buffers in the same order on every pass
+            take, give, launch = p.take, p.give, p.launch
+
+            def pw(x2d, wb, act, out2d, out_f32=False):
+                p.pointwise(prefix + "_pointwise", x2d, wb, act, out2d=out2d, out_f32=out_f32)
+
+            x = launch(prefix + "_crop", crop, take(nc, side, side, 8))
+            for layer, wb in zip(front, wts["front"]):
+                if layer == "pool":
+                    y = launch(prefix + "_pool", K.maxpool2x2, x, take(nc, x.shape[1] // 2, x.shape[2] // 2, x.shape[3]))
+                else:   # split_k=False: the order of an output's sum is then the same whatever the number of crops
+                    y = p.conv3x3(prefix + "_conv", x, wb, act=K.ACT_RELU, split_k=False)
+                give(x)
+                x = y
+            feat = x
+            rows = nc * hl * hl
+            cat = take(nc, hl, hl, cat_cols)
+            cat2d = cat.view(rows, cat_cols)
+            cat2d.zero_()   # the columns behind the heat maps are read (against zero weights) and never written
+            launch(prefix + "_copy", K.copy_cols, feat.view(rows, 128), cat2d, 0)
+            heat_cols = cat2d[:, 128:128 + out2d.shape[1]]
+            fc = take(rows, 512)
+            pw(feat, wts["stage1"]["fc"], K.ACT_RELU, fc)
+            give(feat)
+            pw(fc, wts["stage1"]["out"], K.ACT_NONE, heat_cols)
+            give(fc)
+            cols = None if direct else take(rows, 49 * cat_cols)
+            for t, stage in enumerate(wts["stages"]):
+                a = cat
+                for i in range(5):
+                    y = take(nc, hl, hl, 128)
+                    launch(prefix + "_conv7", K.conv7x7, [a], [stage["conv7"][i][0]], biases=[stage["conv7"][i][1]], relu=True, outs=[y], direct=direct, cols=cols)
+                    if i:
+                        give(a)
+                    a = y
+                fc = take(rows, 128)
+                pw(a, stage["fc"], K.ACT_RELU, fc)
                 give(a)
-            a = y
-        fc = take(rows, 128)
-        pw(a.view(rows, 128), stage["fc"], K.ACT_RELU, fc)
-        give(a)
-        if t == len(wts["stages"]) - 1:
-            pw(fc, stage["out"], K.ACT_NONE, out2d, out_f32=True)
-        else:
-            pw(fc, stage["out"], K.ACT_NONE, heat_cols)
-        give(fc)
-    if cols is not None:
-        give(cols)
-    give(cat)
-    ws["planned"] = True
+                if t == len(wts["stages"]) - 1:
+                    pw(fc, stage["out"], K.ACT_NONE, out2d, out_f32=True)
+                else:
+                    pw(fc, stage["out"], K.ACT_NONE, heat_cols)
+                give(fc)
+            if cols is not None:
+                give(cols)
+            give(cat)
 
 
 # ---- host-side tables ------------------------------------------------------------------------------------------------------------
@@ -403,23 +408,22 @@ class OpenposeAnnotator(AnnotatorBase):
         every later pass reuses the same ones)."""
         import torch
         from . import kernels as K
-        key = (n, h, w)
-        if key not in self._ws:
-            dev = self._device()
+
+        def make(dev):
             t = self.host_tables(h, w)
             g = t["geometry"]
             f32 = dict(dtype=torch.float32, device=dev)
             tables = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (*t["area_x"], *t["area_y"]))
-            self._ws[key] = {"geometry": g, "area": tables,
-                             "mx": torch.from_numpy(np.stack([t["ax"], t["gax"]]).astype(np.float32)).to(dev),
-                             "my": torch.from_numpy(np.stack([t["ay"], t["gay"]]).astype(np.float32)).to(dev),
-                             "sin": torch.from_numpy(t["sin"]).to(dev),
-                             "low": torch.empty((n, g["hl"], g["wl"], 64), **f32),
-                             "raw": torch.empty((n, 18, h, w), **f32), "smooth": torch.empty((n, 18, h, w), **f32), "paf": torch.empty((n, 38, h, w), **f32),
-                             "maps_ws": torch.empty(K.pose_maps_workspace_bytes(n, g["hl"], w), dtype=torch.uint8, device=dev),
-                             "decode": K.pose_decode_buffers(n, dev), "index": torch.empty((n, h, w), dtype=torch.int32, device=dev),
-                             "pool": [], "plan": [], "planned": False}
-        return self._ws[key]
+            return {"geometry": g, "area": tables,
+                    "mx": torch.from_numpy(np.stack([t["ax"], t["gax"]]).astype(np.float32)).to(dev),
+                    "my": torch.from_numpy(np.stack([t["ay"], t["gay"]]).astype(np.float32)).to(dev),
+                    "sin": torch.from_numpy(t["sin"]).to(dev),
+                    "low": torch.empty((n, g["hl"], g["wl"], 64), **f32),
+                    "raw": torch.empty((n, 18, h, w), **f32), "smooth": torch.empty((n, 18, h, w), **f32), "paf": torch.empty((n, 38, h, w), **f32),
+                    "maps_ws": torch.empty(K.pose_maps_workspace_bytes(n, g["hl"], w), dtype=torch.uint8, device=dev),
+                    "decode": K.pose_decode_buffers(n, dev), "index": torch.empty((n, h, w), dtype=torch.int32, device=dev)}
+
+        return self._workspace((n, h, w), make)
 
     # ---- input checks ----------------------------------------------------------------------------------------------------------
     def _check_size(self, h: int, w: int) -> None:
@@ -437,72 +441,69 @@ class OpenposeAnnotator(AnnotatorBase):
         wts = self._weights(src.device)
         n = src.shape[0]
         g = ws["geometry"]
-        plan = BufferPlan(ws, self.dtype, src.device)
-        take, give, timed = plan.take, plan.give, self._timed
+        with self._pass(ws, src.device) as p:
+            take, give, launch = p.take, p.give, p.launch
 
-        def conv3(x, wb):
-            # split_k=False: the order of an output's sum is then the same whatever the number of frames
-            y = timed("conv", K.conv3x3, x, wb[0], bias=wb[1], act=K.ACT_RELU, out=take(*x.shape[:3], wb[0].shape[0]), split_k=False)
-            return y
+            def conv3(x, wb):   # split_k=False: the order of an output's sum is then the same whatever the number of frames
+                return p.conv3x3("conv", x, wb, act=K.ACT_RELU, split_k=False)
 
-        def pw(x2d, wb, act, out2d, out_f32=False):
-            timed("pointwise", K.gemm, x2d, wb[0], bias=wb[1], act=act, out=out2d, out_f32=out_f32)
+            def pw(x, wb, act, out2d, out_f32=False):
+                p.pointwise("pointwise", x, wb, act, out2d=out2d, out_f32=out_f32)
 
-        x = timed("prep", K.pose_prep, src, ws["area"], g["hs"], g["ws"], take(n, g["hp"], g["wp"], 8))
-        for layer, wb in zip(FRONT, wts["front"]):
-            if layer == "pool":
-                y = timed("pool", K.maxpool2x2, x, take(n, x.shape[1] // 2, x.shape[2] // 2, x.shape[3]))
-            else:
-                y = conv3(x, wb)
-            give(x)
-            x = y
-        feat = x
-        hl, wl = g["hl"], g["wl"]
-        rows = n * hl * wl
-        cat = take(n, hl, wl, 192)
-        cat2d = cat.view(rows, 192)
-        timed("copy", K.copy_cols, feat.view(rows, 128), cat2d, 0)
-        col = {0: (128, 168), 1: (168, 192)}     # the columns of L1 (38 + 2) and L2 (19 + 5) in the concatenation
-        low2d = ws["low"][i0:i0 + n].view(rows, 64)
-        lcol = {0: (0, 40), 1: (40, 64)}         # ... and in the fp32 output
-        for br, s1 in enumerate(wts["stage1"]):
-            a = feat
-            for wb in s1["conv"]:
-                y = conv3(a, wb)
-                if a is not feat:
-                    give(a)
-                a = y
-            fc = take(rows, 512)
-            pw(a.view(rows, 128), s1["fc"], K.ACT_RELU, fc)
-            give(a)
-            pw(fc, s1["out"], K.ACT_NONE, cat2d[:, col[br][0]:col[br][1]])
-            give(fc)
-        give(feat)
-        direct = bool(dispatch.pose_conv7_direct)
-        cols = None if direct else take(rows, 49 * 192)
-        for t, stage in enumerate(wts["stages"]):
-            xs = [cat, cat]
-            for i in range(5):
-                outs = [take(n, hl, wl, 128), take(n, hl, wl, 128)]
-                timed("conv7", K.conv7x7, xs, [stage[0]["conv7"][i][0], stage[1]["conv7"][i][0]], biases=[stage[0]["conv7"][i][1], stage[1]["conv7"][i][1]],
-                      relu=True, outs=outs, direct=direct, cols=cols)
-                if i:
-                    give(xs[0]), give(xs[1])
-                xs = outs
-            last = t == len(wts["stages"]) - 1
-            for br in (0, 1):
-                fc = take(rows, 128)
-                pw(xs[br].view(rows, 128), stage[br]["fc"], K.ACT_RELU, fc)
-                give(xs[br])
-                if last:
-                    pw(fc, stage[br]["out"], K.ACT_NONE, low2d[:, lcol[br][0]:lcol[br][1]], out_f32=True)
+            x = launch("prep", K.pose_prep, src, ws["area"], g["hs"], g["ws"], take(n, g["hp"], g["wp"], 8))
+            for layer, wb in zip(FRONT, wts["front"]):
+                if layer == "pool":
+                    y = launch("pool", K.maxpool2x2, x, take(n, x.shape[1] // 2, x.shape[2] // 2, x.shape[3]))
                 else:
-                    pw(fc, stage[br]["out"], K.ACT_NONE, cat2d[:, col[br][0]:col[br][1]])
+                    y = conv3(x, wb)
+                give(x)
+                x = y
+            feat = x
+            hl, wl = g["hl"], g["wl"]
+            rows = n * hl * wl
+            cat = take(n, hl, wl, 192)
+            cat2d = cat.view(rows, 192)
+            launch("copy", K.copy_cols, feat.view(rows, 128), cat2d, 0)
+            col = {0: (128, 168), 1: (168, 192)}     # the columns of L1 (38 + 2) and L2 (19 + 5) in the concatenation
+            low2d = ws["low"][i0:i0 + n].view(rows, 64)
+            lcol = {0: (0, 40), 1: (40, 64)}         # ... and in the fp32 output
+            for br, s1 in enumerate(wts["stage1"]):
+                a = feat
+                for wb in s1["conv"]:
+                    y = conv3(a, wb)
+                    if a is not feat:
+                        give(a)
+                    a = y
+                fc = take(rows, 512)
+                pw(a, s1["fc"], K.ACT_RELU, fc)
+                give(a)
+                pw(fc, s1["out"], K.ACT_NONE, cat2d[:, col[br][0]:col[br][1]])
                 give(fc)
-        if cols is not None:
-            give(cols)
-        give(cat)
-        ws["planned"] = True
+            give(feat)
+            direct = bool(dispatch.pose_conv7_direct)
+            cols = None if direct else take(rows, 49 * 192)
+            for t, stage in enumerate(wts["stages"]):
+                xs = [cat, cat]
+                for i in range(5):
+                    outs = [take(n, hl, wl, 128), take(n, hl, wl, 128)]
+                    launch("conv7", K.conv7x7, xs, [stage[0]["conv7"][i][0], stage[1]["conv7"][i][0]], biases=[stage[0]["conv7"][i][1], stage[1]["conv7"][i][1]],
+                           relu=True, outs=outs, direct=direct, cols=cols)
+                    if i:
+                        give(xs[0]), give(xs[1])
+                    xs = outs
+                last = t == len(wts["stages"]) - 1
+                for br in (0, 1):
+                    fc = take(rows, 128)
+                    pw(xs[br], stage[br]["fc"], K.ACT_RELU, fc)
+                    give(xs[br])
+                    if last:
+                        pw(fc, stage[br]["out"], K.ACT_NONE, low2d[:, lcol[br][0]:lcol[br][1]], out_f32=True)
+                    else:
+                        pw(fc, stage[br]["out"], K.ACT_NONE, cat2d[:, col[br][0]:col[br][1]])
+                    give(fc)
+            if cols is not None:
+                give(cols)
+            give(cat)
 
     def _run(self, src, skeleton, control, rep, decode=True, face=None, hand=None):
         """face, hand: run that stage (None: when there is one and something is drawn)."""
@@ -516,8 +517,8 @@ class OpenposeAnnotator(AnnotatorBase):
         if ws["planned"] and min(step, n) > ws.get("chunk", 0):
             ws["pool"], ws["plan"], ws["planned"] = [], [], False   # a larger chunk than the plan was made for (max_activation_bytes grew)
         ws["chunk"] = max(ws.get("chunk", 0), min(step, n)) if ws["planned"] else min(step, n)
-        for i0 in range(0, n, step):
-            self._network(src[i0:i0 + step], ws, i0)
+        for i0, sl in self._chunks(n, step):
+            self._network(src[sl], ws, i0)
         self._timed("maps", K.pose_maps, ws["low"], ws["mx"], ws["my"], ws["raw"], ws["smooth"], ws["paf"], ws["maps_ws"])
         if decode:
             K.pose_decode(ws["raw"], ws["smooth"], ws["paf"], ws["decode"], stage=self._stage)

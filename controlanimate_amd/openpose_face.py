@@ -53,7 +53,7 @@ import os
 import numpy as np
 
 from . import openpose as _body
-from .annotator_base import check_state_dict, device_weights, load_state_dict
+from .annotator_base import check_state_dict
 from .openpose import bare_keys  # noqa: F401  (one function for the three checkpoints)
 
 WEIGHTS_NAME = "facenet.pth"
@@ -208,28 +208,27 @@ def pack_face_weights(sd, dtype) -> dict:
     return _body.pack_crop_cpm_weights(sd, dtype, FRONT, FACE_PARTS, FACE_MAPS, CAT - 128)
 
 
-class FaceStage:
+class FaceStage(_body.CropStage):
     """The face stage of one OpenposeAnnotator (`owner`: its dtype, max_activation_bytes and timings are used).  `run` starts from given
     keypoints and people tensors, so tests -- and a later hand stage -- can plant them."""
+
+    WEIGHTS_NAME = WEIGHTS_NAME
 
     def __init__(self, owner, state_dict_or_path, max_faces: int = 2):
         if not 1 <= int(max_faces) <= 64:
             raise ValueError(f"max_faces={max_faces} (1 .. 64)")
-        sd = load_state_dict(state_dict_or_path, WEIGHTS_NAME) if isinstance(state_dict_or_path, (str, os.PathLike)) else state_dict_or_path
+        sd = self._load(state_dict_or_path) if isinstance(state_dict_or_path, (str, os.PathLike)) else state_dict_or_path
         sd = bare_keys(sd)
         check_face_state_dict(sd)
         self.owner, self.max_faces = owner, int(max_faces)
         self._host = pack_face_weights(sd, owner.dtype)   # packed once, on the host
-        self._dev = None
         self._ws = {}
-
-    _weights = device_weights
 
     def chunk_crops(self, direct: bool) -> int:
         """Crops per pass through the network: as many as keep the largest 16-bit operand (conv1's output, or the im2col tensor of the
         alternative form of the 7x7 convolutions) within the owner's max_activation_bytes."""
         per_crop = max(FACE_SIZE * FACE_SIZE * 64 * 2, 0 if direct else FACE_HEAT * FACE_HEAT * 49 * CAT * 2)
-        limit = self.owner.max_activation_bytes
+        limit = self.max_activation_bytes
         if per_crop > limit:
             raise ValueError(f"a face crop alone exceeds what the kernels address ({per_crop} > {limit} bytes)")
         return limit // per_crop
@@ -239,15 +238,14 @@ class FaceStage:
         boxes / slots / points / overflow, the network's fp32 output, and the pool of activation buffers with its take / give plan."""
         import torch
         from . import kernels as K
-        key = (n, h, w, str(dev))
-        if key not in self._ws:
-            t = resize_tables(max(h, w))
-            tables = {k: (torch.from_numpy(v).to(dev) if isinstance(v, np.ndarray) else v) for k, v in t.items()}
-            self._ws[key] = {"tables": tables, "xmap": torch.from_numpy(pixel_map(w)).to(dev), "ymap": torch.from_numpy(pixel_map(h)).to(dev),
-                             "buf": K.face_buffers(n, self.max_faces, dev),
-                             "heat": torch.empty((n * self.max_faces, FACE_HEAT, FACE_HEAT, FACE_MAPS), dtype=torch.float32, device=dev),
-                             "pool": [], "plan": [], "planned": False}
-        return self._ws[key]
+
+        def make(dev):
+            tables = {k: (torch.from_numpy(v).to(dev) if isinstance(v, np.ndarray) else v) for k, v in resize_tables(max(h, w)).items()}
+            return {"tables": tables, "xmap": torch.from_numpy(pixel_map(w)).to(dev), "ymap": torch.from_numpy(pixel_map(h)).to(dev),
+                    "buf": K.face_buffers(n, self.max_faces, dev),
+                    "heat": torch.empty((n * self.max_faces, FACE_HEAT, FACE_HEAT, FACE_MAPS), dtype=torch.float32, device=dev)}
+
+        return self._workspace((n, h, w, str(dev)), make, dev)
 
     def _network(self, src, ws, c0: int, nc: int, direct: bool) -> None:
         """Crops c0 .. c0 + nc - 1 of the frames `src`: the resized input and the network, the 72 maps into ws["heat"][c0 : c0 + nc]."""
@@ -256,14 +254,13 @@ class FaceStage:
         def crop(out):
             return K.face_crop(src, ws["buf"]["slots"], ws["tables"], out, first=c0)
 
-        _body.crop_cpm_network(self.owner, ws, self._weights(src.device), "face", FRONT, crop, nc, FACE_SIZE, FACE_HEAT, CAT,
-                               ws["heat"][c0:c0 + nc].view(nc * FACE_HEAT * FACE_HEAT, FACE_MAPS), direct)
+        self._cpm_network(ws, self._weights(src.device), "face", FRONT, crop, nc, FACE_SIZE, FACE_HEAT, CAT,
+                          ws["heat"][c0:c0 + nc].view(nc * FACE_HEAT * FACE_HEAT, FACE_MAPS), direct)
 
     def run(self, src, keypoints, people, overflow_in=None, direct: bool = True) -> dict:
         """frames uint8 [n, H, W, 3] on the device, keypoints int32 [n, 64, 18, 2], people int32 [n] (and the body's overflow int32 [n]) ->
         the stage's workspace: ["buf"] holds boxes, slots, points and overflow, ["heat"] the maps, ["xmap"] / ["ymap"] the draw's tables."""
         from . import kernels as K
-        owner = self.owner
         n, h, w, _ = src.shape
         ws = self.workspace(n, h, w, src.device)
         total = n * self.max_faces
@@ -272,8 +269,8 @@ class FaceStage:
             ws["pool"], ws["plan"], ws["planned"] = [], [], False   # the other form of the 7x7 convolutions, or a larger chunk than was planned
         ws["direct"] = bool(direct)
         ws["chunk"] = max(ws.get("chunk", 0), min(step, total)) if ws["planned"] else min(step, total)
-        owner._timed("face_boxes", K.face_boxes, keypoints, people, h, w, ws["buf"], overflow_in)
-        for c0 in range(0, total, step):
-            self._network(src, ws, c0, min(step, total - c0), direct)
-        owner._timed("face_peaks", K.face_peaks, ws["heat"], ws["buf"]["slots"], ws["buf"]["points"], h, w)
+        self._timed("face_boxes", K.face_boxes, keypoints, people, h, w, ws["buf"], overflow_in)
+        for c0, sl in self._chunks(total, step):
+            self._network(src, ws, c0, sl.stop - c0, direct)
+        self._timed("face_peaks", K.face_peaks, ws["heat"], ws["buf"]["slots"], ws["buf"]["points"], h, w)
         return ws

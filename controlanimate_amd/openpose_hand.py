@@ -55,7 +55,7 @@ import os
 import numpy as np
 
 from . import openpose as _body
-from .annotator_base import check_state_dict, device_weights, load_state_dict
+from .annotator_base import check_state_dict
 from .openpose import bare_keys
 from .openpose_face import FRONT, pixel_map
 
@@ -97,7 +97,7 @@ def check_hand_state_dict(sd) -> None:
 
 
 def load_hand_state_dict(path) -> dict:
-    return load_state_dict(path, WEIGHTS_NAME)
+    return HandStage._load(path)
 
 
 # ---- the resize choice on the host -------------------------------------------------------------------------------------------------------
@@ -205,29 +205,28 @@ HAND_STAGES = {"hand_boxes": 1, "hand_crop": 4, "hand_conv": 60, "hand_pool": 12
                "hand_peaks": 1}
 
 
-class HandStage:
+class HandStage(_body.CropStage):
     """The hand stage of one OpenposeAnnotator (`owner`: its dtype, max_activation_bytes and timings are used).  `run` starts from given
     keypoints and people tensors, so tests can plant them."""
+
+    WEIGHTS_NAME = WEIGHTS_NAME
 
     def __init__(self, owner, state_dict_or_path, max_hands: int = 2):
         if not 1 <= int(max_hands) <= 128:
             raise ValueError(f"max_hands={max_hands} (1 .. 128)")
-        sd = load_hand_state_dict(state_dict_or_path) if isinstance(state_dict_or_path, (str, os.PathLike)) else state_dict_or_path
+        sd = self._load(state_dict_or_path) if isinstance(state_dict_or_path, (str, os.PathLike)) else state_dict_or_path
         sd = bare_keys(sd)
         check_hand_state_dict(sd)
         self.owner, self.max_hands = owner, int(max_hands)
         self._host = pack_hand_weights(sd, owner.dtype)   # packed once, on the host
-        self._dev = None
         self._ws = {}
-
-    _weights = device_weights
 
     def chunk_crops(self, side: int, direct: bool) -> int:
         """Crops per pass through the network at one side: as many as keep the largest 16-bit operand (conv1's output -- 69 MB a crop at
         side 736 -- or the im2col tensor of the alternative form of the 7x7 convolutions) within the owner's max_activation_bytes."""
         m = side // 8
         per_crop = max(side * side * 64 * 2, 0 if direct else m * m * 49 * CAT * 2)
-        limit = self.owner.max_activation_bytes
+        limit = self.max_activation_bytes
         if per_crop > limit:
             raise ValueError(f"a hand crop alone exceeds what the kernels address ({per_crop} > {limit} bytes)")
         return limit // per_crop
@@ -238,17 +237,19 @@ class HandStage:
         buffers with a take / give plan per side (the largest side runs first, the others reuse its buffers)."""
         import torch
         from . import kernels as K
-        key = (n, h, w, str(dev))
-        if key not in self._ws:
+
+        def make(dev):
             total, side_max = n * self.max_hands, min(h, w)
             tables = [{k: (torch.from_numpy(v).to(dev) if isinstance(v, np.ndarray) else v) for k, v in resize_tables(s, side_max).items()} for s in SIDES]
-            pool = []
-            self._ws[key] = {"tables": tables, "mats": torch.from_numpy(map_matrices()).to(dev), "buf": K.hand_buffers(n, self.max_hands, dev),
-                             "blurred": torch.empty((total, side_max, side_max, 3), dtype=torch.uint8, device=dev),
-                             "heat": [torch.empty((total, m, m, HEAT_COLS), dtype=torch.float32, device=dev) for m in MAP_SIDES],
-                             "xmap": torch.from_numpy(pixel_map(w)).to(dev), "ymap": torch.from_numpy(pixel_map(h)).to(dev),
-                             "net": [{"pool": pool, "plan": [], "planned": False} for _ in SIDES]}
-        return self._ws[key]
+            return {"tables": tables, "mats": torch.from_numpy(map_matrices()).to(dev), "buf": K.hand_buffers(n, self.max_hands, dev),
+                    "blurred": torch.empty((total, side_max, side_max, 3), dtype=torch.uint8, device=dev),
+                    "heat": [torch.empty((total, m, m, HEAT_COLS), dtype=torch.float32, device=dev) for m in MAP_SIDES],
+                    "xmap": torch.from_numpy(pixel_map(w)).to(dev), "ymap": torch.from_numpy(pixel_map(h)).to(dev)}
+
+        ws = self._workspace((n, h, w, str(dev)), make, dev)
+        if "net" not in ws:   # one pool, and a plan per side on it
+            ws["net"] = [{"pool": ws["pool"], "plan": [], "planned": False} for _ in SIDES]
+        return ws
 
     def _network(self, src, ws, k: int, c0: int, nc: int, direct: bool, blur: bool) -> None:
         """Crops c0 .. c0 + nc - 1 at side SIDES[k]: the blurred, resized input and the network, the 24 map columns into ws["heat"][k]."""
@@ -258,26 +259,25 @@ class HandStage:
         def crop(out):
             return K.hand_crop(src, ws["buf"]["slots"], ws["tables"][k], ws["blurred"], out, first=c0, blur=blur)
 
-        _body.crop_cpm_network(self.owner, ws["net"][k], self._weights(src.device), "hand", FRONT, crop, nc, side, hl, CAT,
-                               ws["heat"][k][c0:c0 + nc].view(nc * hl * hl, HEAT_COLS), direct)
+        self._cpm_network(ws["net"][k], self._weights(src.device), "hand", FRONT, crop, nc, side, hl, CAT,
+                          ws["heat"][k][c0:c0 + nc].view(nc * hl * hl, HEAT_COLS), direct)
 
     def run(self, src, keypoints, people, overflow_in=None, direct: bool = True) -> dict:
         """frames uint8 [n, H, W, 3] on the device, keypoints int32 [n, 64, 18, 2], people int32 [n] (and the overflow so far, int32 [n]) ->
         the stage's workspace: ["buf"] holds boxes, slots, points, peaks, mass, overflow and the raw / smooth planes, ["heat"] the maps."""
         from . import kernels as K
-        owner = self.owner
         n, h, w, _ = src.shape
         ws = self.workspace(n, h, w, src.device)
         total = n * self.max_hands
-        owner._timed("hand_boxes", K.hand_boxes, keypoints, people, h, w, ws["buf"], overflow_in)
+        self._timed("hand_boxes", K.hand_boxes, keypoints, people, h, w, ws["buf"], overflow_in)
         for k in reversed(range(len(SIDES))):   # the largest side first: it blurs the crops, and its buffers serve the smaller sides
             net, step = ws["net"][k], self.chunk_crops(SIDES[k], direct)
             if net["planned"] and (bool(net.get("direct", True)) != bool(direct) or min(step, total) > net.get("chunk", 0)):
                 net["plan"], net["planned"] = [], False   # the other form of the 7x7 convolutions, or a larger chunk than was planned
             net["direct"] = bool(direct)
             net["chunk"] = max(net.get("chunk", 0), min(step, total)) if net["planned"] else min(step, total)
-            for c0 in range(0, total, step):
-                self._network(src, ws, k, c0, min(step, total - c0), direct, blur=k == len(SIDES) - 1)
-        owner._timed("hand_maps", K.hand_maps, ws["heat"], ws["mats"], ws["buf"]["raw"], ws["buf"]["smooth"])
-        owner._timed("hand_peaks", K.hand_peaks, ws["buf"]["raw"], ws["buf"]["smooth"], ws["buf"], h, w)
+            for c0, sl in self._chunks(total, step):
+                self._network(src, ws, k, c0, sl.stop - c0, direct, blur=k == len(SIDES) - 1)
+        self._timed("hand_maps", K.hand_maps, ws["heat"], ws["mats"], ws["buf"]["raw"], ws["buf"]["smooth"])
+        self._timed("hand_peaks", K.hand_peaks, ws["buf"]["raw"], ws["buf"]["smooth"], ws["buf"], h, w)
         return ws

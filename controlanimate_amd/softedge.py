@@ -45,7 +45,8 @@ from __future__ import annotations
 
 import os
 
-from .annotator_base import AnnotatorBase, BufferPlan, check_state_dict as _check_state_dict
+from . import annotator_base as _base
+from .annotator_base import AnnotatorBase, check_state_dict as _check_state_dict, pack_conv, pack_pointwise
 
 WEIGHTS_NAME = "table5_pidinet.pth"
 LAYER_TYPES = ("cd", "ad", "rd", "cv") * 4       # carv4; layer 0 is init_block
@@ -183,9 +184,7 @@ def folded_layers(sd) -> dict:
 
 def pack_depthwise(w):
     """Depthwise weight [C, 1, k, k] -> [k * k, C]: tap ky * k + kx of every channel (ca_dwconv_k, ca_pdc_block)."""
-    if w.dim() != 4 or w.shape[1] != 1 or w.shape[2] != w.shape[3] or w.shape[2] not in (3, 5):
-        raise ValueError(f"a depthwise weight [C, 1, 3, 3] or [C, 1, 5, 5] is expected, got {tuple(w.shape)}")
-    return w.detach().reshape(w.shape[0], -1).t().contiguous()
+    return _base.pack_depthwise(w, (3, 5))
 
 
 class SoftedgeAnnotator(AnnotatorBase):
@@ -227,13 +226,13 @@ class SoftedgeAnnotator(AnnotatorBase):
             blks.append(b)
         levels = []
         for lv in f["levels"]:
-            levels.append({"cdcm1": (lin(lv["cdcm1"][0]).to(dtype), lv["cdcm1"][1].contiguous()),
+            levels.append({"cdcm1": pack_pointwise(lv["cdcm1"], dtype),
                            "cdcm2": torch.stack([w.permute(0, 2, 3, 1) for w in lv["cdcm2"]]).contiguous().to(dtype),   # [4, cout, ky, kx, cin]
                            "w1": lin(lv["csam1"][0]), "b1": lv["csam1"][1].contiguous(),
                            "w2": lv["csam2"].permute(0, 2, 3, 1)[0].contiguous(),                                     # [ky, kx, 4]
                            "wr": lv["reduce"][0].reshape(-1).contiguous(), "br": lv["reduce"][1].contiguous()})
         # packed once, on the host
-        self._host = {"init": f["init"].permute(0, 2, 3, 1).contiguous().to(dtype), "blocks": blks, "levels": levels,
+        self._host = {"init": pack_conv((f["init"], None), dtype)[0], "blocks": blks, "levels": levels,
                       "classifier": torch.cat([f["classifier"][0].reshape(-1), f["classifier"][1].reshape(-1)]).contiguous()}
         self._ws = {}   # (`timings` receives events under the keys of STAGES -- tools/bench_softedge.py)
 
@@ -249,15 +248,10 @@ class SoftedgeAnnotator(AnnotatorBase):
         asked for, and a pool of activation buffers that the layers of a pass take and give back in a fixed order (contents are never
         assumed; the first pass allocates them and every later pass reuses the same ones)."""
         import torch
-        key = (n, h, w)
-        if key not in self._ws:
-            dev = self._device()
-            chunk = min(n, self.chunk_frames(h, w))
-            self._ws[key] = {"sides": [torch.empty((n, h >> k, w >> k), dtype=torch.float32, device=dev) for k in range(4)],
-                             "logit": torch.empty((n, h, w), dtype=torch.float32, device=dev),
-                             "scratch": torch.empty(5 * chunk * h * w, dtype=torch.float32, device=dev),
-                             "pool": [], "plan": [], "planned": False, "fused": None}
-        return self._ws[key]
+        return self._workspace((n, h, w), lambda dev: {
+            "sides": [torch.empty((n, h >> k, w >> k), dtype=torch.float32, device=dev) for k in range(4)],
+            "logit": torch.empty((n, h, w), dtype=torch.float32, device=dev),
+            "scratch": torch.empty(5 * min(n, self.chunk_frames(h, w)) * h * w, dtype=torch.float32, device=dev), "fused": None})
 
     # ---- input checks ----------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -277,61 +271,52 @@ class SoftedgeAnnotator(AnnotatorBase):
         fused = bool(dispatch.pdc_block_fused)
         if ws["fused"] != fused:   # the other form takes other buffers: plan again
             ws["planned"], ws["fused"] = False, fused
-        plan = BufferPlan(ws, self.dtype, src.device)   # the same buffers in the same order on every pass
-        take, give, timed = plan.take, plan.give, self._timed
+        with self._pass(ws, src.device) as p:   # the same buffers in the same order on every pass
+            take, give, launch, pw = p.take, p.give, p.launch, p.pointwise
 
-        def side(level, x):
-            lv = wts["levels"][level]
-            nn, hh, ww, cc = x.shape
-            m = nn * hh * ww
-            r = timed("relu", K.relu, x, take(nn, hh, ww, cc))
-            t = take(nn, hh, ww, 32)
-            timed("pointwise", K.gemm, r.view(m, cc), lv["cdcm1"][0], bias=lv["cdcm1"][1], out=t.view(m, 32))
-            give(r)
-            f = timed("cdcm", K.cdcm_dil4, t, lv["cdcm2"], take(nn, hh, ww, 32))
-            give(t)
-            timed("csam", K.csam_reduce, f, lv["w1"], lv["b1"], lv["w2"], lv["wr"], lv["br"], side=ws["sides"][level][i0:i0 + nn], scratch=ws["scratch"])
-            give(f)
+            def side(level, x):
+                lv = wts["levels"][level]
+                r = launch("relu", K.relu, x, take(*x.shape))
+                t = pw("pointwise", r, lv["cdcm1"])
+                give(r)
+                f = launch("cdcm", K.cdcm_dil4, t, lv["cdcm2"], take(*t.shape))
+                give(t)
+                launch("csam", K.csam_reduce, f, lv["w1"], lv["b1"], lv["w2"], lv["wr"], lv["br"], side=ws["sides"][level][i0:i0 + n], scratch=ws["scratch"])
+                give(f)
 
-        x = timed("prep", K.softedge_prep, src, take(n, h, w, 8))
-        y = timed("init", K.conv3x3, x, wts["init"], out=take(n, h, w, 64))
-        give(x)
-        x, level = y, 0
-        for (_, _, _, cout, strided), blk in zip(blocks(), wts["blocks"]):
-            nn, hh, ww, cc = x.shape
-            if strided:
-                side(level, x)
-                level += 1
-                p = timed("pool", K.maxpool2x2, x, take(nn, hh // 2, ww // 2, cc))
-                give(x)
-                d = timed("depthwise", K.dwconv_k, p, blk["dw"], relu=True, out=take(*p.shape))
-                m = nn * (hh // 2) * (ww // 2)
-                y = take(nn, hh // 2, ww // 2, blk["pw"].shape[0])
-                timed("pointwise", K.gemm, d.view(m, cc), blk["pw"], a2=p.view(m, cc), bias=blk["bias"], out=y.view(m, -1))
-                give(d)
-                give(p)
-            elif fused and K.pdc_block_supported(cc, 3 if blk["dw"].shape[0] == 9 else 5):
-                y = timed("block", K.pdc_block, x, blk["dw"], blk["pw"], out=take(nn, hh, ww, cc), fused=True)
-                give(x)
-            else:
-                d = timed("depthwise", K.dwconv_k, x, blk["dw"], relu=True, out=take(nn, hh, ww, cc))
-                m = nn * hh * ww
-                y = take(nn, hh, ww, cc)
-                timed("pointwise", K.gemm, d.view(m, cc), blk["pw"], residual=x.view(m, cc), out=y.view(m, cc))
-                give(d)
-                give(x)
-            x = y
-        side(level, x)
-        give(x)
-        ws["planned"] = True
+            x = launch("prep", K.softedge_prep, src, take(n, h, w, 8))
+            y = p.conv3x3("init", x, (wts["init"], None))
+            give(x)
+            x, level = y, 0
+            for (_, _, _, cout, strided), blk in zip(blocks(), wts["blocks"]):
+                nn, hh, ww, cc = x.shape
+                if strided:
+                    side(level, x)
+                    level += 1
+                    pl = launch("pool", K.maxpool2x2, x, take(nn, hh // 2, ww // 2, cc))
+                    give(x)
+                    d = launch("depthwise", K.dwconv_k, pl, blk["dw"], relu=True, out=take(*pl.shape))
+                    y = pw("pointwise", d, (blk["pw"], blk["bias"]), a2=pl)
+                    give(d)
+                    give(pl)
+                elif fused and K.pdc_block_supported(cc, 3 if blk["dw"].shape[0] == 9 else 5):
+                    y = launch("block", K.pdc_block, x, blk["dw"], blk["pw"], out=take(nn, hh, ww, cc), fused=True)
+                    give(x)
+                else:
+                    d = launch("depthwise", K.dwconv_k, x, blk["dw"], relu=True, out=take(nn, hh, ww, cc))
+                    y = pw("pointwise", d, (blk["pw"], None), residual=x)
+                    give(d)
+                    give(x)
+                x = y
+            side(level, x)
+            give(x)
 
     def _run(self, src, edges, control, rep, logit=False):
         from . import kernels as K
         n, h, w, _ = src.shape
         ws = self.workspace(n, h, w)
-        step = self.chunk_frames(h, w)
-        for i0 in range(0, n, step):
-            self._network(src[i0:i0 + step], ws, i0)
+        for i0, sl in self._chunks(n, self.chunk_frames(h, w)):
+            self._network(src[sl], ws, i0)
         self._timed("fuse", K.softedge_fuse, ws["sides"], self._weights(src.device)["classifier"], safe=self.safe, logit=ws["logit"] if logit else None,
                     edges=edges, control=control, rep=rep)
         return ws
