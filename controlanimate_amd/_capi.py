@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("CA_HIP_LIB") or os.path.join(_HERE, "csrc", "libcontr
 CA_BF16, CA_F16 = 0, 1
 CA_F32 = 2  # control tensor of ca_canny_emit / ca_hed_fuse only
 CA_ACT_NONE, CA_ACT_SILU = 0, 1
+CA_ACT_QUICK_GELU, CA_ACT_GELU = 2, 3  # the CLIP MLPs (clip.py)
 CA_ACT_RELU = 4  # the VGG stack of the HED annotator (hed.py)
 CA_ACT_RELU6 = 5  # the MobileNetV2 backbone of the M-LSD annotator (mlsd.py)
 CA_ACT_LEAKY02 = 6  # LeakyReLU(0.2): the U-Net and the SFT branches of the GFPGAN face restorer (gfpgan.py)

@@ -38,7 +38,12 @@ def test_library_exports_every_declared_symbol(capi):
 
 def test_ctypes_structs_match_c_layout(capi):
     structs = {"ca_gemm_args": capi.GemmArgs, "ca_conv_args": capi.ConvArgs, "ca_groupnorm_args": capi.GroupNormArgs,
-               "ca_layernorm_args": capi.LayerNormArgs, "ca_attn_args": capi.AttnArgs}
+               "ca_layernorm_args": capi.LayerNormArgs, "ca_attn_args": capi.AttnArgs, "ca_ff_args": capi.FfArgs, "ca_tattn_args": capi.TattnArgs,
+               "ca_xattn_args": capi.XattnArgs, "ca_conv3x3_narrow_args": capi.ConvNarrowArgs, "ca_perceiver_attn_args": capi.PerceiverAttnArgs,
+               "ca_modconv_args": capi.ModconvArgs, "ca_conv7x7_args": capi.Conv7x7Args}
+    unlisted = [c.__name__ for c in vars(capi).values() if isinstance(c, type) and issubclass(c, C.Structure) and c is not C.Structure
+                and c not in structs.values()]
+    assert not unlisted, f"{unlisted}: every ctypes.Structure of _capi needs its C name in this table"
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){"]
     for cname, st in structs.items():
         lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')

@@ -142,6 +142,29 @@ def test_gemm_rejects_bad_args():
         k.gemm(a, w)
 
 
+def test_wrong_operands_are_rejected_by_name_before_any_launch():
+    """The front end's own checks on real device tensors: each raises CAHipError naming the entry and the operand, and the
+    sentinel-filled output is untouched afterwards."""
+    k = _k()
+    from controlanimate_amd._capi import CAHipError
+    x = rnd(1, 4, 8, 16, dtype=torch.float16, seed=1).to(DEV)
+    w, bias = rnd(9, 16, dtype=torch.float16, seed=2).to(DEV), torch.zeros(16, device=DEV)
+    short = torch.full((1, 3, 8, 16), 7.0, dtype=torch.float16, device=DEV)  # one row short
+    with pytest.raises(CAHipError, match=r"ca_dwconv3x3: out must be float16 \[1, 4, 8, 16\], contiguous; got float16 \[1, 3, 8, 16\]"):
+        k.dwconv3x3(x, w, bias, out=short)
+    strided = rnd(1, 4, 8, 32, dtype=torch.float16, seed=3).to(DEV)[..., ::2]
+    full = torch.full((1, 4, 8, 16), 7.0, dtype=torch.float16, device=DEV)
+    with pytest.raises(CAHipError, match=r"ca_relu: x must be contiguous; got float16 \[1, 4, 8, 16\] with strides"):
+        k.relu(strided, out=full)
+    frames = torch.zeros((1, 4, 8, 3), dtype=torch.uint8, device=DEV)
+    prepped = torch.full((1, 4, 8, 8), 7.0, dtype=torch.float16, device=DEV)
+    with pytest.raises(CAHipError, match=r"ca_hed_prep: norm is not on the device"):
+        k.hed_prep(frames, torch.zeros(3), prepped)
+    torch.cuda.synchronize()
+    for out in (short, full, prepped):
+        assert bool((out == 7.0).all())
+
+
 # ------------------------------------------------------------------------------------ conv
 CONV_CASES = [
     # images, h, w, cin1, cin2, cout, stride, upsample, bias, rowbias, residual, act, out_f32
